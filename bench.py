@@ -118,6 +118,10 @@ def parse_args(argv=None):
                     help="N=1, config 2: skip the legs behind the headline (configs 4 and 5, cold context, random cameras, split rehearsal)")
     ap.add_argument("--extras-steps", type=int, default=20, help="timed launches of each `configs` leg and of the `cold` leg")
     ap.add_argument("--launcher-dry-run", action="store_true", help="--gpus N without WORLD_SIZE: print the child command line and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write the frame of the last timed step as DIR/frame.npy (float32 H x W x 4); a frame over 64 MB as a "
+                         "fixed seeded sample of its pixels, DIR/frame_sample.npy (float32 n x 4) + DIR/frame_sample_index.npy (float64 "
+                         "row-major pixel indices)")
     return ap.parse_args(argv)
 
 
@@ -562,6 +566,26 @@ def _trace(msg):
         print('[bench] ' + msg, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21     # 32 MB of RGBA32F + 16 MB of float64 indices
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what the timed path hands its caller (the RGBA32F frame of its last step), for output-by-output
+    comparison of two builds.  The inputs are the same from run to run (fixed scene and camera); so is the sample."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    pixels = frame.reshape(-1, frame.shape[-1])
+    index = np.sort(np.random.default_rng(0).choice(len(pixels), DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), pixels[index])
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), index.astype(np.float64))
+
+
 def median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2] if xs else None
@@ -797,6 +821,8 @@ def main(argv=None):
     _trace(f'timed region done: {elapsed:.6f} s')
     if img is not None:
         img = img.clone()                                # the legs below reuse the frame buffers
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, img.cpu().numpy())
     latency = None
     if use_comm:
         # single-frame latency of the split: one frame per collective, the host waits for the assembled frame before it

@@ -1429,27 +1429,39 @@ def test_plain_cpp_example_renders_config1(tmp_path):
     assert out.stat().st_size == len(b"P6\n512 512\n255\n") + 512 * 512 * 3
 
 
-def test_reference_host_stack_drives_the_hip_path(orc, scenes, camera, tmp_path):
-    """oracle/_ref/dropin_test = the REFERENCE's compiled OctreeVoxel.cpp/Camera.cpp (+ its headers and glm) linked
-    with this repo's RayTracerBVH.cpp built with -DRTO_REFERENCE_HEADERS; it follows main.cpp's call sequence.
-    Built only where /root/reference exists (make -C oracle dropin); the binary travels to the GPU box."""
-    import os
+def test_reference_host_stack_drives_the_hip_path(ctx, orc, scenes, camera, golden, tmp_path):
+    """What the REFERENCE's host stack hands the HIP path in main.cpp's sphere scene -- the 64^3 shell sphere's octree from its
+    compiled createOctreeFromVoxelGrid + setOctree numbering and its Camera(0.5, 0.7, 1.8), stored in
+    tests/golden/ref_random_grids.npz -- renders, through a frustum update as renderSceneComputeWithCulling(true) does, the
+    oracle's frame.  Where oracle/_ref/dropin_test was built (make -C oracle dropin: the reference's compiled
+    OctreeVoxel.cpp/Camera.cpp (+ its headers and glm) linked with this repo's RayTracerBVH.cpp built with
+    -DRTO_REFERENCE_HEADERS, following main.cpp's call sequence), that program's frame is checked too."""
     import subprocess
 
-    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "dropin_test")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/dropin_test not built (needs the reference checkout)")
     W, H = 400, 240
-    out = tmp_path / "frame.raw"
-    env = dict(os.environ, RTO_HIP_LIB=hip.lib_path())
-    p = subprocess.run([exe, "64", str(W), str(H), str(out)], env=env, capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "23561 nodes" in p.stdout
-    got = np.fromfile(out, dtype=np.float32).reshape(H, W, 4)
     s = scenes("sphere64")
     view, pos = camera("sphere")
     want, _ = oracle_frame(orc, s, view, pos, W, H)
-    assert_bit_exact(got, want, "reference host stack + HIP path")
+    z = golden("ref_random_grids.npz")
+    assert z["dropin_view"].tobytes() == np.asarray(view, np.float32).tobytes()
+    assert z["dropin_pos"].tobytes() == np.asarray(pos, np.float32).tobytes()
+    ref_nodes = z["dropin_nodes"]
+    assert len(ref_nodes) == 23561
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(ref_nodes, z["dropin_min"], z["dropin_voxel"])
+    ctx.update_frustum(z["dropin_view"], 45.0, W / H, enable=True)
+    got = ctx.render_host(rto.make_frame(z["dropin_view"], z["dropin_pos"], W / H, 45.0, W, H))
+    assert_bit_exact(got, want, "reference octree and camera + HIP path")
+
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin_test")
+    if os.path.exists(exe):
+        out = tmp_path / "frame.raw"
+        env = dict(os.environ, RTO_HIP_LIB=hip.lib_path())
+        p = subprocess.run([exe, "64", str(W), str(H), str(out)], env=env, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stdout + p.stderr
+        assert "23561 nodes" in p.stdout
+        got = np.fromfile(out, dtype=np.float32).reshape(H, W, 4)
+        assert_bit_exact(got, want, "reference host stack + HIP path")
 
 
 @pytest.mark.parametrize("scene", ["sphere32", "odd", "calgary"])

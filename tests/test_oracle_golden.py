@@ -264,37 +264,38 @@ def test_probe_consumer_equals_the_reference(orc, scenes, golden, scene, cam):
         assert want[2] > 0 and abs(want[2] - want[1]) < abs(want[1] - want[0])        # converging towards 0.75 x the percentile
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/453-skeleton"), reason="reference checkout not present")
-def test_octree_ray_skip_against_live_reference_random_grids(orc):
-    """Where the reference sources exist: the oracle against the compiled octreeRaySkip itself, on random grids and rays."""
-    if not orc.refvr_available():
-        pytest.skip("oracle/_ref/libref_vr.so not built (make -C oracle refvr)")
-    rng = np.random.default_rng(321)
-    for dims, p in (((7, 5, 3), 0.5), ((16, 16, 16), 0.1), ((33, 9, 20), 0.7), ((2, 3, 1), 1.0)):
-        data = (rng.random((dims[2], dims[1], dims[0])) < p).astype(np.uint8)
-        g = orc.Grid(dims, np.array([0.5, -2.0, 3.0], np.float32), np.float32(0.3), data)
+def _random_grid(orc, data):
+    return orc.Grid((data.shape[2], data.shape[1], data.shape[0]), np.array([0.5, -2.0, 3.0], np.float32), np.float32(0.3), data)
+
+
+def test_octree_ray_skip_against_live_reference_random_grids(orc, golden):
+    """The oracle against the compiled octreeRaySkip itself, on random grids, rays and visibility maps: the reference's
+    distances are stored in tests/golden/ref_random_grids.npz (made by tests/golden/make_golden_random_grids.py); where
+    oracle/_ref/libref_vr.so was built, the live function is asked as well."""
+    z = golden("ref_random_grids.npz")
+    for i in range(4):
+        g = _random_grid(orc, z[f"skip_{i}_data"])
         nodes = orc.build_flat_octree(g)
-        ro = np.array([4.0, 1.5, -3.0], np.float32)
-        rd = rng.normal(size=(200, 3)).astype(np.float32)
-        rd /= np.linalg.norm(rd, axis=1, keepdims=True).astype(np.float32)
-        rd[:6] = np.array([[1, 0, 0], [0, -1, 0], [0, 0, 1], [1e-11, 1, 0], [-0.0, 0, -1], [1, 1e-9, -1e-11]], np.float32)
-        flags = (rng.random(len(nodes)) < 0.8).astype(np.uint8)
-        flags[0] = 1
-        for vis in (None, flags):
-            want = orc.ref_octree_ray_skip(g, ro, rd, 0.0, 1e30, visible=vis)
+        ro, rd, flags = z[f"skip_{i}_ro"], z[f"skip_{i}_rd"], z[f"skip_{i}_flags"]
+        assert len(flags) == len(nodes), i
+        for vis, key in ((None, "out"), (flags, "out_vis")):
+            want = z[f"skip_{i}_{key}"]
             got = orc.octree_ray_skip_many(nodes, g.min, g.voxel_size, ro, rd, 0.0, 1e30, visible=vis)
-            assert got.tobytes() == want.tobytes(), (dims, vis is not None)
+            assert got.tobytes() == want.tobytes(), (g.dims, key)
+            if orc.refvr_available():
+                assert orc.ref_octree_ray_skip(g, ro, rd, 0.0, 1e30, visible=vis).tobytes() == want.tobytes(), (g.dims, key, "live")
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/453-skeleton"), reason="reference checkout not present")
-def test_oracle_against_live_reference_random_grids(orc):
-    """Where the reference sources exist, compare against their compiled code directly on random grids."""
-    assert orc.ref_available()
-    rng = np.random.default_rng(99)
-    for dims, p in (((7, 5, 3), 0.5), ((16, 16, 16), 0.1), ((33, 9, 20), 0.9), ((1, 1, 1), 1.0), ((2, 3, 1), 0.0)):
-        data = (rng.random((dims[2], dims[1], dims[0])) < p).astype(np.uint8)
-        g = orc.Grid(dims, np.array([0.5, -2.0, 3.0], np.float32), np.float32(0.3), data)
-        assert orc.build_flat_octree(g).tobytes() == orc.ref_build_flat_octree(g).tobytes(), dims
+def test_oracle_against_live_reference_random_grids(orc, golden):
+    """The oracle's flat octree against the reference's compiled builder + setOctree numbering on random grids (stored in
+    tests/golden/ref_random_grids.npz; where oracle/_ref/libref.so was built, against the live code as well)."""
+    z = golden("ref_random_grids.npz")
+    for i in range(5):
+        g = _random_grid(orc, z[f"octree_{i}_data"])
+        want = z[f"octree_{i}_nodes"]
+        assert orc.build_flat_octree(g).tobytes() == want.tobytes(), g.dims
+        if orc.ref_available():
+            assert orc.ref_build_flat_octree(g).tobytes() == want.tobytes(), (g.dims, "live")
 
 
 def test_render_triangles_refuses_arrays_of_the_wrong_shape(orc, scenes):
