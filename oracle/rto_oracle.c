@@ -1023,11 +1023,11 @@ static inline int ray_triangle(v3 ro, v3 rd, const float* T, float* tOut) {
     return 1;
 }
 
-typedef struct { int hit; int steps; float t; v3 normal; } tri_result;
+typedef struct { int hit; int steps; int tri; float t; v3 normal; } tri_result;
 
 static inline tri_result trace_triangles(const orc_node* nodes, const float* tris, const int32_t* triOffset,
                                          const frame_consts* fc, v3 ro, v3 rd) {
-    tri_result r; r.hit = 0; r.steps = 0; r.t = 1e30f; r.normal = v3_(0, 0, 0);
+    tri_result r; r.hit = 0; r.steps = 0; r.tri = -1; r.t = 1e30f; r.normal = v3_(0, 0, 0);
     float closestT = 1e30f;
     int stack[128];
     int sp = 0;
@@ -1054,7 +1054,7 @@ static inline tri_result trace_triangles(const orc_node* nodes, const float* tri
                 if (ray_triangle(ro, rd, tris + (size_t)k * 12, &t) && t < bestT) { bestT = t; best = k; }
             }
             if (best >= 0) {
-                r.hit = 1; r.t = bestT;
+                r.hit = 1; r.t = bestT; r.tri = best;
                 r.normal = v3_(tris[(size_t)best * 12 + 9], tris[(size_t)best * 12 + 10], tris[(size_t)best * 12 + 11]);
                 break;
             }
@@ -1097,8 +1097,15 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
             if (v3_dot(nrm, rd) > 0.0f) nrm = v3_(-nrm.x, -nrm.y, -nrm.z);
             float ndotl = gmax(0.0f, v3_dot(nrm, nl));
             if (shadow) {
+                /* shadow origin: p = ro + rd t carries the rounding of t, which grows with the distance travelled; p is put
+                 * back on the hit triangle's plane (its height over the plane through v0, along the turned normal, taken
+                 * off) before the offset, so the origin's error is that of p's own coordinates; the offset is at least
+                 * 2^-18 max|p| (tiny voxels far from the origin: DESIGN.md, config 5) */
                 v3 p = v3_(ro.x + rd.x * tr.t, ro.y + rd.y * tr.t, ro.z + rd.z * tr.t);
-                v3 so = v3_(p.x + nrm.x * bias, p.y + nrm.y * bias, p.z + nrm.z * bias);
+                const float* v0 = tris + (size_t)tr.tri * 12;
+                float pm = gmax(gmax(fabsf(p.x), fabsf(p.y)), fabsf(p.z));
+                float h = (bias + pm * 0x1p-18f) - ((p.x - v0[0]) * nrm.x + (p.y - v0[1]) * nrm.y + (p.z - v0[2]) * nrm.z);
+                v3 so = v3_(p.x + nrm.x * h, p.y + nrm.y * h, p.z + nrm.z * h);
                 tri_result sh = trace_triangles(nodes, tris, triOffset, &fc, so, nl);
                 pops += (uint64_t)sh.steps;
                 if (sh.hit) ndotl = 0.0f;

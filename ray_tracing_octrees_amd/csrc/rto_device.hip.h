@@ -2211,10 +2211,10 @@ __device__ __forceinline__ bool ray_triangle(float ox, float oy, float oz, float
     return true;
 }
 
-struct TriHit { bool hit; int steps; float t; float nx, ny, nz; };
+struct TriHit { bool hit; int steps; int tri; float t; float nx, ny, nz; };
 
 __device__ __forceinline__ TriHit trace_triangles(const RenderParams& P, const TriScene& S, const Ray& r) {
-    TriHit h; h.hit = false; h.steps = 0; h.t = 1e30f; h.nx = h.ny = h.nz = 0.f;
+    TriHit h; h.hit = false; h.steps = 0; h.tri = -1; h.t = 1e30f; h.nx = h.ny = h.nz = 0.f;
     int stack[128];
     int sp = 0;
     stack[sp++] = 0;
@@ -2237,7 +2237,7 @@ __device__ __forceinline__ TriHit trace_triangles(const RenderParams& P, const T
                 if (ray_triangle(r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, S.tris + (size_t)k * 12, t) && t < bestT) { bestT = t; best = k; }
             }
             if (best >= 0) {
-                h.hit = true; h.t = bestT;
+                h.hit = true; h.t = bestT; h.tri = best;
                 h.nx = S.tris[(size_t)best * 12 + 9]; h.ny = S.tris[(size_t)best * 12 + 10]; h.nz = S.tris[(size_t)best * 12 + 11];
                 break;
             }
@@ -2278,8 +2278,12 @@ __global__ __launch_bounds__(kBlock) void k_trace_triangles(RenderParams P, TriS
             if (shadow) {
                 const float bias = P.voxelSize * 1e-3f;
                 const float hx = r.ox + r.dx * h.t, hy = r.oy + r.dy * h.t, hz = r.oz + r.dz * h.t;
+                // back on the hit triangle's plane, then the offset
+                const float* v0 = S.tris + (size_t)h.tri * 12;
+                const float hm = gmax(gmax(__builtin_fabsf(hx), __builtin_fabsf(hy)), __builtin_fabsf(hz));
+                const float hb = (bias + hm * 0x1p-18f) - ((hx - v0[0]) * nx + (hy - v0[1]) * ny + (hz - v0[2]) * nz);
                 Ray s;
-                s.ox = hx + nx * bias; s.oy = hy + ny * bias; s.oz = hz + nz * bias;
+                s.ox = hx + nx * hb; s.oy = hy + ny * hb; s.oz = hz + nz * hb;
                 s.dx = P.lightNeg[0]; s.dy = P.lightNeg[1]; s.dz = P.lightNeg[2];
                 s.ix = 1.0f / s.dx; s.iy = 1.0f / s.dy; s.iz = 1.0f / s.dz;
                 const TriHit sh = trace_triangles(P, S, s);
@@ -2461,8 +2465,12 @@ __global__ __launch_bounds__(kBlock) void k_trace_packed_triangles(RenderParams 
             if (shadow) {
                 const float bias = P.voxelSize * 1e-3f;
                 const float hx = r.ox + r.dx * h.t, hy = r.oy + r.dy * h.t, hz = r.oz + r.dz * h.t;
+                // back on the hit triangle's plane, then the offset
+                const float* v0 = S.tris + (size_t)h.tri * 12;
+                const float hm = gmax(gmax(__builtin_fabsf(hx), __builtin_fabsf(hy)), __builtin_fabsf(hz));
+                const float hb = (bias + hm * 0x1p-18f) - ((hx - v0[0]) * nx + (hy - v0[1]) * ny + (hz - v0[2]) * nz);
                 Ray s;
-                s.ox = hx + nx * bias; s.oy = hy + ny * bias; s.oz = hz + nz * bias;
+                s.ox = hx + nx * hb; s.oy = hy + ny * hb; s.oz = hz + nz * hb;
                 s.dx = P.lightNeg[0]; s.dy = P.lightNeg[1]; s.dz = P.lightNeg[2];
                 s.ix = 1.0f / s.dx; s.iy = 1.0f / s.dy; s.iz = 1.0f / s.dz;
                 const PTriHit sh = trace_packed_triangles(P, S, s, stk);
@@ -2821,7 +2829,11 @@ __device__ __forceinline__ void trace_tile_lean_triangles(const RenderParams& P,
                     if (shadow && (MODE == kModeSteps || ndotl > 0.0f)) {
                         const float bias = G.vs * 1e-3f;
                         const float hx = r.ox + r.dx * bestT, hy = r.oy + r.dy * bestT, hz = r.oz + r.dz * bestT;
-                        r.ox = hx + nx * bias; r.oy = hy + ny * bias; r.oz = hz + nz * bias;
+                        // back on the hit triangle's plane, then the offset (see k_trace_triangles)
+                        const float* v0 = Sc.tris + (size_t)best * 12;
+                        const float hm = gmax(gmax(__builtin_fabsf(hx), __builtin_fabsf(hy)), __builtin_fabsf(hz));
+                        const float hb = (bias + hm * 0x1p-18f) - ((hx - v0[0]) * nx + (hy - v0[1]) * ny + (hz - v0[2]) * nz);
+                        r.ox = hx + nx * hb; r.oy = hy + ny * hb; r.oz = hz + nz * hb;
                         r.dx = lnx; r.dy = lny; r.dz = lnz;
                         r.ix = lix; r.iy = liy; r.iz = liz;
                         K = exact_patterns3(lsx, lsy, lsz);
