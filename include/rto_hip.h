@@ -64,7 +64,7 @@ typedef struct rto_partition {
 /* Which traversal kernel runs. AUTO = PACKED when the uploaded array is a
  * canonical BFS octree (what setOctree produces), else GENERIC. */
 #define RTO_KERNEL_AUTO    0
-#define RTO_KERNEL_GENERIC 1       /* 60-byte nodes, explicit child indices, per-thread stack[128] */
+#define RTO_KERNEL_GENERIC 1       /* 60-byte nodes, explicit child indices, per-thread stack[141] */
 #define RTO_KERNEL_PACKED  2       /* 8-byte child descriptors, LDS level stack, branch-free O(1)-ascent loop with the pop
                                     * count rebuilt once per ray after the loop (k_trace_lean) */
 #define RTO_KERNEL_PACKED_V1 3     /* first form of the packed kernel (level-by-level ascent); kept for A/B runs */
@@ -98,7 +98,10 @@ int  rto_device_name(const rto_context* ctx, char* buf, size_t buflen);
 /* ---- octree upload --------------------------------------------------------
  * replaces: glBufferData(GL_SHADER_STORAGE_BUFFER, numNodes*sizeof(GPUNodes), ...) in
  * RayTracerBVH::setOctree (S/RayTracerBVH.cpp:495-504).  The array is copied; the
- * library additionally repacks canonical arrays into child descriptors. */
+ * library additionally repacks canonical arrays into child descriptors.  Refused:
+ * a child index outside the array (RTO_E_INVALID); a cycle, a node larger than
+ * 2^20 voxels, or a walk from node 0 that could hold more than 7*20+1 stack
+ * entries (RTO_E_UNSUPPORTED).  Canonical octrees of depth <= 20 always pass. */
 int  rto_upload_octree(rto_context* ctx, const rto_node* nodes, int64_t num_nodes,
                        const float grid_min[3], float voxel_size);
 /* N4 -- replaces createOctreeFromVoxelGrid + the BFS of setOctree + the upload (S/OctreeVoxel.cpp:704-778,

@@ -35,7 +35,7 @@ class _Grid(C.Structure):
 class _Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("pops", C.c_uint64), ("hits", C.c_uint64),
                 ("capped", C.c_uint64), ("internal", C.c_uint64),
-                ("max_stack", C.c_uint32), ("pad", C.c_uint32)]
+                ("max_stack", C.c_uint32), ("overflow", C.c_uint32)]
 
 
 class _Camera(C.Structure):
@@ -268,7 +268,7 @@ def render(nodes, grid_min, voxel_size, view, cam_pos, aspect, fov_deg, W, H, ro
     st = _Stats()
     lib().orc_render(nodes.ctypes.data, len(nodes), _f32(grid_min), float(voxel_size), _f32(view), _f32(cam_pos),
                      float(aspect), float(fov_deg), W, H, y0, y1, out.ctypes.data, C.byref(st), nthreads)
-    stats = {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped", "internal", "max_stack")}
+    stats = {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped", "internal", "max_stack", "overflow")}
     return out, stats
 
 
@@ -279,7 +279,7 @@ def render_closest(nodes, grid_min, voxel_size, view, cam_pos, aspect, fov_deg, 
     st = _Stats()
     lib().orc_render_closest(nodes.ctypes.data, len(nodes), _f32(grid_min), float(voxel_size), _f32(view), _f32(cam_pos),
                              float(aspect), float(fov_deg), W, H, out.ctypes.data, C.byref(st), nthreads)
-    return out, {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped", "internal", "max_stack")}
+    return out, {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped", "internal", "max_stack", "overflow")}
 
 
 def render_steps(nodes, grid_min, voxel_size, view, cam_pos, aspect, fov_deg, W, H):
@@ -393,7 +393,7 @@ def render_triangles(nodes, tris, tri_offset, grid_min, voxel_size, view, cam_po
     lib().orc_render_triangles(nodes.ctypes.data, len(nodes), tris.ctypes.data, tri_offset.ctypes.data, _f32(grid_min),
                                float(voxel_size), _f32(view), _f32(cam_pos), float(aspect), float(fov_deg), W, H,
                                1 if shadow else 0, out.ctypes.data, C.byref(st), nthreads)
-    return out, {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped")}
+    return out, {k: getattr(st, k) for k in ("rays", "pops", "hits", "capped", "overflow")}
 
 
 def max_threads() -> int:

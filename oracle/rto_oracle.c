@@ -531,13 +531,13 @@ static inline int intersect_aabb(v3 ro, v3 rd, v3 bmin, v3 bmax, float* tNear, f
     return (*tNear <= *tFar && *tFar > 0.0f);
 }
 
-typedef struct { int hit; int steps; int max_sp; int internal; v3 normal; } trace_result;
+typedef struct { int hit; int steps; int max_sp; int internal; int overflow; v3 normal; } trace_result;
 
 static inline trace_result trace(const orc_node* nodes, const frame_consts* fc, v3 ro, v3 rd) {
     /* :239-327 intersectOctreeIterative */
-    trace_result r; r.hit = 0; r.steps = 0; r.max_sp = 1; r.internal = 0; r.normal = v3_(0, 0, 0);
+    trace_result r; r.hit = 0; r.steps = 0; r.max_sp = 1; r.internal = 0; r.overflow = 0; r.normal = v3_(0, 0, 0);
     float closestT = 1e30f;
-    int stack[128];
+    int stack[ORC_STACK_CAP];
     int sp = 0;
     stack[sp++] = 0;
     int traversalSteps = 0;
@@ -573,10 +573,13 @@ static inline trace_result trace(const orc_node* nodes, const frame_consts* fc, 
             continue;
         }
         r.internal++;
-        for (int i = 0; i < 8; i++) {
+        for (int i = 0; i < 8 && !r.overflow; i++) {
             int childIdx = node->child[i];
-            if (childIdx >= 0) stack[sp++] = childIdx;
+            if (childIdx < 0) continue;
+            if (sp == ORC_STACK_CAP) r.overflow = 1;
+            else stack[sp++] = childIdx;
         }
+        if (r.overflow) { r.hit = 0; break; }
         if (sp > r.max_sp) r.max_sp = sp;
     }
     r.steps = traversalSteps;
@@ -589,9 +592,9 @@ static inline trace_result trace(const orc_node* nodes, const frame_consts* fc, 
  * ties go to the leaf popped first).  Dead code upstream -- the only traversal rule of the reference this repo could not render
  * until round 4 (rto_render_closest_*).  steps: nodes popped (uncapped). */
 static inline trace_result trace_closest(const orc_node* nodes, const frame_consts* fc, v3 ro, v3 rd) {
-    trace_result r; r.hit = 0; r.steps = 0; r.max_sp = 1; r.internal = 0; r.normal = v3_(0, 0, 0);
+    trace_result r; r.hit = 0; r.steps = 0; r.max_sp = 1; r.internal = 0; r.overflow = 0; r.normal = v3_(0, 0, 0);
     float closestT = 1e30f;                                   /* :66 */
-    int stack[128];                                           /* :71 */
+    int stack[ORC_STACK_CAP];                                 /* :71 has 128: too few from depth 19 on */
     int sp = 0;
     stack[sp++] = 0;
     v3 gmn = v3_(fc->gridMin[0], fc->gridMin[1], fc->gridMin[2]);
@@ -622,10 +625,13 @@ static inline trace_result trace_closest(const orc_node* nodes, const frame_cons
             continue;
         }
         r.internal++;
-        for (int i = 0; i < 8; i++) {                         /* :125-129 */
+        for (int i = 0; i < 8 && !r.overflow; i++) {          /* :125-129 */
             int childIdx = node->child[i];
-            if (childIdx >= 0) stack[sp++] = childIdx;
+            if (childIdx < 0) continue;
+            if (sp == ORC_STACK_CAP) r.overflow = 1;
+            else stack[sp++] = childIdx;
         }
+        if (r.overflow) { r.hit = 0; break; }
         if (sp > r.max_sp) r.max_sp = sp;
     }
     return r;
@@ -662,10 +668,10 @@ void orc_render(const orc_node* nodes, int64_t n, const float gridMin[3], float 
     frame_setup(&fc, gridMin, voxelSize, view, camPos, aspect, fovDeg, W, H);
     v3 ro = v3_(camPos[0], camPos[1], camPos[2]);
     uint64_t pops = 0, hits = 0, capped = 0, internal = 0;
-    unsigned max_stack = 0;
+    unsigned max_stack = 0, overflow = 0;
     if (nthreads < 1) nthreads = 1;
 #ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,capped,internal) reduction(max:max_stack)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,capped,internal,overflow) reduction(max:max_stack)
 #endif
     for (int py = y0; py < y1; py++) {
         for (int px = 0; px < W; px++) {
@@ -675,13 +681,14 @@ void orc_render(const orc_node* nodes, int64_t n, const float gridMin[3], float 
             shade_store(&tr, out + ((size_t)py * W + px) * 4);
             pops += (uint64_t)tr.steps; hits += (uint64_t)tr.hit; internal += (uint64_t)tr.internal;
             capped += (uint64_t)(!tr.hit && tr.steps >= MAX_TRAVERSAL_STEPS);
+            overflow += (unsigned)tr.overflow;
             if ((unsigned)tr.max_sp > max_stack) max_stack = (unsigned)tr.max_sp;
         }
     }
     if (stats) {
         stats->rays = (uint64_t)W * (uint64_t)(y1 - y0);
         stats->pops = pops; stats->hits = hits; stats->capped = capped; stats->internal = internal;
-        stats->max_stack = max_stack; stats->pad = 0;
+        stats->max_stack = max_stack; stats->overflow = overflow;
     }
 }
 
@@ -694,10 +701,10 @@ void orc_render_closest(const orc_node* nodes, int64_t n, const float gridMin[3]
     frame_setup(&fc, gridMin, voxelSize, view, camPos, aspect, fovDeg, W, H);
     v3 ro = v3_(camPos[0], camPos[1], camPos[2]);
     uint64_t pops = 0, hits = 0, internal = 0;
-    unsigned max_stack = 0;
+    unsigned max_stack = 0, overflow = 0;
     if (nthreads < 1) nthreads = 1;
 #ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,internal) reduction(max:max_stack)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,internal,overflow) reduction(max:max_stack)
 #endif
     for (int py = 0; py < H; py++) {
         for (int px = 0; px < W; px++) {
@@ -706,13 +713,14 @@ void orc_render_closest(const orc_node* nodes, int64_t n, const float gridMin[3]
             trace_result tr = trace_closest(nodes, &fc, ro, rd);
             shade_store(&tr, out + ((size_t)py * W + px) * 4);
             pops += (uint64_t)tr.steps; hits += (uint64_t)tr.hit; internal += (uint64_t)tr.internal;
+            overflow += (unsigned)tr.overflow;
             if ((unsigned)tr.max_sp > max_stack) max_stack = (unsigned)tr.max_sp;
         }
     }
     if (stats) {
         stats->rays = (uint64_t)W * (uint64_t)H;
         stats->pops = pops; stats->hits = hits; stats->capped = 0; stats->internal = internal;
-        stats->max_stack = max_stack; stats->pad = 0;
+        stats->max_stack = max_stack; stats->overflow = overflow;
     }
 }
 
@@ -861,7 +869,7 @@ void orc_render_skip(const orc_node* nodes, int64_t n, const float gridMin[3], f
             const size_t pix = (size_t)py * W + px;
             if (outT) outT[pix] = t;
             if (!outRGBA) continue;
-            trace_result tr; tr.hit = 0; tr.steps = 0; tr.max_sp = 0; tr.internal = 0; tr.normal = v3_(0, 0, 0);
+            trace_result tr; tr.hit = 0; tr.steps = 0; tr.max_sp = 0; tr.internal = 0; tr.overflow = 0; tr.normal = v3_(0, 0, 0);
             if (t < 1e30f && leaf >= 0) {
                 const orc_node* nd = &nodes[leaf];
                 v3 nodeMin = v3_(gridMin[0] + (float)nd->x * voxelSize, gridMin[1] + (float)nd->y * voxelSize, gridMin[2] + (float)nd->z * voxelSize);
@@ -1023,13 +1031,13 @@ static inline int ray_triangle(v3 ro, v3 rd, const float* T, float* tOut) {
     return 1;
 }
 
-typedef struct { int hit; int steps; int tri; float t; v3 normal; } tri_result;
+typedef struct { int hit; int steps; int tri; int overflow; float t; v3 normal; } tri_result;
 
 static inline tri_result trace_triangles(const orc_node* nodes, const float* tris, const int32_t* triOffset,
                                          const frame_consts* fc, v3 ro, v3 rd) {
-    tri_result r; r.hit = 0; r.steps = 0; r.tri = -1; r.t = 1e30f; r.normal = v3_(0, 0, 0);
+    tri_result r; r.hit = 0; r.steps = 0; r.tri = -1; r.overflow = 0; r.t = 1e30f; r.normal = v3_(0, 0, 0);
     float closestT = 1e30f;
-    int stack[128];
+    int stack[ORC_STACK_CAP];
     int sp = 0;
     stack[sp++] = 0;
     int traversalSteps = 0;
@@ -1060,10 +1068,13 @@ static inline tri_result trace_triangles(const orc_node* nodes, const float* tri
             }
             continue;
         }
-        for (int i = 0; i < 8; i++) {
+        for (int i = 0; i < 8 && !r.overflow; i++) {
             int childIdx = node->child[i];
-            if (childIdx >= 0) stack[sp++] = childIdx;
+            if (childIdx < 0) continue;
+            if (sp == ORC_STACK_CAP) r.overflow = 1;
+            else stack[sp++] = childIdx;
         }
+        if (r.overflow) break;
     }
     r.steps = traversalSteps;
     return r;
@@ -1080,9 +1091,10 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
     v3 nl = v3_(-l.x, -l.y, -l.z);
     float bias = voxelSize * 1e-3f;
     uint64_t pops = 0, hits = 0, capped = 0;
+    unsigned overflow = 0;
     if (nthreads < 1) nthreads = 1;
 #ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,capped)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+:pops,hits,capped,overflow)
 #endif
     for (int py = 0; py < H; py++)
         for (int px = 0; px < W; px++) {
@@ -1091,6 +1103,7 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
             tri_result tr = trace_triangles(nodes, tris, triOffset, &fc, ro, rd);
             float* o = out + ((size_t)py * W + px) * 4;
             pops += (uint64_t)tr.steps;
+            overflow += (unsigned)tr.overflow;
             if (!tr.hit) { o[0] = o[1] = o[2] = 0.0f; o[3] = 1.0f; capped += (uint64_t)(tr.steps >= MAX_TRAVERSAL_STEPS); continue; }
             hits++;
             v3 nrm = tr.normal;
@@ -1108,9 +1121,10 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
                 v3 so = v3_(p.x + nrm.x * h, p.y + nrm.y * h, p.z + nrm.z * h);
                 tri_result sh = trace_triangles(nodes, tris, triOffset, &fc, so, nl);
                 pops += (uint64_t)sh.steps;
+                overflow += (unsigned)sh.overflow;
                 if (sh.hit) ndotl = 0.0f;
             }
             o[0] = 1.0f * ndotl + 0.1f; o[1] = 0.8f * ndotl + 0.1f; o[2] = 0.6f * ndotl + 0.1f; o[3] = 1.0f;
         }
-    if (stats) { stats->rays = (uint64_t)W * H; stats->pops = pops; stats->hits = hits; stats->capped = capped; stats->internal = 0; stats->max_stack = 0; stats->pad = 0; }
+    if (stats) { stats->rays = (uint64_t)W * H; stats->pops = pops; stats->hits = hits; stats->capped = capped; stats->internal = 0; stats->max_stack = 0; stats->overflow = overflow; }
 }

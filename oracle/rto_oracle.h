@@ -52,8 +52,13 @@ typedef struct orc_stats {
     uint64_t capped;       /* rays that ended because steps reached 512  */
     uint64_t internal;     /* internal nodes whose children were pushed  */
     uint32_t max_stack;    /* max stack pointer observed                 */
-    uint32_t pad;
+    uint32_t overflow;     /* rays whose walk would pass ORC_STACK_CAP   */
 } orc_stats;
+
+/* Stack of the node-by-node walks: 7 entries per level of a depth-20 octree, plus one (the library's kStackCap; its upload
+ * refuses arrays that could need more).  A walk that would pass it stops and is counted in orc_stats.overflow. */
+#define ORC_MAX_DEPTH 20
+#define ORC_STACK_CAP (7 * ORC_MAX_DEPTH + 1)
 
 /* ---- scene (S/main.cpp:337-372, 1052-1070, 376-422) ------------------- */
 void orc_generate_test_sphere(int dimX, int dimY, int dimZ, uint8_t* out);

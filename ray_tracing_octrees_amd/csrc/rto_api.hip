@@ -317,9 +317,8 @@ static bool build_descriptors(const rto_node* nodes, int64_t n, std::vector<uint
     const rto_node& root = nodes[0];
     rootSize = root.size; depth = 0;
     if (is_terminal(root) || root.x != 0 || root.y != 0 || root.z != 0) return false;
-    if (root.size < 2 || (root.size & (root.size - 1)) != 0) return false;
+    if (root.size < 2 || (root.size & (root.size - 1)) != 0 || root.size > (1 << kMaxDepth)) return false;
     while ((1 << depth) < root.size) depth++;
-    if (depth > kMaxDepth) return false;
     std::vector<int> rank((size_t)n + 1);   // rank[i] = internal nodes among [0, i)
     int r = 0;
     for (int64_t i = 0; i < n; i++) { rank[(size_t)i] = r; r += is_terminal(nodes[i]) ? 0 : 1; }
@@ -349,6 +348,48 @@ static bool build_descriptors(const rto_node* nodes, int64_t n, std::vector<uint
     return true;
 }
 
+// Stack entries the node-by-node walks (k_trace_generic, k_trace_closest, trace_triangles) need on an arbitrary array when every
+// slab test passes: need(leaf) = 1, need(v) = max(1, max over pushed children c of (children pushed before c) + need(c)) -- the
+// pushed siblings below c stay on the stack while c's subtree is walked.  7 d + 1 on a full octree of depth d.  Returns RTO_OK or
+// the refusal of rto_upload_octree (child index out of range, cycle, node larger than 2^kMaxDepth, need above kStackCap).
+static int walk_stack_need(rto_context* c, const rto_node* nodes, int64_t n, int& need) {
+    std::vector<int> nd((size_t)n, 0);                 // 0 unvisited, -1 on the current path, > 0 the node's need
+    std::vector<std::pair<int64_t, int>> path;         // (node, next child slot)
+    nd[0] = -1;
+    path.push_back({ 0, 0 });
+    while (!path.empty()) {
+        const int64_t u = path.back().first;
+        const rto_node& v = nodes[u];
+        if (v.size > (1 << kMaxDepth))
+            return fail(c, RTO_E_UNSUPPORTED, "rto_upload_octree: a node is larger than 2^20 voxels (octree deeper than 20 levels)");
+        int k = is_terminal(v) ? 8 : path.back().second;
+        for (; k < 8; k++) {
+            const int ch = v.child[k];
+            if (ch < 0) continue;
+            if (ch >= n) return fail(c, RTO_E_INVALID, "rto_upload_octree: child index outside the node array");
+            if (nd[(size_t)ch] == -1) return fail(c, RTO_E_UNSUPPORTED, "rto_upload_octree: the child indices form a cycle");
+            if (nd[(size_t)ch] == 0) break;
+        }
+        if (k < 8) {                                   // descend; slot k is looked at again (then finished) on the way back
+            path.back().second = k;
+            nd[(size_t)v.child[k]] = -1;
+            path.push_back({ v.child[k], 0 });
+            continue;
+        }
+        int m = 1, pushed = 0;
+        if (!is_terminal(v))
+            for (int i = 0; i < 8; i++)
+                if (v.child[i] >= 0) { m = std::max(m, pushed + nd[(size_t)v.child[i]]); pushed++; }
+        if (m > kStackCap)
+            return fail(c, RTO_E_UNSUPPORTED, "rto_upload_octree: a traversal of this array could hold more than " +
+                                                  std::to_string(kStackCap) + " stack entries (7 per level of a depth-20 octree, plus one)");
+        nd[(size_t)u] = m;
+        path.pop_back();
+    }
+    need = nd[0];
+    return RTO_OK;
+}
+
 static void bounds_from_nodes(const rto_node* nodes, int64_t n, const float grid_min[3], float voxel_size, rto_scene_bounds* b);   // rto_split.inc
 
 static int build_cells(rto_context* c);
@@ -359,6 +400,15 @@ int rto_upload_octree(rto_context* c, const rto_node* nodes, int64_t n, const fl
     if (!c) return RTO_E_INVALID;
     if (!nodes || n <= 0 || !grid_min) return fail(c, RTO_E_INVALID, "rto_upload_octree: empty node array");
     if (n > 0x7fffffff) return fail(c, RTO_E_INVALID, "rto_upload_octree: node indices are int32 (GPUNodes.child)");
+    std::vector<uint2> desc;
+    std::vector<int> firstChild;
+    int rootSize = 0, depth = 0;
+    const bool canonical = build_descriptors(nodes, n, desc, firstChild, rootSize, depth);
+    if (!canonical) {   // a canonical octree has depth <= kMaxDepth, hence needs at most kStackCap entries; any other array is walked first
+        int need = 0;
+        const int rc = walk_stack_need(c, nodes, n, need);
+        if (rc != RTO_OK) return rc;
+    }
     RTO_HIP(c, hipSetDevice(c->device));
     RTO_HIP(c, hipStreamSynchronize(c->stream));
     free_octree(c);
@@ -378,9 +428,8 @@ int rto_upload_octree(rto_context* c, const rto_node* nodes, int64_t n, const fl
             c->solidLo[a] = sb.solid_lo[a]; c->solidHi[a] = sb.solid_hi[a];
         }
     }
-    std::vector<uint2> desc;
-    std::vector<int> firstChild;
-    c->canonical = build_descriptors(nodes, n, desc, firstChild, c->rootSize, c->depth);
+    c->canonical = canonical;
+    c->rootSize = rootSize; c->depth = depth;
     if (c->canonical) {
         c->numInternal = (int64_t)desc.size();
         RTO_HIP(c, hipMalloc(&c->d_desc, desc.size() * sizeof(uint2)));

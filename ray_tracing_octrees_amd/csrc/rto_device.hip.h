@@ -5,7 +5,7 @@
 // produce bit-identical pixels:
 //
 //   k_trace_generic  walks the uploaded 60-byte GPUNodes array with explicit child
-//                    indices and a private stack[128] -- a direct statement of
+//                    indices and a private stack[kStackCap] -- a direct statement of
 //                    S/RT:239-327, used for arbitrary (e.g. user-compacted) arrays.
 //
 //   k_trace_packed   the MI355X path.  For canonical BFS octrees (what
@@ -20,7 +20,7 @@
 //                    advance the step counter, which is all S/RT:257-274 does for
 //                    them), and the per-ray stack is one 8-byte entry per tree LEVEL
 //                    in LDS ([level][lane], bank-conflict free) instead of
-//                    stack[128] per thread.
+//                    stack[kStackCap] per thread.
 //
 // Exactness contract (DESIGN.md "Numerics"): every float expression keeps the
 // operation order of the GLSL/glm source, the TU is compiled with
@@ -52,6 +52,10 @@ constexpr int kBlock = RTO_BLOCK;         // 4 waves, each owns one 8x8 pixel ti
 #define RTO_PERSIST_CHUNK 8       // launch slots a persistent wave takes per atomic (A/B builds: -DRTO_PERSIST_CHUNK=n)
 #endif
 constexpr int kMaxDepth = 20;             // log2(root size) supported by the packed kernel
+// Entries of the per-thread stacks of the node-by-node walks (generic, closest hit, triangles).  A LIFO walk that pushes up to 8
+// children holds at most 7 d + 1 entries on an octree of depth d; rto_upload_octree refuses every array whose walk could need
+// more, so no push can pass the end.
+constexpr int kStackCap = 7 * kMaxDepth + 1;
 
 // Where a traversal starts while a frustum update is active -- kept ON THE DEVICE (written by k_cull_desc, read by the traversal
 // kernels), so that rto_update_frustum needs no read-back and can be stream-captured.  Normally the root.  If the update
@@ -322,7 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_generic(RenderParams P, const 
     float shade = kShadeMiss;
     if (inImage && P.rootVisible) {
         Ray r = generate_ray(P, px, py);
-        int stack[128];                 // S/RT:247
+        int stack[kStackCap];           // S/RT:247 has 128: too few from depth 19 on
         int sp = 0;
         stack[sp++] = 0;
         const float closestT = 1e30f;   // S/RT:242; only ever written together with the break
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_closest(RenderParams P, const 
     float shade = kShadeMiss;
     if (inImage && P.rootVisible) {
         Ray r = generate_ray(P, px, py);
-        int stack[128];                 // S/RT:71
+        int stack[kStackCap];           // S/RT:71 (128 there)
         int sp = 0;
         stack[sp++] = 0;
         float closestT = 1e30f;         // S/RT:66
@@ -411,7 +415,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_closest(RenderParams P, const 
 #pragma unroll
             for (int i = 0; i < 8; i++) {                                                                    // S/RT:125-129
                 int c = nd.child[i];
-                if (c >= 0 && sp < 128) stack[sp++] = c;       // (a LIFO walk of an octree of depth d holds at most 7 d + 1 entries)
+                if (c >= 0) stack[sp++] = c;
             }
         }
         if (hit) shade = shade_term(P, r, bx, by, bz, bs);     // the normal of S/RT:101-103 at the winning leaf: p = o + d * tHit, tHit = max(0, tNear) of ITS box
@@ -2215,7 +2219,7 @@ struct TriHit { bool hit; int steps; int tri; float t; float nx, ny, nz; };
 
 __device__ __forceinline__ TriHit trace_triangles(const RenderParams& P, const TriScene& S, const Ray& r) {
     TriHit h; h.hit = false; h.steps = 0; h.tri = -1; h.t = 1e30f; h.nx = h.ny = h.nz = 0.f;
-    int stack[128];
+    int stack[kStackCap];
     int sp = 0;
     stack[sp++] = 0;
     const float closestT = 1e30f;

@@ -1,4 +1,5 @@
-"""Float64 reference of config 5's leaf-triangle renderer (test code only).
+"""Float64 references of the box renderer (Octree64.trace_boxes: first hit, closest hit, stack depth) and of config 5's
+leaf-triangle renderer (TriScene64; test code only).
 
 Written from the rules of the path, not from the oracle's source:
   * primary ray: the float32 ray of generate_rays (pinned elsewhere); the octree is walked depth-first with a LIFO
@@ -36,12 +37,15 @@ def _norm(a):
     return np.sqrt((a * a).sum(-1))
 
 
-class TriScene64:
-    def __init__(self, nodes, tris, tri_offset, grid_min, voxel_size):
+class Octree64:
+    """The node boxes in float64 and the walk order; shared by the box and the triangle renderers."""
+
+    def __init__(self, nodes, grid_min, voxel_size):
         n = len(nodes)
         self.n = n
         self.child = np.asarray(nodes["child"], np.int64).reshape(n, 8)
         self.leafy = (nodes["isLeaf"] == 1) | (nodes["isUniform"] == 1)
+        self.solid = self.leafy & (nodes["isSolid"] == 1)
         vs = float(np.float32(voxel_size))
         gmin = np.asarray(grid_min, np.float64).reshape(3)
         xyz = np.stack([nodes["x"], nodes["y"], nodes["z"]], 1).astype(np.float64)
@@ -49,12 +53,8 @@ class TriScene64:
         self.bmax = self.bmin + nodes["size"].astype(np.float64)[:, None] * vs
         self.bmag = np.maximum(np.abs(self.bmin), np.abs(self.bmax)).max(1)
         self.bias = vs * 1e-3
-        t = np.asarray(tris, np.float64).reshape(-1, 12)
-        self.v0, self.v1, self.v2, self.nrm = t[:, 0:3], t[:, 3:6], t[:, 6:9], t[:, 9:12]
-        self.e1, self.e2 = self.v1 - self.v0, self.v2 - self.v0
-        self.vmag = np.abs(t[:, 0:9]).max(1)
-        self.off = np.asarray(tri_offset, np.int64)
         self.rank = self._preorder_rank()
+        self.below, self.pushes = self._stack_depths()
 
     def _preorder_rank(self):
         """Pop position of every node in a walk that enters everything (LIFO, child 7 first)."""
@@ -88,7 +88,10 @@ class TriScene64:
         return rank
 
     # ---------------------------------------------------------------- slab test over (ray, node) pairs
-    def _slab(self, o, d, nodes):
+    def _slab_terms(self, o, d, nodes):
+        """tNear, tFar of (ray, box) pairs and first-order bounds of the float32 slab test's errors in them.  Each axis
+        has its own bound; tNear = max over the axes can only move by as much as an axis whose interval comes within
+        its own bound of it (likewise tFar)."""
         bmin, bmax = self.bmin[nodes], self.bmax[nodes]
         zero = d == 0.0
         with np.errstate(all="ignore"):
@@ -97,25 +100,34 @@ class TriScene64:
             t2 = (bmax - o) * inv
             tmin, tmax = np.minimum(t1, t2), np.maximum(t1, t2)
             tn, tf = tmin.max(1), tmax.min(1)
-            err = np.where(zero, 0.0, K * EPS * ((self.bmag[nodes][:, None] + np.abs(o)) * np.abs(inv) + np.abs(tmax))).max(1)
+            ea = np.where(zero, 0.0, K * EPS * ((self.bmag[nodes][:, None] + np.abs(o)) * np.abs(inv) + np.maximum(np.abs(t1), np.abs(t2))))
+            en = np.where(np.isfinite(tn), (tmin + ea).max(1) - tn, 0.0)
+            ef = np.where(np.isfinite(tf), tf - (tmax - ea).min(1), 0.0)
+        return tn, tf, en, ef
+
+    def _slab(self, o, d, nodes):
+        tn, tf, en, ef = self._slab_terms(o, d, nodes)
+        zero = d == 0.0
+        with np.errstate(all="ignore"):
             passes = (tn <= tf) & (tf > 0) & (tn < 1e30)
-            amb = np.isnan(tn) | np.isnan(tf) | (np.abs(tn - tf) <= 2 * err) | (np.abs(tf) <= err)
-            amb |= zero.any(1) & ((o == bmin) | (o == bmax)).any(1)
+            amb = np.isnan(tn) | np.isnan(tf) | (np.abs(tn - tf) <= en + ef) | (np.abs(tf) <= ef)
+            amb |= zero.any(1) & ((o == self.bmin[nodes]) | (o == self.bmax[nodes])).any(1)
         return passes & ~np.isnan(tn), amb
 
     def _walk(self, o, d, R):
         """All (ray, leaf) pairs a walk can reach when every nominal or borderline slab decision is taken as a pass.
         Per pair: nominal (every box on the way, the leaf's included, passes in float64), path_amb (one of them is
-        borderline), and the reached nodes (ray, rank, borderline) for the pop count."""
+        borderline), and the nodes the nominal walk pops (ray, rank, borderline, passes) for the pop count."""
         rays = np.arange(R)
         nds = np.zeros(R, np.int64)
         nom_reach = np.ones(R, bool)           # every ancestor passed nominally: the node is popped in the nominal walk
         amb_path = np.zeros(R, bool)
         leaf_r, leaf_n, leaf_nom, leaf_amb = [], [], [], []
-        pop_r, pop_rank, pop_amb = [], [], []
+        pop_r, pop_rank, pop_amb, pop_ok = [], [], [], []
         while len(rays):
             ok, amb = self._slab(o[rays], d[rays], nds)
             pop_r.append(rays[nom_reach]); pop_rank.append(self.rank[nds[nom_reach]]); pop_amb.append(amb[nom_reach])
+            pop_ok.append(ok[nom_reach])
             go = ok | amb
             nom = nom_reach & ok
             pa = amb_path | amb
@@ -129,7 +141,116 @@ class TriScene64:
             rays = np.repeat(rays[sel], cnt); nds = c[has]
             nom_reach = np.repeat(nom[sel], cnt); amb_path = np.repeat(pa[sel], cnt)
         cat = np.concatenate
-        return (cat(leaf_r), cat(leaf_n), cat(leaf_nom), cat(leaf_amb)), (cat(pop_r), cat(pop_rank), cat(pop_amb))
+        return (cat(leaf_r), cat(leaf_n), cat(leaf_nom), cat(leaf_amb)), (cat(pop_r), cat(pop_rank), cat(pop_amb), cat(pop_ok))
+
+    def _stack_depths(self):
+        """below[v]: entries under v on the stack when v is popped (the siblings pushed before each node on its path);
+        pushes[v]: children v pushes.  An internal node that passes leaves below + pushes entries on the stack."""
+        ch = np.where(self.leafy[:, None], -1, self.child)
+        has = ch >= 0
+        pos = np.cumsum(has, 1) - has
+        below = np.zeros(self.n, np.int64)
+        level = np.array([0])
+        while len(level):
+            c, p = ch[level], pos[level]
+            ok = c >= 0
+            below[c[ok]] = np.repeat(below[level], ok.sum(1)) + p[ok]
+            level = c[ok]
+        return below, has.sum(1)
+
+
+    def _entry(self, o, d, nodes):
+        """Float64 tNear of (ray, box) pairs and a first-order bound of the float32 slab test's error in it."""
+        tn, _, en, _ = self._slab_terms(o, d, nodes)
+        return tn, en
+
+    def _shade(self, o, d, leaf, tn, terr):
+        """n . l of the hit on a leaf box (n = normalize(p - centre), p = o + d max(0, tNear)) and a bound of its float32 error."""
+        t = np.maximum(0.0, tn)
+        p = o + d * t[:, None]
+        v = p - 0.5 * (self.bmin[leaf] + self.bmax[leaf])
+        nv = _norm(v)
+        n = v / nv[:, None]
+        perr = terr * _norm(d) + 2 * EPS * (np.abs(p).max(1) + self.bmag[leaf])
+        return np.maximum(0.0, _dot(n, LIGHT)), 2.0 * perr / nv + 16 * EPS
+
+    def trace_boxes(self, o, d):
+        """The box renderer's two rules over rays (o, d), float64.
+        first: the first solid leaf in pop order whose box passes (tHit = max(0, tNear) <= tFar), under the 512-pop cap.
+        closest: the solid leaf with the smallest tHit among all whose box the ray meets (brute force over the leaves the
+        walk reaches when nothing is pruned: boxes nest, so a leaf's box passes only when its ancestors' do); ties go to
+        the leaf popped first.
+        Per rule a dict: hit, leaf, shade (n . l), tol (float32 error bound of the shade), robust; first also `need`, the
+        stack entries the nominal walk holds at most (a passed internal node leaves below + pushes entries)."""
+        R = len(o)
+        NONE = np.iinfo(np.int64).max
+        (lr, ln, lnom, _), (pr, prank, pamb, pok) = self._walk(o, d, R)
+        node_of = np.zeros(self.n, np.int64)
+        node_of[self.rank[::-1]] = np.arange(self.n)[::-1]          # rank 0: the root (unreachable nodes share it)
+        pnode = node_of[prank]
+        live = ~self.leafy[pnode] | self.solid[pnode]                     # a borderline empty leaf changes nothing
+        # ---- first hit
+        sol = self.solid[ln]
+        first = np.full(R, NONE)
+        np.minimum.at(first, lr[sol & lnom], self.rank[ln[sol & lnom]])
+        order = np.lexsort((prank, pr))
+        pr_s, prank_s = pr[order], prank[order]
+        start = np.searchsorted(pr_s, np.arange(R))
+        cnt = np.bincount(pr_s, minlength=R)
+        cap_rank = np.where(cnt >= MAX_POPS, prank_s[np.minimum(start + MAX_POPS - 1, len(pr_s) - 1)], NONE)
+        stop = np.minimum(first, cap_rank)                                # the last node the walk pops
+        upto = prank <= stop[pr]
+        capped = (first != NONE) & (first > cap_rank)
+        amb_before = np.zeros(R, bool)
+        amb_before[pr[upto & pamb & live]] = True
+        pushes = upto & pok & ~self.leafy[pnode]
+        need = np.ones(R, np.int64)
+        np.maximum.at(need, pr[pushes], self.below[pnode[pushes]] + self.pushes[pnode[pushes]])
+        hit = (first != NONE) & ~capped
+        leaf = np.where(hit, node_of[np.where(hit, first, 0)], -1)
+        out_first = dict(hit=hit, leaf=leaf, need=need, robust=~amb_before, shade=np.zeros(R), tol=np.zeros(R))
+        # ---- closest hit
+        cand = sol
+        cr, cl = lr[cand], ln[cand]
+        tn, terr = self._entry(o[cr], d[cr], cl)
+        th = np.maximum(0.0, tn)
+        ok, amb = self._slab(o[cr], d[cr], cl)
+        best = np.full(R, np.inf)
+        np.minimum.at(best, cr[ok], th[ok])
+        win = ok & (th == best[cr])
+        wrank = np.full(R, NONE)
+        np.minimum.at(wrank, cr[win], self.rank[cl[win]])
+        chit = wrank != NONE
+        cleaf = np.where(chit, node_of[np.where(chit, wrank, 0)], -1)
+        is_w = win & (self.rank[cl] == wrank[cr])
+        werr = np.zeros(R)
+        werr[cr[is_w]] = terr[is_w]
+        rival = ~is_w & (ok | amb) & ((th <= best[cr] + werr[cr] + terr) | np.isnan(th))
+        crob = np.ones(R, bool)
+        crob[cr[rival | (is_w & amb)]] = False
+        out_close = dict(hit=chit, leaf=cleaf, robust=crob, shade=np.zeros(R), tol=np.zeros(R))
+        for rule in (out_first, out_close):
+            h = np.nonzero(rule["hit"])[0]
+            t_, e_ = self._entry(o[h], d[h], rule["leaf"][h])
+            rule["shade"][h], rule["tol"][h] = self._shade(o[h], d[h], rule["leaf"][h], t_, e_)
+        return out_first, out_close
+
+
+def render_boxes64(S: Octree64, ro, rd):
+    """ro (3,) float32 eye, rd (N, 3) float32 directions: trace_boxes on the float64 rays."""
+    d = np.asarray(rd, np.float64).reshape(-1, 3)
+    o = np.broadcast_to(np.asarray(ro, np.float64).reshape(1, 3), d.shape).copy()
+    return S.trace_boxes(o, d)
+
+
+class TriScene64(Octree64):
+    def __init__(self, nodes, tris, tri_offset, grid_min, voxel_size):
+        super().__init__(nodes, grid_min, voxel_size)
+        t = np.asarray(tris, np.float64).reshape(-1, 12)
+        self.v0, self.v1, self.v2, self.nrm = t[:, 0:3], t[:, 3:6], t[:, 6:9], t[:, 9:12]
+        self.e1, self.e2 = self.v1 - self.v0, self.v2 - self.v0
+        self.vmag = np.abs(t[:, 0:9]).max(1)
+        self.off = np.asarray(tri_offset, np.int64)
 
     # ---------------------------------------------------------------- Moeller-Trumbore over (ray, triangle) pairs
     def _mt(self, o, d, k):
@@ -188,7 +309,7 @@ class TriScene64:
         out = dict(hit=hit, tri=tri, t=tt, dt=dtt, robust=robust, hit_robust=robust.copy())
         if self.n == 0 or R == 0:
             return out
-        (lr, ln, lnom, _), (pr, prank, pamb) = self._walk(o, d, R)
+        (lr, ln, lnom, _), (pr, prank, pamb, _) = self._walk(o, d, R)
         pi, k = self._pairs(lr, ln)
         ray = lr[pi]
         h, a, t, dt = self._mt(o[ray], d[ray], k)
