@@ -404,6 +404,49 @@ int  rto_probe_skip_device(rto_context* ctx, const float view[16], const float c
 int  rto_probe_skip_host(rto_context* ctx, const float view[16], const float cam_pos[3], float aspect, int use_visibility,
                          float* io_skip, float* probe_t /* 49 floats or NULL */);
 
+/* ---- ray queries ----------------------------------------------------------
+ * No reference counterpart as an API: RayTracerBVH.h:14-18 declares struct Ray { origin; direction; } and nothing consumes it;
+ * the click handler (main.cpp:646-700) finds the voxel under the cursor by a CPU march over the dense grid
+ * (intersectBuildingVoxel, main.cpp:209-).  These trace caller-supplied rays -- or the renders' own pixel rays -- through the
+ * whole resident octree and return one record per ray.
+ *
+ * Acceptance rule.  t_lo = max(t_min, 0).  A solid leaf is accepted when its box and every ancestor's
+ * pass the reference's float32 slab test (tNear <= tFar && tFar > 0, S/RT:226-236, glm min/max) with tNear < 1e30 (the
+ * renders' closestT, S/RT:242), and tHit = max(t_lo, tNear) satisfies tHit <= tFar and tHit <= t_max; hits at or beyond 1e30
+ * (the miss value) are misses.  With (t_min, t_max) = (0, 1e30) this is the renders' rule: FIRST on a frame's pixel rays gives
+ * rto_render_device's hits, CLOSEST rto_render_closest_device's, bit for bit.
+ * A ray with a NaN in its origin, direction, t_min or t_max, or with t_min > t_max, is a miss; directions with zero components
+ * follow the slab formula with its infinite reciprocals.  The whole uploaded octree is seen whatever rto_update_frustum did.
+ * Face: the lowest axis whose entry parameter equals tNear, signed by d[axis]; -1 when tHit > tNear (origin inside the box,
+ * or t_min clipped the entry). */
+typedef struct rto_ray {            /* 32 bytes */
+    float ox, oy, oz, t_min;
+    float dx, dy, dz, t_max;        /* d need not be normalised; t is in units of d */
+} rto_ray;
+
+typedef struct rto_hit {            /* 32 bytes */
+    float   t;                      /* tHit of the accepted leaf; 1e30f for a miss */
+    int32_t node;                   /* index in the resident array (what rto_download_nodes returns); -1 = miss */
+    int32_t face;                   /* entry face 0..5 = 2*axis + (d[axis] < 0); -1 = none (tHit > tNear) or miss */
+    int32_t size;                   /* leaf box, voxel units (the node's x, y, z, size); 0 for a miss */
+    int32_t x, y, z;
+    int32_t reserved;               /* 0 */
+} rto_hit;
+
+#define RTO_QUERY_FIRST   0   /* the default render's rule: LIFO pop order, first accepted solid leaf, 512-pop cap */
+#define RTO_QUERY_CLOSEST 1   /* rto_render_closest's rule: least tHit, ties to the leaf popped first */
+#define RTO_QUERY_ANY     2   /* occlusion: some accepted leaf, or a miss; which leaf is unspecified */
+
+/* Asynchronous on hip_stream; d_rays and d_hits are device pointers, 16-byte aligned.  n == 0: no-op.  RTO_E_INVALID: NULL
+ * buffer, unknown mode, n < 0, misaligned buffer; RTO_E_NO_OCTREE: nothing uploaded.  _host: synchronous, host buffers. */
+int  rto_query_rays_device(rto_context* ctx, int mode, const rto_ray* d_rays, int64_t n, rto_hit* d_hits, void* hip_stream);
+int  rto_query_rays_host(rto_context* ctx, int mode, const rto_ray* rays, int64_t n, rto_hit* hits);
+/* rays = the renders' own generateRay for pixel (x, y) of `frame` (row 0 = top), bit-identical to the rays they trace, with
+ * (t_min, t_max) = (0, 1e30); d_xy holds n (x, y) int32 pairs.  A pixel outside the frame gets a miss record. */
+int  rto_query_pixels_device(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* d_xy, int64_t n,
+                             rto_hit* d_hits, void* hip_stream);
+int  rto_query_pixels_host(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_hit* hits);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

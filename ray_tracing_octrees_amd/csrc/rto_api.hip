@@ -2656,3 +2656,4 @@ int rto_synchronize(rto_context* c) {
 
 #include "rto_split.inc"
 #include "rto_comm.inc"
+#include "rto_query.inc"

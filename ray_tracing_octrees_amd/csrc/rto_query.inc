@@ -1,0 +1,364 @@
+// rto_query.inc -- ray queries (include/rto_hip.h, rto_query_*): caller-supplied rays, or the renders' own pixel rays, traced
+// through the whole resident octree; one rto_hit record per ray.  Included at the end of rto_api.hip.
+//
+// Acceptance rule (DESIGN.md section 10).  t_lo = max(t_min, 0), t_hi = min(t_max, largest float below 1e30).  A solid leaf is
+// accepted when its own box and every ancestor's pass the reference's slab test (S/RT:226-236: tNear <= tFar && tFar > 0, glm
+// min / max, the renders' operation order) with tNear < 1e30 (the renders' `tNear >= closestT` prune at its start value,
+// S/RT:242), and tHit = max(t_lo, tNear) satisfies tHit <= tFar and tHit <= t_hi.  With (0, 1e30) this is the renders' rule.
+//   FIRST   the first accepted leaf in the reference's LIFO pop order (children 7 .. 0), under its 512-pop cap (rto_render_device);
+//   CLOSEST the accepted leaf of least tHit, ties to the leaf popped first (rto_render_closest_device);
+//   ANY     some accepted leaf (occlusion): a hit exactly when CLOSEST has one.
+// The walks ignore the frustum state: the descriptors' visibility bits are masked off and d_compact is never read.
+
+namespace rto {
+
+constexpr int kQueryFirst = RTO_QUERY_FIRST, kQueryClosest = RTO_QUERY_CLOSEST, kQueryAny = RTO_QUERY_ANY;
+
+// Where the rays come from: rays[base + i] (PIXELS = false: 32-byte rto_ray records, 16-byte aligned) or the pixel
+// (xy[2 (base + i)], xy[2 (base + i) + 1]) of the frame in RenderParams (PIXELS = true, generate_ray_tab).
+struct QuerySrc {
+    const rto_ray* rays;
+    const int32_t* xy;
+    rto_hit* hits;           // 16-byte aligned
+    int64_t n;               // rays of the whole call
+    int64_t base;            // first ray of this launch
+};
+
+// The ray of query i and its window; false: the ray is a miss whatever the tree (NaN input, t_min > t_max, pixel outside the frame).
+template <bool PIXELS>
+__device__ __forceinline__ bool query_ray(const RenderParams& P, const QuerySrc& Q, int64_t i, Ray& r, float& tlo, float& thi) {
+    const float kBelow1e30 = __uint_as_float(0x7149f2c9u);
+    if (PIXELS) {
+        const int px = Q.xy[2 * i], py = Q.xy[2 * i + 1];
+        if (px < 0 || px >= P.W || py < 0 || py >= P.H) return false;
+        r = generate_ray_tab(P, px, py);
+        tlo = 0.0f; thi = kBelow1e30;
+        return true;
+    }
+    const float4* src = reinterpret_cast<const float4*>(Q.rays) + 2 * i;
+    const float4 a = src[0], b = src[1];
+    r.ox = a.x; r.oy = a.y; r.oz = a.z; r.dx = b.x; r.dy = b.y; r.dz = b.z;
+    if (__builtin_isnan(a.x) || __builtin_isnan(a.y) || __builtin_isnan(a.z) || __builtin_isnan(b.x) || __builtin_isnan(b.y) ||
+        __builtin_isnan(b.z) || !(a.w <= b.w))                      // NaN t_min / t_max or t_min > t_max
+        return false;
+    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
+    tlo = a.w > 0.0f ? a.w : 0.0f;
+    thi = gmin(b.w, kBelow1e30);
+    return true;
+}
+
+// Entry face of an accepted leaf: the lowest axis whose entry parameter min(t1, t2) is tNear, signed by the direction; -1 when
+// tHit > tNear (the window or the origin clipped the entry).  The slab arithmetic of slab_exact.
+__device__ __forceinline__ int query_face(const Geo& G, const Ray& r, int x, int y, int z, int size, float tHit) {
+    const float ext = (float)size * G.vs;
+    const float mnx = G.gx + (float)x * G.vs, mny = G.gy + (float)y * G.vs, mnz = G.gz + (float)z * G.vs;
+    const float ex = gmin((mnx - r.ox) * r.ix, ((mnx + ext) - r.ox) * r.ix);
+    const float ey = gmin((mny - r.oy) * r.iy, ((mny + ext) - r.oy) * r.iy);
+    const float ez = gmin((mnz - r.oz) * r.iz, ((mnz + ext) - r.oz) * r.iz);
+    const float tNear = gmax(gmax(ex, ey), ez);
+    if (tHit > tNear) return -1;
+    if (ex == tNear) return r.dx < 0.0f ? 1 : 0;
+    if (ey == tNear) return r.dy < 0.0f ? 3 : 2;
+    return r.dz < 0.0f ? 5 : 4;
+}
+
+__device__ __forceinline__ void store_hit(const QuerySrc& Q, int64_t i, bool hit, float t, int node, int face, int size, int x, int y, int z) {
+    int4* dst = reinterpret_cast<int4*>(Q.hits) + 2 * i;
+    if (hit) {
+        dst[0] = make_int4(__float_as_int(t), node, face, size);
+        dst[1] = make_int4(x, y, z, 0);
+    } else {
+        dst[0] = make_int4(__float_as_int(1e30f), -1, -1, 0);
+        dst[1] = make_int4(0, 0, 0, 0);
+    }
+}
+
+// ================================================================ canonical trees: the descriptor walk
+// One ray per lane.  Per tree level and lane two LDS words: the entry the lean kernels keep (children still to pop | internal
+// mask << 8, first internal child's descriptor) and the descriptor index of the node itself (a leaf's array index is
+// descFirstChild[that] + child).  The 8 child verdicts of an entered node come at once from child_fail_mask_fast (waves holding a
+// non-finite origin, direction or reciprocal: child_fail_mask_exact); the visibility byte of the descriptor is never looked at.
+//   FIRST   children pop 7 .. 0 as in the reference.  Every entered internal node pushes its 8 children and everything pushed is
+//           popped except, at a leaf, the children below the path on each level: pops = 1 + 8 entered - sum of the path's child
+//           indices, and that sum is popcount(x) + 2 popcount(y) + 4 popcount(z) of the leaf's position (the path's bits).  A hit
+//           past 512 pops is a miss (the render's loop ended first); past 8 entered > 511 + 7 depth no later hit can be in reach.
+//   CLOSEST the ray's own octant first (k_closest_near_first's order), a node cut when tNear > min(best, t_hi) -- a child's tNear is
+//           never below its parent's --, equal tHit resolved by the LIFO pop order (pops_before).
+//   ANY     the same order, ends at the first accepted leaf.
+template <int QMODE, bool PIXELS>
+__global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc Q, const uint2* __restrict__ desc,
+                                                       const int* __restrict__ descFirstChild) {
+    extern __shared__ uint2 lds_stack[];   // [wave][level][lane] entries, then [wave][level][lane] descriptor indices
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
+    const int levels = P.depth;
+    uint2* stk = lds_stack + (size_t)wave * levels * kWave + lane;
+    unsigned* stkNode = reinterpret_cast<unsigned*>(lds_stack + (size_t)waves * levels * kWave) + (size_t)wave * levels * kWave + lane;
+    const int64_t i = Q.base + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const Geo G = geo_of(P);
+    const float kEps = __uint_as_float(1u), kBelow1e30 = __uint_as_float(0x7149f2c9u);
+
+    Ray r;
+    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
+    float tlo = 0.0f, thi = 0.0f;
+    bool active = false;
+    if (i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi)) {
+        float tNear, tFar, a0, a1, a2, a3, a4, a5;
+        active = slab_exact(G, r, 0, 0, 0, P.rootSize, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
+        if (QMODE != kQueryFirst) active = active && !(tNear > thi);
+    }
+    const bool risky = active && !(__builtin_isfinite(r.ix) && __builtin_isfinite(r.iy) && __builtin_isfinite(r.iz) &&
+                                   __builtin_isfinite(r.ox) && __builtin_isfinite(r.oy) && __builtin_isfinite(r.oz) &&
+                                   __builtin_isfinite(r.dx) && __builtin_isfinite(r.dy) && __builtin_isfinite(r.dz));
+    const bool anyRisky = __builtin_amdgcn_ballot_w64(risky) != 0ull;
+    const unsigned sgnX = (unsigned)((int)__float_as_uint(r.ix) >> 31), sgnY = (unsigned)((int)__float_as_uint(r.iy) >> 31),
+                   sgnZ = (unsigned)((int)__float_as_uint(r.iz) >> 31);
+    const unsigned flip = QMODE == kQueryFirst ? 0u : ((r.dx < 0.0f ? 1u : 0u) | (r.dy < 0.0f ? 2u : 0u) | (r.dz < 0.0f ? 4u : 0u));
+
+    bool hit = false, enter = active;
+    float best = 1e30f;
+    int bx = 0, by = 0, bz = 0, bs = 0, bj = 0;
+    unsigned bnode = 0;
+    unsigned cur = 0, lvlPending = 0;
+    int cx = 0, cy = 0, cz = 0, bpos = P.depth - 1;
+    int entered = 0;
+    const int capEntered = kMaxTraversalSteps - 1 + 7 * P.depth;      // FIRST: 8 entered above this puts every later hit past the cap
+    while (active) {
+        if (enter) {
+            entered++;
+            if (QMODE == kQueryFirst && 8 * entered > capEntered) break;
+            const uint2 d = desc[cur];
+            unsigned fail8;
+            if (anyRisky) fail8 = child_fail_mask_exact(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, cx, cy, cz, 1 << bpos);
+            else fail8 = child_fail_mask_fast<true, false>(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, sgnX, sgnY, sgnZ,
+                                                           cx, cy, cz, (float)(1 << bpos), kEps,
+                                                           QMODE == kQueryFirst ? kBelow1e30 : gmax(kEps, gmin(best, thi)));   // the pop re-tests exactly
+            const unsigned im = (d.x >> 8) & 0xffu;
+            unsigned cand = ((d.x | im) & 0xffu) & ~fail8;       // solid leaves and internal children whose box the ray meets
+            if (QMODE != kQueryFirst) cand = flip_children(cand, flip);
+            stk[bpos * kWave] = make_uint2(cand | (im << 8), d.y);
+            stkNode[bpos * kWave] = cur;
+            lvlPending = cand ? (lvlPending | (1u << bpos)) : (lvlPending & ~(1u << bpos));
+            enter = false;
+        }
+        if (lvlPending == 0) break;
+        const int Lb = __builtin_ctz(lvlPending);                  // the deepest node with children left: LIFO
+        const uint2 e = stk[Lb * kWave];
+        const int k = QMODE == kQueryFirst ? 31 - __builtin_clz(e.x & 0xffu) : __builtin_ctz(e.x & 0xffu);
+        const unsigned left = e.x ^ (1u << k);
+        stk[Lb * kWave].x = left;
+        if ((left & 0xffu) == 0) lvlPending &= ~(1u << Lb);
+        const int j = k ^ (int)flip;
+        const unsigned bit = 1u << j;
+        const int h = 1 << Lb, keep = ~(2 * h - 1);
+        const int chx = (cx & keep) + ((j & 1) ? h : 0), chy = (cy & keep) + ((j & 2) ? h : 0), chz = (cz & keep) + ((j & 4) ? h : 0);
+        const unsigned im = (e.x >> 8) & 0xffu;
+        const bool internal = (im & bit) != 0;
+        float tNear = 0.0f, tFar = 0.0f;
+        bool pass = true;
+        if (QMODE != kQueryFirst || !internal) {
+            float a0, a1, a2, a3, a4, a5;
+            pass = slab_exact(G, r, chx, chy, chz, h, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
+            if (QMODE != kQueryFirst) pass = pass && !(tNear > gmin(best, thi));
+        }
+        if (!pass) continue;
+        if (internal) {
+            cur = e.y + (unsigned)__builtin_popcount(im & (bit - 1u));
+            cx = chx; cy = chy; cz = chz; bpos = Lb - 1; enter = true;
+            continue;
+        }
+        const float tHit = gmax(tlo, tNear);
+        const bool ok = tHit <= tFar && tHit <= thi;
+        if (QMODE == kQueryClosest) {
+            // plain booleans, as in k_closest_near_first (a short-circuit form lost updates in this divergent loop there)
+            const bool nearer = tHit < best;
+            const bool tie = tHit == best;                         // only after a hit: best starts at 1e30 > t_hi
+            const bool first = pops_before(chx, chy, chz, bx, by, bz);
+            if (ok && (nearer || (tie && first))) {
+                best = tHit; hit = true; bx = chx; by = chy; bz = chz; bs = h; bj = j; bnode = stkNode[Lb * kWave];
+            }
+        } else if (ok) {
+            best = tHit; hit = true; bx = chx; by = chy; bz = chz; bs = h; bj = j; bnode = stkNode[Lb * kWave];
+            if (QMODE == kQueryFirst) {
+                const int pops = 1 + 8 * entered - (__builtin_popcount(chx) + 2 * __builtin_popcount(chy) + 4 * __builtin_popcount(chz));
+                if (pops > kMaxTraversalSteps) hit = false;        // S/RT:254: the loop ended before this pop
+            }
+            break;
+        }
+    }
+    if (i < Q.n) {
+        const int node = hit ? descFirstChild[bnode] + bj : -1;
+        const int face = hit ? query_face(G, r, bx, by, bz, bs, best) : -1;
+        store_hit(Q, i, hit, best, node, face, bs, bx, by, bz);
+    }
+}
+
+// ================================================================ any array, or RTO_KERNEL_GENERIC: node by node
+// The 60-byte array with explicit child indices and a stack of kStackCap entries (rto_upload_octree bounds every walk by it) in
+// the reference's LIFO order.  The stack lives in LDS, [entry][lane] (conflict free), one wave per workgroup (36 KB): a private
+// int[kStackCap] would be scratch memory.  FIRST is the loop of k_trace_generic, CLOSEST that of k_trace_closest (a leaf replaces the best only
+// when strictly nearer: ties to the leaf popped first), ANY ends at the first accepted leaf; CLOSEST and ANY also cut nodes with
+// tNear > t_hi.
+constexpr int kQueryNodesBlock = kWave;
+template <int QMODE, bool PIXELS>
+__global__ __launch_bounds__(kQueryNodesBlock) void k_query_nodes(RenderParams P, QuerySrc Q, const rto_node* __restrict__ nodes) {
+    extern __shared__ int lds_query_stack[];                     // [kStackCap][lane]
+    int* stack = lds_query_stack + threadIdx.x;
+    const int64_t i = Q.base + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const Geo G = geo_of(P);
+    Ray r;
+    float tlo = 0.0f, thi = 0.0f;
+    bool hit = false;
+    float closestT = 1e30f;                                        // S/RT:242
+    int bnode = -1, bx = 0, by = 0, bz = 0, bs = 0;
+    if (i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi)) {
+        int sp = 0, steps = 0;
+        stack[kWave * sp++] = 0;
+        while (sp > 0 && (QMODE != kQueryFirst || steps < kMaxTraversalSteps)) {
+            const int nodeIdx = stack[kWave * --sp];
+            steps++;
+            const rto_node nd = nodes[nodeIdx];
+            float tNear, tFar, a0, a1, a2, a3, a4, a5;
+            if (!slab_exact(G, r, nd.x, nd.y, nd.z, nd.size, tNear, tFar, a0, a1, a2, a3, a4, a5)) continue;
+            if (tNear >= closestT) continue;
+            if (QMODE != kQueryFirst && tNear > thi) continue;
+            if (nd.isUniform == 1 || nd.isLeaf == 1) {
+                if (nd.isSolid == 1) {
+                    const float tHit = gmax(tlo, tNear);
+                    if (tHit < closestT && tHit <= tFar && tHit <= thi) {
+                        hit = true; closestT = tHit; bnode = nodeIdx; bx = nd.x; by = nd.y; bz = nd.z; bs = nd.size;
+                        if (QMODE != kQueryClosest) break;
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int ch = nd.child[c];
+                if (ch >= 0) stack[kWave * sp++] = ch;
+            }
+        }
+    }
+    if (i < Q.n) store_hit(Q, i, hit, closestT, bnode, hit ? query_face(G, r, bx, by, bz, bs, closestT) : -1, bs, bx, by, bz);
+}
+
+}  // namespace rto
+
+// ---------------------------------------------------------------- host side
+constexpr int64_t kQueryChunk = (int64_t)1 << 28;       // rays per launch: 2^20 workgroups of 256 (2^22 of 64)
+
+// Geometry of the resident octree for a launch of rays from memory (the pixel form fills the frame part with fill_params).
+static void query_geometry(const rto_context* c, RenderParams& P) {
+    std::memcpy(P.gridMin, c->gridMin, sizeof P.gridMin);
+    P.voxelSize = c->voxelSize;
+    P.rootSize = c->rootSize;
+    P.depth = c->depth > 0 ? c->depth : 1;
+}
+
+static int query_check(rto_context* c, const char* fn, int mode, int64_t n, const void* in, const void* out) {
+    if (mode != RTO_QUERY_FIRST && mode != RTO_QUERY_CLOSEST && mode != RTO_QUERY_ANY)
+        return fail(c, RTO_E_INVALID, std::string(fn) + ": unknown mode " + std::to_string(mode));
+    if (n < 0) return fail(c, RTO_E_INVALID, std::string(fn) + ": n < 0");
+    if (n > 0 && (!in || !out)) return fail(c, RTO_E_INVALID, std::string(fn) + ": NULL buffer");
+    return RTO_OK;
+}
+
+template <bool PIXELS>
+static int launch_query(rto_context* c, int mode, const RenderParams& P, QuerySrc Q, hipStream_t s) {
+    const bool desc = c->canonical && c->numInternal > 0 && c->kernelMode != RTO_KERNEL_GENERIC;
+    const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * (sizeof(uint2) + sizeof(unsigned));   // <= 64,512 B (depth 20)
+    for (int64_t off = 0; off < Q.n; off += kQueryChunk) {
+        Q.base = off;
+        const int64_t rays = std::min(Q.n - off, kQueryChunk);
+        const dim3 grid((unsigned)((rays + kBlock - 1) / kBlock)), block(kBlock);
+        const dim3 gridN((unsigned)((rays + kQueryNodesBlock - 1) / kQueryNodesBlock)), blockN(kQueryNodesBlock);
+        const size_t ldsN = (size_t)kStackCap * kQueryNodesBlock * sizeof(int);
+        if (desc) {
+            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_query_desc<kQueryFirst, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
+            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_query_desc<kQueryClosest, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
+            else hipLaunchKernelGGL((k_query_desc<kQueryAny, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
+        } else {
+            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_query_nodes<kQueryFirst, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
+            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_query_nodes<kQueryClosest, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
+            else hipLaunchKernelGGL((k_query_nodes<kQueryAny, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
+        }
+        RTO_HIP(c, hipGetLastError());
+    }
+    return RTO_OK;
+}
+
+static int query_rays(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_hit* d_hits, hipStream_t s) {
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_hits) & 15))
+        return fail(c, RTO_E_INVALID, "rto_query_rays: the ray and hit buffers must be 16-byte aligned");
+    RenderParams P;
+    std::memset(&P, 0, sizeof P);
+    query_geometry(c, P);
+    return launch_query<false>(c, mode, P, QuerySrc{ d_rays, nullptr, d_hits, n, 0 }, s);
+}
+
+static int query_pixels(rto_context* c, int mode, const rto_frame* f, const int32_t* d_xy, int64_t n, rto_hit* d_hits, hipStream_t s) {
+    if (reinterpret_cast<uintptr_t>(d_hits) & 15) return fail(c, RTO_E_INVALID, "rto_query_pixels: the hit buffer must be 16-byte aligned");
+    RenderParams P;
+    const int rc = fill_params(c, f, nullptr, P, s);             // the renders' ray tables and inverse view: bit-identical rays
+    if (rc != RTO_OK) return rc;
+    return launch_query<true>(c, mode, P, QuerySrc{ nullptr, d_xy, d_hits, n, 0 }, s);
+}
+
+extern "C" {
+
+int rto_query_rays_device(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_hit* d_hits, void* hip_stream) {
+    if (!c) return RTO_E_INVALID;
+    int rc = query_check(c, "rto_query_rays_device", mode, n, d_rays, d_hits);
+    if (rc != RTO_OK || n == 0) return rc;
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_rays_device: no octree uploaded");
+    RTO_HIP(c, hipSetDevice(c->device));
+    return query_rays(c, mode, d_rays, n, d_hits, (hipStream_t)hip_stream);
+}
+
+int rto_query_rays_host(rto_context* c, int mode, const rto_ray* rays, int64_t n, rto_hit* hits) {
+    if (!c) return RTO_E_INVALID;
+    int rc = query_check(c, "rto_query_rays_host", mode, n, rays, hits);
+    if (rc != RTO_OK || n == 0) return rc;
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_rays_host: no octree uploaded");
+    RTO_HIP(c, hipSetDevice(c->device));
+    BuildScratch scratch(c->stream);
+    rto_ray* d_rays = nullptr;
+    rto_hit* d_hits = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_rays, (size_t)n));
+    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
+    RTO_HIP(c, hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rto_ray), hipMemcpyHostToDevice, c->stream));
+    if ((rc = query_rays(c, mode, d_rays, n, d_hits, c->stream)) != RTO_OK) return rc;
+    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_hit), hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
+    return RTO_OK;
+}
+
+int rto_query_pixels_device(rto_context* c, int mode, const rto_frame* frame, const int32_t* d_xy, int64_t n, rto_hit* d_hits, void* hip_stream) {
+    if (!c) return RTO_E_INVALID;
+    int rc = query_check(c, "rto_query_pixels_device", mode, n, d_xy, d_hits);
+    if (rc != RTO_OK || n == 0) return rc;
+    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_pixels_device: frame is NULL");
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_pixels_device: no octree uploaded");
+    RTO_HIP(c, hipSetDevice(c->device));
+    return query_pixels(c, mode, frame, d_xy, n, d_hits, (hipStream_t)hip_stream);
+}
+
+int rto_query_pixels_host(rto_context* c, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_hit* hits) {
+    if (!c) return RTO_E_INVALID;
+    int rc = query_check(c, "rto_query_pixels_host", mode, n, xy, hits);
+    if (rc != RTO_OK || n == 0) return rc;
+    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_pixels_host: frame is NULL");
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_pixels_host: no octree uploaded");
+    RTO_HIP(c, hipSetDevice(c->device));
+    BuildScratch scratch(c->stream);
+    int32_t* d_xy = nullptr;
+    rto_hit* d_hits = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_xy, (size_t)n * 2));
+    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
+    RTO_HIP(c, hipMemcpyAsync(d_xy, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if ((rc = query_pixels(c, mode, frame, d_xy, n, d_hits, c->stream)) != RTO_OK) return rc;
+    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_hit), hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
+    return RTO_OK;
+}
+
+}  // extern "C"

@@ -35,8 +35,16 @@ SYMBOLS = (
     "rto_comm_submit_all", "rto_comm_render_resident_all", "rto_comm_flush", "rto_comm_flush_timeout", "rto_comm_is_dead", "rto_comm_ranks_seen", "rto_comm_debug_abort", "rto_comm_stream", "rto_comm_debug_rehearse", "rto_comm_debug_last_payload", "rto_comm_debug_set_timing", "rto_comm_debug_last_timing", "rto_comm_debug_set_rehearsal_clear", "rto_debug_fault_alloc", "rto_render_triangles_batch_device",
     "rto_debug_set_tile_mask", "rto_debug_tile_mask_info", "rto_render_closest_device", "rto_render_closest_host", "rto_render_skip_device", "rto_render_skip_host", "rto_probe_skip_device", "rto_probe_skip_host",
     "rto_scene_bounds_get", "rto_scene_bounds_of_nodes", "rto_split_plan_make", "rto_split_part_of_rank", "rto_split_rows_of_part", "rto_split_row_source",
+    "rto_query_rays_device", "rto_query_rays_host", "rto_query_pixels_device", "rto_query_pixels_host",
 )
 SPLIT_MAX_FRAMES = 32
+QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
+
+# struct rto_ray / rto_hit (include/rto_hip.h), 32 bytes each
+RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("t_min", "<f4"),
+                      ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("t_max", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("node", "<i4"), ("face", "<i4"), ("size", "<i4"),
+                      ("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("reserved", "<i4")])
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
 
@@ -54,6 +62,28 @@ class Frame(C.Structure):
 
 class Partition(C.Structure):
     _fields_ = [("num_parts", C.c_int32), ("part", C.c_int32), ("band_rows", C.c_int32)]
+
+
+class Ray(C.Structure):
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("t_min", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("t_max", C.c_float)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("node", C.c_int32), ("face", C.c_int32), ("size", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("reserved", C.c_int32)]
+
+
+def make_rays(origins, dirs, t_min=0.0, t_max=1e30) -> np.ndarray:
+    """A RAY_DTYPE array from (n, 3) origins (or one origin for all rays), (n, 3) directions and scalar or per-ray windows."""
+    d = np.asarray(dirs, np.float32).reshape(-1, 3)
+    o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
+    r = np.zeros(len(d), RAY_DTYPE)
+    r["ox"], r["oy"], r["oz"] = o[:, 0], o[:, 1], o[:, 2]
+    r["dx"], r["dy"], r["dz"] = d[:, 0], d[:, 1], d[:, 2]
+    r["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), len(d))
+    r["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), len(d))
+    return r
 
 
 class Stats(C.Structure):
@@ -194,6 +224,10 @@ def load():
     L.rto_split_part_of_rank.argtypes = [C.POINTER(SplitPlan), C.c_int]
     L.rto_split_rows_of_part.argtypes = [C.POINTER(SplitPlan), C.c_int]
     L.rto_split_row_source.argtypes = [C.POINTER(SplitPlan), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.rto_query_rays_device.argtypes = [vp, C.c_int, vp, C.c_int64, vp, vp]
+    L.rto_query_rays_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
+    L.rto_query_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
+    L.rto_query_pixels_host.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -464,6 +498,35 @@ class Context:
         self._check(self._L.rto_octree_ray_skip(self._h, o, rd.ctypes.data, len(rd), _f(t_min), _f(t_max),
                                                 1 if use_visibility else 0, out.ctypes.data))
         return out
+
+    # -- ray queries -------------------------------------------------------
+    def query_rays(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:
+        """Trace caller-supplied rays through the whole resident octree (rto_query_rays_host).  origins: (n, 3) or one origin,
+        dirs: (n, 3), t_min / t_max: scalars or per-ray arrays.  Returns a HIT_DTYPE array (node -1, t 1e30 for a miss)."""
+        return self.query_ray_records(make_rays(origins, dirs, t_min, t_max), mode)
+
+    def query_ray_records(self, rays: np.ndarray, mode: int = QUERY_CLOSEST) -> np.ndarray:
+        """The same for a RAY_DTYPE array."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        self._check(self._L.rto_query_rays_host(self._h, int(mode), rays.ctypes.data, len(rays), hits.ctypes.data))
+        return hits
+
+    def query_rays_device(self, mode: int, d_rays: int, n: int, d_hits: int, stream: int = 0):
+        """Asynchronous: n rto_ray records at d_rays -> n rto_hit records at d_hits (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_rays_device(self._h, int(mode), C.c_void_p(d_rays) if d_rays else None, int(n),
+                                                  C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    def query_pixels(self, frame: Frame, xy, mode: int = QUERY_FIRST) -> np.ndarray:
+        """The renders' own rays through pixels (x, y) of `frame` (row 0 = top): xy (n, 2) int; a HIT_DTYPE array."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.int32).reshape(-1, 2))
+        hits = np.zeros(len(xy), HIT_DTYPE)
+        self._check(self._L.rto_query_pixels_host(self._h, int(mode), C.byref(frame), xy.ctypes.data, len(xy), hits.ctypes.data))
+        return hits
+
+    def query_pixels_device(self, mode: int, frame: Frame, d_xy: int, n: int, d_hits: int, stream: int = 0):
+        self._check(self._L.rto_query_pixels_device(self._h, int(mode), C.byref(frame), C.c_void_p(d_xy) if d_xy else None, int(n),
+                                                    C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
 
     def render_closest_host(self, frame: Frame, stats: bool = False):
         """The reference's closest-hit traversal (its earlier, block-commented shader): RGBA frame [, {rays, pops, hits}]."""

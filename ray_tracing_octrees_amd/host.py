@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import NODE_DTYPE, RtoError, _f
+from .hip import HIT_DTYPE, NODE_DTYPE, RtoError, _f
 
 _lib = None
 _vp = C.c_void_p
@@ -116,6 +116,10 @@ def load():
     L.rtoh_rt_context.restype = _vp
     L.rtoh_rt_last_error.argtypes = [_vp]
     L.rtoh_rt_last_error.restype = C.c_char_p
+    L.rtoh_rt_intersect_rays.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp]
+    L.rtoh_rt_intersect_rays.restype = None
+    L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
+    L.rtoh_rt_pick.restype = C.c_int
     _lib = L
     return L
 
@@ -365,6 +369,22 @@ class RayTracerBVH:
         out = np.empty((h.value, w.value, 4), np.float32)
         load().rtoh_rt_framebuffer(self._h, out.ctypes.data, out.size, C.byref(w), C.byref(h))
         return out
+
+    def intersectRays(self, origins, dirs, mode: int = 1, tMin: float = 0.0, tMax: float = 1e30) -> np.ndarray:
+        """Addition: RayTracerBVH::intersectRays -- rays (origins (n, 3) or one origin, dirs (n, 3)) through the resident octree;
+        a structured array of rto_hit records (hip.HIT_DTYPE; node -1 = miss).  mode: 0 first, 1 closest (default), 2 any."""
+        d = np.asarray(dirs, np.float32).reshape(-1, 3)
+        o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
+        rays = np.ascontiguousarray(np.concatenate([o, d], 1), dtype=np.float32)
+        hits = np.zeros(len(d), HIT_DTYPE)
+        load().rtoh_rt_intersect_rays(self._h, rays.ctypes.data, len(d), int(mode), _f(tMin), _f(tMax), hits.ctypes.data)
+        return hits
+
+    def pick(self, camera: Camera, px: int, py: int, width: int, height: int, aspect: float, fovDeg: float):
+        """Addition: RayTracerBVH::pick -- the leaf renderSceneCompute shows at pixel (px, py): an rto_hit record, or None."""
+        out = np.zeros(1, HIT_DTYPE)
+        hit = load().rtoh_rt_pick(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg), out.ctypes.data)
+        return out[0] if hit else None
 
     def finish(self):
         """Wait for the GPU(s): the counterpart of glFinish for timing loops (renders are asynchronous)."""

@@ -34,6 +34,8 @@ struct HipApi {
     decltype(&rto_comm_destroy) comm_destroy = nullptr;
     decltype(&rto_comm_last_error) comm_last_error = nullptr;
     decltype(&rto_comm_render_resident_all) comm_render_resident_all = nullptr;
+    decltype(&rto_query_rays_host) query_rays_host = nullptr;
+    decltype(&rto_query_pixels_host) query_pixels_host = nullptr;
     std::string error;
 
     bool load() {
@@ -79,6 +81,8 @@ struct HipApi {
         comm_destroy = reinterpret_cast<decltype(comm_destroy)>(sym("rto_comm_destroy"));
         comm_last_error = reinterpret_cast<decltype(comm_last_error)>(sym("rto_comm_last_error"));
         comm_render_resident_all = reinterpret_cast<decltype(comm_render_resident_all)>(sym("rto_comm_render_resident_all"));
+        query_rays_host = reinterpret_cast<decltype(query_rays_host)>(sym("rto_query_rays_host"));
+        query_pixels_host = reinterpret_cast<decltype(query_pixels_host)>(sym("rto_query_pixels_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -294,6 +298,57 @@ void RayTracerBVH::renderSceneTriangles(const Camera& camera, int width, int hei
         return;
     }
     m_frameW = width; m_frameH = height; m_frameStale = true;
+}
+
+static RayHit to_ray_hit(const rto_hit& h) {
+    RayHit r;
+    r.t = h.t; r.node = h.node; r.face = h.face; r.size = h.size; r.x = h.x; r.y = h.y; r.z = h.z;
+    return r;
+}
+
+void RayTracerBVH::intersectRays(const std::vector<Ray>& rays, std::vector<RayHit>& hits, int mode, float tMin, float tMax) {
+    hits.assign(rays.size(), RayHit());
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return;
+    }
+    if (rays.empty() || m_numNodes <= 0) return;
+    std::vector<rto_ray> in(rays.size());
+    for (size_t i = 0; i < rays.size(); i++) {
+        const Ray& r = rays[i];
+        in[i] = rto_ray{ r.origin.x, r.origin.y, r.origin.z, tMin, r.direction.x, r.direction.y, r.direction.z, tMax };
+    }
+    std::vector<rto_hit> out(rays.size());
+    if (api().query_rays_host(m_ctx, mode, in.data(), (int64_t)in.size(), out.data()) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] ray query failed: " << m_lastError << std::endl;
+        return;
+    }
+    for (size_t i = 0; i < out.size(); i++) hits[i] = to_ray_hit(out[i]);
+}
+
+bool RayTracerBVH::pick(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RayHit& out) {
+    out = RayHit();
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return false;
+    }
+    if (m_numNodes <= 0 || width <= 0 || height <= 0) return false;
+    rto_frame f;
+    const auto view = camera.getView();
+    std::memcpy(f.view, &view[0][0], sizeof f.view);
+    const auto pos = camera.getPos();
+    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
+    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const int32_t xy[2] = { px, py };
+    rto_hit h;
+    if (api().query_pixels_host(m_ctx, RTO_QUERY_FIRST, &f, xy, 1, &h) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] pick failed: " << m_lastError << std::endl;
+        return false;
+    }
+    out = to_ray_hit(h);
+    return out.hit();
 }
 
 const std::vector<float>& RayTracerBVH::framebuffer() const {

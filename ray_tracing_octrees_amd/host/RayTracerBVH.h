@@ -45,8 +45,22 @@ struct Ray {
     rto_host::vec3 direction;
 };
 
+// What a ray query found (the fields of rto_hit, include/rto_hip.h): the accepted solid leaf's index in the resident array, its
+// box (voxel units), the ray parameter t of the hit and the entry face (0..5 = 2 * axis + (d[axis] < 0), -1 = none).  A miss has
+// node -1 and t 1e30.
+struct RayHit {
+    float t = 1e30f;
+    int node = -1;
+    int face = -1;
+    int size = 0;
+    int x = 0, y = 0, z = 0;
+    bool hit() const { return node >= 0; }
+};
+
 class RayTracerBVH {
 public:
+    enum QueryMode { First = RTO_QUERY_FIRST, Closest = RTO_QUERY_CLOSEST, Any = RTO_QUERY_ANY };
+
     RayTracerBVH();
     ~RayTracerBVH();
     RayTracerBVH(const RayTracerBVH&) = delete;
@@ -72,6 +86,14 @@ public:
 #ifndef RTO_REFERENCE_HEADERS   // needs this repo's localMC: the same buffer made on the host and uploaded (cross-check)
     void buildLeafTrianglesOnHost();
 #endif
+    // Ray queries over the whole resident octree (rto_query_rays_host): one RayHit per Ray, d need not be normalised, t in units
+    // of d, hits accepted for tMin <= t <= tMax.  The consumer the reference's struct Ray never had.
+    void intersectRays(const std::vector<Ray>& rays, std::vector<RayHit>& hits, int mode = Closest, float tMin = 0.0f,
+                       float tMax = 1e30f);
+    // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
+    // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
+    // click handler.  false (and out a miss) when nothing is hit.
+    bool pick(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RayHit& out);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

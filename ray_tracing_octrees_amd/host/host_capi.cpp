@@ -169,6 +169,26 @@ int rtoh_rt_framebuffer(const RayTracerBVH* rt, float* out, int64_t capacityFloa
     if (out && capacityFloats >= (int64_t)fb.size()) std::memcpy(out, fb.data(), fb.size() * sizeof(float));
     return 1;
 }
+// rays: n x (ox, oy, oz, dx, dy, dz); hits: n rto_hit records
+void rtoh_rt_intersect_rays(RayTracerBVH* rt, const float* rays, int64_t n, int mode, float tMin, float tMax, rto_hit* hits) {
+    std::vector<Ray> in((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        in[(size_t)i].origin = rto_host::vec3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+        in[(size_t)i].direction = rto_host::vec3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    }
+    std::vector<RayHit> out;
+    rt->intersectRays(in, out, mode, tMin, tMax);
+    for (int64_t i = 0; i < n; i++) {
+        const RayHit& h = out[(size_t)i];
+        hits[i] = rto_hit{ h.t, h.node, h.face, h.size, h.x, h.y, h.z, 0 };
+    }
+}
+int rtoh_rt_pick(RayTracerBVH* rt, const Camera* cam, int px, int py, int w, int h, float aspect, float fovDeg, rto_hit* out) {
+    RayHit r;
+    const bool hit = rt->pick(*cam, px, py, w, h, aspect, fovDeg, r);
+    *out = rto_hit{ r.t, r.node, r.face, r.size, r.x, r.y, r.z, 0 };
+    return hit ? 1 : 0;
+}
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }
 const char* rtoh_rt_last_error(const RayTracerBVH* rt) { return rt->lastError().c_str(); }
