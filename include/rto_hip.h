@@ -447,6 +447,36 @@ int  rto_query_pixels_device(rto_context* ctx, int mode, const rto_frame* frame,
                              rto_hit* d_hits, void* hip_stream);
 int  rto_query_pixels_host(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_hit* hits);
 
+/* ---- triangle queries -----------------------------------------------------
+ * The same rays against the resident leaf triangles (rto_build_leaf_triangles / rto_upload_leaf_triangles): the surface
+ * rto_render_triangles_* draws.  One rto_tri_hit per ray.  rto_ray, the modes, the pixel rays, the NaN and t_min > t_max misses,
+ * the 16-byte alignment, the error codes and the disregard of the frustum state are those of the box queries above.
+ *
+ * Acceptance rule ("Triangle queries").  A leaf is reachable when its box and every ancestor's pass the
+ * float32 slab test with tNear < 1e30 (the triangle render's box rule; boxes see no window).  A triangle of a reachable leaf is
+ * accepted when the renders' Moeller-Trumbore test hits it (t > 0) and t_min <= t <= min(t_max, largest float below 1e30).
+ *   FIRST    the render's rule: the first leaf in the reference's LIFO pop order that has an accepted triangle, under the
+ *            512-pop cap (a capped ray is a miss); in it the least t, ties to the lowest index.  The window decides only which
+ *            triangles count, never which nodes are popped.  With (0, 1e30) on a frame's pixel rays: exactly the t and triangle
+ *            rto_render_triangles_device shades.
+ *   CLOSEST  least t over the accepted triangles of all reachable leaves, ties to the lowest index; no cap.
+ *   ANY      a hit exactly when CLOSEST has one; which triangle is unspecified.
+ * RTO_E_NO_OCTREE when no leaf triangles are resident: a fresh context, or an rto_upload_octree / rto_build_octree since the last
+ * triangle build or upload. */
+typedef struct rto_tri_hit {        /* 32 bytes */
+    float   t;                      /* Moeller-Trumbore t of the accepted triangle; 1e30f for a miss */
+    int32_t tri;                    /* index into the resident triangle buffer (rto_download_leaf_triangles order); -1 = miss */
+    int32_t node;                   /* the leaf that owns it (tri_offset[node] <= tri < tri_offset[node+1]); -1 = miss */
+    float   u, v;                   /* barycentrics of the hit, as Moeller-Trumbore computes them; 0 for a miss */
+    float   nx, ny, nz;             /* the triangle's stored face normal, negated when dot(n, d) > 0 (the renders' turn); 0 for a miss */
+} rto_tri_hit;
+
+int  rto_query_triangles_device(rto_context* ctx, int mode, const rto_ray* d_rays, int64_t n, rto_tri_hit* d_hits, void* hip_stream);
+int  rto_query_triangles_host(rto_context* ctx, int mode, const rto_ray* rays, int64_t n, rto_tri_hit* hits);
+int  rto_query_triangle_pixels_device(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* d_xy, int64_t n,
+                                      rto_tri_hit* d_hits, void* hip_stream);
+int  rto_query_triangle_pixels_host(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_tri_hit* hits);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -2657,3 +2657,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_split.inc"
 #include "rto_comm.inc"
 #include "rto_query.inc"
+#include "rto_tri_query.inc"

@@ -36,6 +36,7 @@ SYMBOLS = (
     "rto_debug_set_tile_mask", "rto_debug_tile_mask_info", "rto_render_closest_device", "rto_render_closest_host", "rto_render_skip_device", "rto_render_skip_host", "rto_probe_skip_device", "rto_probe_skip_host",
     "rto_scene_bounds_get", "rto_scene_bounds_of_nodes", "rto_split_plan_make", "rto_split_part_of_rank", "rto_split_rows_of_part", "rto_split_row_source",
     "rto_query_rays_device", "rto_query_rays_host", "rto_query_pixels_device", "rto_query_pixels_host",
+    "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
 )
 SPLIT_MAX_FRAMES = 32
 QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
@@ -45,6 +46,9 @@ RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("t_min", "<f
                       ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("t_max", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("node", "<i4"), ("face", "<i4"), ("size", "<i4"),
                       ("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("reserved", "<i4")])
+# struct rto_tri_hit, 32 bytes
+TRI_HIT_DTYPE = np.dtype([("t", "<f4"), ("tri", "<i4"), ("node", "<i4"), ("u", "<f4"), ("v", "<f4"),
+                          ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")])
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
 
@@ -67,6 +71,11 @@ class Partition(C.Structure):
 class Ray(C.Structure):
     _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("t_min", C.c_float),
                 ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("t_max", C.c_float)]
+
+
+class TriHit(C.Structure):
+    _fields_ = [("t", C.c_float), ("tri", C.c_int32), ("node", C.c_int32), ("u", C.c_float), ("v", C.c_float),
+                ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float)]
 
 
 class Hit(C.Structure):
@@ -228,6 +237,10 @@ def load():
     L.rto_query_rays_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
     L.rto_query_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
     L.rto_query_pixels_host.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp]
+    L.rto_query_triangles_device.argtypes = [vp, C.c_int, vp, C.c_int64, vp, vp]
+    L.rto_query_triangles_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
+    L.rto_query_triangle_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
+    L.rto_query_triangle_pixels_host.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -527,6 +540,38 @@ class Context:
     def query_pixels_device(self, mode: int, frame: Frame, d_xy: int, n: int, d_hits: int, stream: int = 0):
         self._check(self._L.rto_query_pixels_device(self._h, int(mode), C.byref(frame), C.c_void_p(d_xy) if d_xy else None, int(n),
                                                     C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    # -- triangle queries (the resident leaf triangles) --------------------
+    def query_triangles(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:
+        """Caller-supplied rays against the resident leaf triangles (rto_query_triangles_host): origins (n, 3) or one origin,
+        dirs (n, 3), t_min / t_max scalars or per-ray arrays.  Returns a TRI_HIT_DTYPE array (tri -1, t 1e30 for a miss)."""
+        return self.query_triangle_records(make_rays(origins, dirs, t_min, t_max), mode)
+
+    def query_triangle_records(self, rays: np.ndarray, mode: int = QUERY_CLOSEST) -> np.ndarray:
+        """The same for a RAY_DTYPE array."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.zeros(len(rays), TRI_HIT_DTYPE)
+        self._check(self._L.rto_query_triangles_host(self._h, int(mode), rays.ctypes.data, len(rays), hits.ctypes.data))
+        return hits
+
+    def query_triangles_device(self, mode: int, d_rays: int, n: int, d_hits: int, stream: int = 0):
+        """Asynchronous: n rto_ray records at d_rays -> n rto_tri_hit records at d_hits (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_triangles_device(self._h, int(mode), C.c_void_p(d_rays) if d_rays else None, int(n),
+                                                       C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    def query_triangle_pixels(self, frame: Frame, xy, mode: int = QUERY_FIRST) -> np.ndarray:
+        """The renders' own rays through pixels (x, y) of `frame` against the leaf triangles: a TRI_HIT_DTYPE array.  FIRST gives
+        the triangle and t render_triangles_* shades there."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.int32).reshape(-1, 2))
+        hits = np.zeros(len(xy), TRI_HIT_DTYPE)
+        self._check(self._L.rto_query_triangle_pixels_host(self._h, int(mode), C.byref(frame), xy.ctypes.data, len(xy),
+                                                           hits.ctypes.data))
+        return hits
+
+    def query_triangle_pixels_device(self, mode: int, frame: Frame, d_xy: int, n: int, d_hits: int, stream: int = 0):
+        self._check(self._L.rto_query_triangle_pixels_device(self._h, int(mode), C.byref(frame), C.c_void_p(d_xy) if d_xy else None,
+                                                             int(n), C.c_void_p(d_hits) if d_hits else None,
+                                                             C.c_void_p(stream) if stream else None))
 
     def render_closest_host(self, frame: Frame, stats: bool = False):
         """The reference's closest-hit traversal (its earlier, block-commented shader): RGBA frame [, {rays, pops, hits}]."""

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import HIT_DTYPE, NODE_DTYPE, RtoError, _f
+from .hip import HIT_DTYPE, NODE_DTYPE, TRI_HIT_DTYPE, RtoError, _f
 
 _lib = None
 _vp = C.c_void_p
@@ -120,6 +120,10 @@ def load():
     L.rtoh_rt_intersect_rays.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
+    L.rtoh_rt_intersect_triangles.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp, _vp]
+    L.rtoh_rt_intersect_triangles.restype = None
+    L.rtoh_rt_pick_surface.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp]
+    L.rtoh_rt_pick_surface.restype = C.c_int
     _lib = L
     return L
 
@@ -385,6 +389,28 @@ class RayTracerBVH:
         out = np.zeros(1, HIT_DTYPE)
         hit = load().rtoh_rt_pick(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg), out.ctypes.data)
         return out[0] if hit else None
+
+    def intersectTriangles(self, origins, dirs, mode: int = 1, tMin: float = 0.0, tMax: float = 1e30):
+        """Addition: RayTracerBVH::intersectTriangles -- rays against the resident leaf triangles.  Returns (hits, points): a
+        structured array of rto_tri_hit records (hip.TRI_HIT_DTYPE; tri -1 = miss) and the (n, 3) hit points o + d t (0 for a
+        miss).  mode: 0 first, 1 closest (default), 2 any."""
+        d = np.asarray(dirs, np.float32).reshape(-1, 3)
+        o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
+        rays = np.ascontiguousarray(np.concatenate([o, d], 1), dtype=np.float32)
+        hits = np.zeros(len(d), TRI_HIT_DTYPE)
+        points = np.zeros((len(d), 3), np.float32)
+        load().rtoh_rt_intersect_triangles(self._h, rays.ctypes.data, len(d), int(mode), _f(tMin), _f(tMax), hits.ctypes.data,
+                                           points.ctypes.data)
+        return hits, points
+
+    def pickSurface(self, camera: Camera, px: int, py: int, width: int, height: int, aspect: float, fovDeg: float):
+        """Addition: RayTracerBVH::pickSurface -- the triangle renderSceneTriangles shows at pixel (px, py): (rto_tri_hit record,
+        point (3,)), or None."""
+        out = np.zeros(1, TRI_HIT_DTYPE)
+        point = np.zeros(3, np.float32)
+        hit = load().rtoh_rt_pick_surface(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg),
+                                          out.ctypes.data, point.ctypes.data)
+        return (out[0], point) if hit else None
 
     def finish(self):
         """Wait for the GPU(s): the counterpart of glFinish for timing loops (renders are asynchronous)."""

@@ -5,6 +5,7 @@
 
 #include <dlfcn.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,6 +37,8 @@ struct HipApi {
     decltype(&rto_comm_render_resident_all) comm_render_resident_all = nullptr;
     decltype(&rto_query_rays_host) query_rays_host = nullptr;
     decltype(&rto_query_pixels_host) query_pixels_host = nullptr;
+    decltype(&rto_query_triangles_host) query_triangles_host = nullptr;
+    decltype(&rto_query_triangle_pixels_host) query_triangle_pixels_host = nullptr;
     std::string error;
 
     bool load() {
@@ -83,6 +86,8 @@ struct HipApi {
         comm_render_resident_all = reinterpret_cast<decltype(comm_render_resident_all)>(sym("rto_comm_render_resident_all"));
         query_rays_host = reinterpret_cast<decltype(query_rays_host)>(sym("rto_query_rays_host"));
         query_pixels_host = reinterpret_cast<decltype(query_pixels_host)>(sym("rto_query_pixels_host"));
+        query_triangles_host = reinterpret_cast<decltype(query_triangles_host)>(sym("rto_query_triangles_host"));
+        query_triangle_pixels_host = reinterpret_cast<decltype(query_triangle_pixels_host)>(sym("rto_query_triangle_pixels_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -349,6 +354,88 @@ bool RayTracerBVH::pick(const Camera& camera, int px, int py, int width, int hei
     }
     out = to_ray_hit(h);
     return out.hit();
+}
+
+// The renders' ray direction through pixel (px, py) (S/RT:338-355 in the oracle's operation order: what fill_params and
+// generate_ray_tab compute on the device), so that pickSurface's point is o + d t on the very ray the frame traced.
+static rto_host::vec3 pixel_direction(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg) {
+    const auto view = camera.getView();
+#ifdef RTO_REFERENCE_HEADERS
+    const auto m = glm::inverse(view);
+    const float tanHalfFov = std::tan(glm::radians(fovDeg) * 0.5f);
+#else
+    const auto m = rtmath::inverse(view);
+    const float tanHalfFov = std::tan(rtmath::radians(fovDeg) * 0.5f);
+#endif
+    float nx = ((float)px + 0.5f) / (float)width * 2.0f - 1.0f;
+    float ny = 1.0f - ((float)py + 0.5f) / (float)height * 2.0f;
+    nx *= aspect;
+    nx *= tanHalfFov;
+    ny *= tanHalfFov;
+    const float d4 = (nx * nx + ny * ny) + ((-1.0f) * (-1.0f) + 0.0f * 0.0f);
+    const float inv4 = 1.0f / std::sqrt(d4);
+    const float vx = nx * inv4, vy = ny * inv4, vz = (-1.0f) * inv4, vw = 0.0f * inv4;
+    const float wx = (m[0][0] * vx + m[1][0] * vy) + (m[2][0] * vz + m[3][0] * vw);
+    const float wy = (m[0][1] * vx + m[1][1] * vy) + (m[2][1] * vz + m[3][1] * vw);
+    const float wz = (m[0][2] * vx + m[1][2] * vy) + (m[2][2] * vz + m[3][2] * vw);
+    const float tx = wx * wx, ty = wy * wy, tz = wz * wz;
+    const float s = 1.0f / std::sqrt(tx + ty + tz);
+    return rto_host::vec3(wx * s, wy * s, wz * s);
+}
+
+static TriangleHit to_triangle_hit(const rto_tri_hit& h, const rto_host::vec3& o, const rto_host::vec3& d) {
+    TriangleHit r;
+    if (h.tri < 0) return r;
+    r.t = h.t; r.tri = h.tri; r.node = h.node; r.u = h.u; r.v = h.v;
+    r.point = rto_host::vec3(o.x + d.x * h.t, o.y + d.y * h.t, o.z + d.z * h.t);
+    r.normal = rto_host::vec3(h.nx, h.ny, h.nz);
+    return r;
+}
+
+void RayTracerBVH::intersectTriangles(const std::vector<Ray>& rays, std::vector<TriangleHit>& hits, int mode, float tMin, float tMax) {
+    hits.assign(rays.size(), TriangleHit());
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return;
+    }
+    if (rays.empty() || m_numNodes <= 0) return;
+    std::vector<rto_ray> in(rays.size());
+    for (size_t i = 0; i < rays.size(); i++) {
+        const Ray& r = rays[i];
+        in[i] = rto_ray{ r.origin.x, r.origin.y, r.origin.z, tMin, r.direction.x, r.direction.y, r.direction.z, tMax };
+    }
+    std::vector<rto_tri_hit> out(rays.size());
+    if (api().query_triangles_host(m_ctx, mode, in.data(), (int64_t)in.size(), out.data()) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] triangle query failed: " << m_lastError << std::endl;
+        return;
+    }
+    for (size_t i = 0; i < out.size(); i++) hits[i] = to_triangle_hit(out[i], rays[i].origin, rays[i].direction);
+}
+
+bool RayTracerBVH::pickSurface(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, TriangleHit& out) {
+    out = TriangleHit();
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return false;
+    }
+    if (m_numNodes <= 0 || width <= 0 || height <= 0 || px < 0 || px >= width || py < 0 || py >= height) return false;
+    rto_frame f;
+    const auto view = camera.getView();
+    std::memcpy(f.view, &view[0][0], sizeof f.view);
+    const auto pos = camera.getPos();
+    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
+    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const int32_t xy[2] = { px, py };
+    rto_tri_hit h;
+    if (api().query_triangle_pixels_host(m_ctx, RTO_QUERY_FIRST, &f, xy, 1, &h) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] pickSurface failed: " << m_lastError << std::endl;
+        return false;
+    }
+    if (h.tri < 0) return false;
+    out = to_triangle_hit(h, pos, pixel_direction(camera, px, py, width, height, aspect, fovDeg));
+    return true;
 }
 
 const std::vector<float>& RayTracerBVH::framebuffer() const {

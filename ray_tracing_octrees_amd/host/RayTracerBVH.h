@@ -57,6 +57,19 @@ struct RayHit {
     bool hit() const { return node >= 0; }
 };
 
+// What a triangle query found (the fields of rto_tri_hit, include/rto_hip.h): the accepted triangle's index in the resident
+// triangle buffer, the leaf that owns it, the ray parameter t, the hit point o + d t, the barycentrics u, v (the point is
+// (1 - u - v) v0 + u v1 + v v2) and the stored face normal turned against the ray.  A miss has tri -1 and t 1e30.
+struct TriangleHit {
+    float t = 1e30f;
+    int tri = -1;
+    int node = -1;
+    float u = 0.0f, v = 0.0f;
+    rto_host::vec3 point = rto_host::vec3(0.0f, 0.0f, 0.0f);
+    rto_host::vec3 normal = rto_host::vec3(0.0f, 0.0f, 0.0f);
+    bool hit() const { return tri >= 0; }
+};
+
 class RayTracerBVH {
 public:
     enum QueryMode { First = RTO_QUERY_FIRST, Closest = RTO_QUERY_CLOSEST, Any = RTO_QUERY_ANY };
@@ -94,6 +107,14 @@ public:
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
     bool pick(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RayHit& out);
+    // The same queries against the resident leaf triangles (rto_query_triangles_host, DESIGN.md section 10 "Triangle queries"):
+    // one TriangleHit per Ray.  First is renderSceneTriangles' rule, Closest the nearest surface, Any occlusion (a shadow ray
+    // towards a point light: tMax = the distance to it in units of d).
+    void intersectTriangles(const std::vector<Ray>& rays, std::vector<TriangleHit>& hits, int mode = Closest, float tMin = 0.0f,
+                            float tMax = 1e30f);
+    // The triangle renderSceneTriangles shows at pixel (px, py) (row 0 = top): the render's own ray and its FIRST rule
+    // (rto_query_triangle_pixels_host), with the surface point, barycentrics and normal.  false (and out a miss) when nothing is hit.
+    bool pickSurface(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, TriangleHit& out);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

@@ -189,6 +189,33 @@ int rtoh_rt_pick(RayTracerBVH* rt, const Camera* cam, int px, int py, int w, int
     *out = rto_hit{ r.t, r.node, r.face, r.size, r.x, r.y, r.z, 0 };
     return hit ? 1 : 0;
 }
+static rto_tri_hit to_rto_tri_hit(const TriangleHit& h) {
+    return rto_tri_hit{ h.t, h.tri, h.node, h.u, h.v, h.normal.x, h.normal.y, h.normal.z };
+}
+// rays: n x (ox, oy, oz, dx, dy, dz); hits: n rto_tri_hit records; points: n x 3 floats (o + d t; NULL: not wanted)
+void rtoh_rt_intersect_triangles(RayTracerBVH* rt, const float* rays, int64_t n, int mode, float tMin, float tMax, rto_tri_hit* hits,
+                                 float* points) {
+    std::vector<Ray> in((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        in[(size_t)i].origin = rto_host::vec3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+        in[(size_t)i].direction = rto_host::vec3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    }
+    std::vector<TriangleHit> out;
+    rt->intersectTriangles(in, out, mode, tMin, tMax);
+    for (int64_t i = 0; i < n; i++) {
+        const TriangleHit& h = out[(size_t)i];
+        hits[i] = to_rto_tri_hit(h);
+        if (points) { points[3 * i] = h.point.x; points[3 * i + 1] = h.point.y; points[3 * i + 2] = h.point.z; }
+    }
+}
+int rtoh_rt_pick_surface(RayTracerBVH* rt, const Camera* cam, int px, int py, int w, int h, float aspect, float fovDeg, rto_tri_hit* out,
+                         float* point) {
+    TriangleHit r;
+    const bool hit = rt->pickSurface(*cam, px, py, w, h, aspect, fovDeg, r);
+    *out = to_rto_tri_hit(r);
+    if (point) { point[0] = r.point.x; point[1] = r.point.y; point[2] = r.point.z; }
+    return hit ? 1 : 0;
+}
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }
 const char* rtoh_rt_last_error(const RayTracerBVH* rt) { return rt->lastError().c_str(); }
