@@ -477,6 +477,42 @@ int  rto_query_triangle_pixels_device(rto_context* ctx, int mode, const rto_fram
                                       rto_tri_hit* d_hits, void* hip_stream);
 int  rto_query_triangle_pixels_host(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_tri_hit* hits);
 
+/* ---- voxel edits ----------------------------------------------------------
+ * Brushes carve (-> EMPTY = 0) or fill (-> FILLED = 1) the voxel grid rto_build_octree keeps in HBM; the octree is then rebuilt
+ * from that grid on the GPU, with no host copy.  Rule, exact in integers at 1/64 voxel:
+ *   cq[a] = floor((centre[a] - gridMin[a]) / voxelSize * 64 + 0.5), eq[a] = floor(extent[a] / voxelSize * 64 + 0.5), in double
+ *   from the context's float gridMin / voxelSize; D[a] = 64 (2 i[a] + 1) - 2 cq[a] for voxel (i0, i1, i2), the cell [i, i + 1);
+ *   SPHERE (radius extent[0]): D0^2 + D1^2 + D2^2 <= (2 eq[0])^2;  BOX: |D[a]| <= 2 eq[a] on every axis.
+ * A brush is invalid (RTO_E_INVALID) for an unknown shape or op, a NaN or infinite input, a negative extent, or |cq| or eq above
+ * 2^27.  Brushes apply in array order (the later one wins); voxels outside the grid's dims do not exist, the grid never grows.
+ * rto_edit_voxels: *changed (may be NULL) = voxels whose final value differs from their value before the call.  When it is > 0
+ * the context is then as rto_build_octree(edited grid, same gridMin, same voxelSize) leaves it (nodes, descriptors, info, scene
+ * bounds; frustum culling off), on the build path rto_debug_set_build_path chose, and leaf triangles that were resident are
+ * rebuilt from the edited grid as rto_build_leaf_triangles(NULL) builds them.  changed == 0 touches nothing.  n == 0: no-op.
+ * RTO_E_NO_OCTREE: no octree; RTO_E_UNSUPPORTED: the octree came from rto_upload_octree (no resident grid); RTO_E_INVALID: an
+ * invalid brush, NULL brushes with n > 0, n < 0 or n > RTO_EDIT_MAX_BRUSHES.  Every error leaves the context untouched.
+ * Synchronous on the context's stream. */
+#define RTO_BRUSH_SPHERE 0
+#define RTO_BRUSH_BOX    1
+#define RTO_EDIT_CARVE   0   /* -> EMPTY  */
+#define RTO_EDIT_FILL    1   /* -> FILLED */
+#define RTO_EDIT_MAX_BRUSHES 65536
+typedef struct rto_brush {          /* 32 bytes */
+    float   centre[3];              /* world units */
+    float   extent[3];              /* SPHERE: radius in extent[0] (extent[1..2] are checked, not used); BOX: half-sizes */
+    int32_t shape;                  /* RTO_BRUSH_* */
+    int32_t op;                     /* RTO_EDIT_* */
+} rto_brush;
+
+int  rto_edit_voxels(rto_context* ctx, const rto_brush* brushes, int n, int64_t* changed);
+/* The resident grid, dims[2] x dims[1] x dims[0] bytes, x fastest (rto_build_octree's layout).  out == NULL: dims only (dims may
+ * be NULL).  Errors as rto_edit_voxels; RTO_E_INVALID when capacity is below the grid's size. */
+int  rto_download_voxels(rto_context* ctx, uint8_t* out, int64_t capacity, int dims[3]);
+/* Device time in ms of the last rto_edit_voxels: the brush kernel, the octree rebuild, the triangle rebuild (-1: not run). */
+int  rto_last_edit_ms(const rto_context* ctx, float ms[3]);
+/* Pure host function, no device: the quantised brush of the rule above for this grid, or RTO_E_INVALID. */
+int  rto_brush_quantize(const rto_brush* brush, const float grid_min[3], float voxel_size, int64_t cq[3], int64_t eq[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

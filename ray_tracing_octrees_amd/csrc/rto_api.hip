@@ -149,6 +149,7 @@ struct rto_context {
     bool asyncPooled = false;  // d_nodes / d_desc come from the stream-ordered memory pool (hipMallocAsync): a rebuild reuses them without hipMalloc
     int buildPath = 0;         // 0 = automatic (Morton-order build where it applies), 1 = level-by-level build (rto_debug_set_build_path)
     float buildUploadMs = -1.f;
+    float editMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_voxels: brushes, octree rebuild, triangle rebuild (-1: not run)
 };
 
 static thread_local std::string g_createError;
@@ -198,7 +199,8 @@ static void free_cull_buffers(rto_context* c) {
     (void)hipFree(c->d_compact); c->d_compact = nullptr;
 }
 
-static void free_octree(rto_context* c) {
+// The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rto_edit_voxels rebuilds from it).
+static void free_octree_arrays(rto_context* c) {
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -214,12 +216,16 @@ static void free_octree(rto_context* c) {
     (void)hipFree(c->d_tris); c->d_tris = nullptr;
     (void)hipFree(c->d_triOffset); c->d_triOffset = nullptr;
     (void)hipFree(c->d_triRec); c->d_triRec = nullptr;
-    (void)hipFree(c->d_vox); c->d_vox = nullptr;
-    c->voxDim[0] = c->voxDim[1] = c->voxDim[2] = 0;
     c->numTris = 0;
     for (auto& kv : c->orders) { kv.second.tab[0].valid = kv.second.tab[1].valid = false; kv.second.costValid = false; }
     c->numNodes = c->numInternal = 0;
     c->canonical = false; c->culling = false; c->rootVisible = 1; c->visibleNodes = 0;
+}
+
+static void free_octree(rto_context* c) {
+    free_octree_arrays(c);
+    (void)hipFree(c->d_vox); c->d_vox = nullptr;
+    c->voxDim[0] = c->voxDim[1] = c->voxDim[2] = 0;
 }
 
 extern "C" {
@@ -550,7 +556,8 @@ static int build_cells_impl(rto_context* c) {
 
 // The four-launch build (k_mb_*): fills c->d_nodes / d_desc / d_descFirstChild from c->d_vox.  *total / *internal: sizes;
 // solidBox: lo[3], hi[3] of the cells that hold FILLED voxels (level-1 cell precision; lo > hi: nothing solid).
-// The voxels are uploaded here (between the events e0 and e1), after the scratch has been allocated and the chunk sums zeroed.
+// Host voxels (if any) are uploaded here (between the events e0 and e1), after the scratch has been allocated and the chunk sums
+// zeroed; voxels == nullptr: c->d_vox already holds the grid (rto_edit_voxels) and e0, e1 bracket nothing.
 static int build_octree_morton(rto_context* c, hipStream_t s, BuildScratch& scratch, int R, int dimX, int dimY, int dimZ,
                                const uint8_t* voxels, hipEvent_t e0, hipEvent_t e1, int64_t* total, int64_t* internal, int solidBox[6]) {
     MbLevels Lv;
@@ -587,7 +594,7 @@ static int build_octree_morton(rto_context* c, hipStream_t s, BuildScratch& scra
     RTO_HIP(c, scratch.alloc(&d_tab, 1));
     RTO_HIP(c, hipMemsetAsync(d_chunk, 0, ((size_t)chunks + 1) * sizeof(int), s));       // summed into by atomics
     RTO_HIP(c, hipEventRecord(e0, s));
-    RTO_HIP(c, hipMemcpyAsync(c->d_vox, voxels, (size_t)dimX * dimY * dimZ, hipMemcpyHostToDevice, s));
+    if (voxels) RTO_HIP(c, hipMemcpyAsync(c->d_vox, voxels, (size_t)dimX * dimY * dimZ, hipMemcpyHostToDevice, s));
     RTO_HIP(c, hipEventRecord(e1, s));
     hipLaunchKernelGGL(k_mb_bricks, dim3((unsigned)numBricks), dim3(kBlock), 0, s, c->d_vox, Lv, bricksX, runsX, bricksY, d_brickBox, d_chunk);
     hipLaunchKernelGGL(k_mb_top_scan, dim3(1), dim3(1024), 0, s, Lv, d_brickBox, numBricks, d_chunk, d_tab);
@@ -623,6 +630,8 @@ static int build_octree_morton(rto_context* c, hipStream_t s, BuildScratch& scra
     return RTO_OK;
 }
 
+static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R);
+
 extern "C" {
 
 int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, int dimZ, const float grid_min[3], float voxel_size) {
@@ -639,6 +648,19 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
     free_octree(c);
     std::memcpy(c->gridMin, grid_min, sizeof c->gridMin);
     c->voxelSize = voxel_size;
+    uint8_t* d_vox = nullptr;
+    RTO_HIP(c, hipMalloc(&d_vox, (size_t)dimX * dimY * dimZ));
+    c->d_vox = d_vox; c->voxDim[0] = dimX; c->voxDim[1] = dimY; c->voxDim[2] = dimZ;    // kept: rto_build_leaf_triangles and rto_edit_voxels read it
+    return build_octree_resident(c, voxels, R);
+}
+
+}  // extern "C"
+
+// The build proper: the octree of the grid in c->d_vox (dims c->voxDim, root 2^R), into arrays the caller has freed (free_octree /
+// free_octree_arrays).  voxels != nullptr (rto_build_octree): they are first copied into c->d_vox, between the events e0 and e1;
+// nullptr (rto_edit_voxels): c->d_vox already holds them and the upload time reads 0.
+static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
+    const int dimX = c->voxDim[0], dimY = c->voxDim[1], dimZ = c->voxDim[2];
     hipStream_t s = c->stream;
     BuildScratch scratch(c->stream);
     hipEvent_t e0, e1, e2;
@@ -647,9 +669,7 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
 
     // ---- voxels -> HBM
     const size_t nvox = (size_t)dimX * dimY * dimZ;
-    uint8_t* d_vox = nullptr;
-    RTO_HIP(c, hipMalloc(&d_vox, nvox));
-    c->d_vox = d_vox; c->voxDim[0] = dimX; c->voxDim[1] = dimY; c->voxDim[2] = dimZ;    // kept: rto_build_leaf_triangles reads it
+    uint8_t* d_vox = c->d_vox;
     int64_t total = 0, internal = 0;
     int box[6];
     bool haveBox = false;              // the Morton-order build delivers the solid box with its one read-back
@@ -662,7 +682,7 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
         haveBox = true;
     } else {
         RTO_HIP(c, hipEventRecord(e0, s));
-        RTO_HIP(c, hipMemcpyAsync(d_vox, voxels, nvox, hipMemcpyHostToDevice, s));
+        if (voxels) RTO_HIP(c, hipMemcpyAsync(d_vox, voxels, nvox, hipMemcpyHostToDevice, s));
         RTO_HIP(c, hipEventRecord(e1, s));
         // level-by-level form (any depth up to kMaxDepth; also the cross-check of the other: rto_debug_set_build_path)
         // ---- occupancy pyramid, bottom-up; every level also leaves its number of mixed cells = internal nodes
@@ -777,6 +797,8 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
     c->canonical = internal > 0;                 // a one-node tree is rendered by the generic kernel
     return build_cells(c);
 }
+
+extern "C" {
 
 int rto_debug_set_build_path(rto_context* c, int level_by_level) {
     if (!c) return RTO_E_INVALID;
@@ -2658,3 +2680,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_comm.inc"
 #include "rto_query.inc"
 #include "rto_tri_query.inc"
+#include "rto_edit.inc"

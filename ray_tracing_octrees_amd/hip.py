@@ -37,6 +37,7 @@ SYMBOLS = (
     "rto_scene_bounds_get", "rto_scene_bounds_of_nodes", "rto_split_plan_make", "rto_split_part_of_rank", "rto_split_rows_of_part", "rto_split_row_source",
     "rto_query_rays_device", "rto_query_rays_host", "rto_query_pixels_device", "rto_query_pixels_host",
     "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
+    "rto_edit_voxels", "rto_download_voxels", "rto_last_edit_ms", "rto_brush_quantize",
 )
 SPLIT_MAX_FRAMES = 32
 QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
@@ -49,6 +50,11 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("node", "<i4"), ("face", "<i4"), ("size", "
 # struct rto_tri_hit, 32 bytes
 TRI_HIT_DTYPE = np.dtype([("t", "<f4"), ("tri", "<i4"), ("node", "<i4"), ("u", "<f4"), ("v", "<f4"),
                           ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")])
+# struct rto_brush, 32 bytes: voxel edits (rto_edit_voxels)
+BRUSH_SPHERE, BRUSH_BOX = 0, 1
+EDIT_CARVE, EDIT_FILL = 0, 1
+EDIT_MAX_BRUSHES = 65536
+BRUSH_DTYPE = np.dtype([("centre", "<f4", (3,)), ("extent", "<f4", (3,)), ("shape", "<i4"), ("op", "<i4")])
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
 
@@ -78,6 +84,10 @@ class TriHit(C.Structure):
                 ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float)]
 
 
+class Brush(C.Structure):
+    _fields_ = [("centre", C.c_float * 3), ("extent", C.c_float * 3), ("shape", C.c_int32), ("op", C.c_int32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("node", C.c_int32), ("face", C.c_int32), ("size", C.c_int32),
                 ("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("reserved", C.c_int32)]
@@ -93,6 +103,31 @@ def make_rays(origins, dirs, t_min=0.0, t_max=1e30) -> np.ndarray:
     r["t_min"] = np.broadcast_to(np.asarray(t_min, np.float32), len(d))
     r["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), len(d))
     return r
+
+
+def make_brushes(centres, extents, shape=BRUSH_SPHERE, op=EDIT_CARVE) -> np.ndarray:
+    """A BRUSH_DTYPE array from (n, 3) centres; extents as (n, 3) per-axis half-sizes, or (n,) / one scalar (a radius, or the
+    half-size on every axis); shape and op as one scalar or one per brush."""
+    c = np.asarray(centres, np.float32).reshape(-1, 3)
+    e = np.asarray(extents, np.float32)
+    e = np.broadcast_to(e, c.shape) if e.ndim == 2 else np.repeat(np.broadcast_to(e, (len(c),))[:, None], 3, axis=1)
+    b = np.zeros(len(c), BRUSH_DTYPE)
+    b["centre"], b["extent"] = c, e
+    b["shape"] = np.broadcast_to(np.asarray(shape, np.int32), len(c))
+    b["op"] = np.broadcast_to(np.asarray(op, np.int32), len(c))
+    return b
+
+
+def brush_quantize(brush, grid_min, voxel_size):
+    """rto_brush_quantize: (cq, eq) as two tuples of int for one BRUSH_DTYPE record; RtoError(RTO_E_INVALID) for an invalid brush."""
+    L = load()
+    b = np.ascontiguousarray(np.asarray(brush, BRUSH_DTYPE).reshape(1))
+    gm = (C.c_float * 3)(*[_f(x) for x in grid_min])
+    cq, eq = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    rc = L.rto_brush_quantize(b.ctypes.data, gm, _f(voxel_size), cq, eq)
+    if rc != RTO_OK:
+        raise RtoError(rc, "rto_brush_quantize: invalid brush")
+    return tuple(cq), tuple(eq)
 
 
 class Stats(C.Structure):
@@ -241,6 +276,10 @@ def load():
     L.rto_query_triangles_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
     L.rto_query_triangle_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
     L.rto_query_triangle_pixels_host.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp]
+    L.rto_edit_voxels.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int64)]
+    L.rto_download_voxels.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
+    L.rto_last_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_brush_quantize.argtypes = [vp, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -659,6 +698,29 @@ class Context:
         if n.value:
             self._check(self._L.rto_timing_read(self._h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    # -- voxel edits -----------------------------------------------------------
+    def edit_voxels(self, brushes) -> int:
+        """rto_edit_voxels: apply BRUSH_DTYPE brushes (make_brushes) to the resident grid in order and rebuild; the number of
+        voxels that changed."""
+        b = np.ascontiguousarray(np.asarray(brushes, BRUSH_DTYPE).reshape(-1))
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_voxels(self._h, b.ctypes.data if len(b) else None, len(b), C.byref(changed)))
+        return changed.value
+
+    def download_voxels(self) -> np.ndarray:
+        """The resident grid as uint8 (dimZ, dimY, dimX): build_octree's input layout."""
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.uint8)
+        self._check(self._L.rto_download_voxels(self._h, out.ctypes.data, out.size, dims))
+        return out
+
+    def last_edit_ms(self):
+        """Device ms of the last edit: (brushes, octree rebuild, triangle rebuild); -1 for a step that did not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_edit_ms(self._h, ms))
+        return tuple(ms)
 
     def scene_bounds(self) -> SceneBounds:
         b = SceneBounds()

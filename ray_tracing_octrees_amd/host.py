@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import HIT_DTYPE, NODE_DTYPE, TRI_HIT_DTYPE, RtoError, _f
+from .hip import BRUSH_DTYPE, HIT_DTYPE, NODE_DTYPE, TRI_HIT_DTYPE, RtoError, _f
 
 _lib = None
 _vp = C.c_void_p
@@ -124,6 +124,9 @@ def load():
     L.rtoh_rt_intersect_triangles.restype = None
     L.rtoh_rt_pick_surface.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp]
     L.rtoh_rt_pick_surface.restype = C.c_int
+    L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
+    L.rtoh_rt_edit_voxels.restype = C.c_int64
+    L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
     _lib = L
     return L
 
@@ -411,6 +414,23 @@ class RayTracerBVH:
         hit = load().rtoh_rt_pick_surface(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg),
                                           out.ctypes.data, point.ctypes.data)
         return (out[0], point) if hit else None
+
+    def editVoxels(self, brushes) -> int:
+        """Addition: RayTracerBVH::editVoxels -- hip.BRUSH_DTYPE brushes (hip.make_brushes), in order, on the grid every GPU holds,
+        then the rebuild there.  Returns the number of voxels changed (-1: the edit failed, see lastError)."""
+        b = np.asarray(brushes, BRUSH_DTYPE).reshape(-1)
+        f = np.ascontiguousarray(np.concatenate([b["centre"], b["extent"]], 1), dtype=np.float32)
+        shapes = np.ascontiguousarray(b["shape"], dtype=np.int32)
+        ops = np.ascontiguousarray(b["op"], dtype=np.int32)
+        return int(load().rtoh_rt_edit_voxels(self._h, f.ctypes.data, shapes.ctypes.data, ops.ctypes.data, len(b)))
+
+    def grid(self) -> np.ndarray:
+        """Addition: RayTracerBVH::grid -- the current voxels, uint8 (dimZ, dimY, dimX), every edit applied."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        out = np.empty((dims[2], dims[1], dims[0]), np.uint8)
+        load().rtoh_rt_grid(self._h, dims, out.ctypes.data)
+        return out
 
     def finish(self):
         """Wait for the GPU(s): the counterpart of glFinish for timing loops (renders are asynchronous)."""

@@ -39,6 +39,10 @@ struct HipApi {
     decltype(&rto_query_pixels_host) query_pixels_host = nullptr;
     decltype(&rto_query_triangles_host) query_triangles_host = nullptr;
     decltype(&rto_query_triangle_pixels_host) query_triangle_pixels_host = nullptr;
+    decltype(&rto_edit_voxels) edit_voxels = nullptr;
+    decltype(&rto_download_voxels) download_voxels = nullptr;
+    decltype(&rto_download_leaf_triangles) download_leaf_triangles = nullptr;
+    decltype(&rto_download_nodes) download_nodes = nullptr;
     std::string error;
 
     bool load() {
@@ -88,6 +92,10 @@ struct HipApi {
         query_pixels_host = reinterpret_cast<decltype(query_pixels_host)>(sym("rto_query_pixels_host"));
         query_triangles_host = reinterpret_cast<decltype(query_triangles_host)>(sym("rto_query_triangles_host"));
         query_triangle_pixels_host = reinterpret_cast<decltype(query_triangle_pixels_host)>(sym("rto_query_triangle_pixels_host"));
+        edit_voxels = reinterpret_cast<decltype(edit_voxels)>(sym("rto_edit_voxels"));
+        download_voxels = reinterpret_cast<decltype(download_voxels)>(sym("rto_download_voxels"));
+        download_leaf_triangles = reinterpret_cast<decltype(download_leaf_triangles)>(sym("rto_download_leaf_triangles"));
+        download_nodes = reinterpret_cast<decltype(download_nodes)>(sym("rto_download_nodes"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -163,6 +171,7 @@ std::vector<GPUNodes> RayTracerBVH::flatten(const OctreeNode* root) {
 void RayTracerBVH::setOctree(OctreeNode* root, const VoxelGrid& grid) {
     m_octreeRoot = root;
     m_grid = grid;                      // the reference copies the grid too (RayTracerBVH.cpp:433)
+    m_gridStale = false;
     m_flatNodes.clear();
     m_numNodes = 0;
     if (!root) return;                  // :439
@@ -179,6 +188,7 @@ void RayTracerBVH::setOctree(OctreeNode* root, const VoxelGrid& grid) {
 void RayTracerBVH::setOctreeFromGrid(const VoxelGrid& grid) {
     m_octreeRoot = nullptr;
     m_grid = grid;
+    m_gridStale = false;
     m_flatNodes.clear();
     m_numNodes = 0;
     if (!m_computeInited) ensureComputeInitialized();
@@ -276,10 +286,19 @@ void RayTracerBVH::buildLeafTrianglesOnHost() {
         std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
         return;
     }
-    if (m_flatNodes.empty()) return;
+    if (m_numNodes <= 0) return;
+    // the resident array: setOctree()'s, or (after setOctreeFromGrid / editVoxels) the one the GPU built
+    std::vector<GPUNodes> downloaded;
+    if (m_flatNodes.empty()) {
+        int64_t n = 0;
+        if (api().download_nodes(m_ctx, nullptr, 0, &n) != RTO_OK) { m_lastError = api().last_error(m_ctx); return; }
+        downloaded.resize((size_t)n);
+        if (api().download_nodes(m_ctx, reinterpret_cast<rto_node*>(downloaded.data()), n, &n) != RTO_OK) { m_lastError = api().last_error(m_ctx); return; }
+    }
+    const std::vector<GPUNodes>& nodes = m_flatNodes.empty() ? downloaded : m_flatNodes;
     std::vector<float> tris;
     std::vector<int32_t> off;
-    ::buildLeafTriangles(m_grid, GPUNodesView{ reinterpret_cast<const int32_t*>(m_flatNodes.data()), (int64_t)m_flatNodes.size() }, tris, off);
+    ::buildLeafTriangles(grid(), GPUNodesView{ reinterpret_cast<const int32_t*>(nodes.data()), (int64_t)nodes.size() }, tris, off);
     forEachContext([&](rto_context* c) { return api().upload_leaf_triangles(c, tris.data(), (int64_t)(tris.size() / 12), off.data()); }, "triangle upload");
 }
 #endif
@@ -481,4 +500,57 @@ void RayTracerBVH::renderSceneComputeWithCulling(const Camera& camera, int width
         if (!forEachContext([&](rto_context* c) { return api().update_frustum(c, &view[0][0], fovDeg, aspect, 1); }, "frustum update")) return;
     }
     render(camera, width, height, aspect, fovDeg);
+}
+
+// Carve / fill the resident grid on every GPU (rto_edit_voxels) and rebuild the octree there; triangles that were resident are
+// rebuilt too.  After setOctree() no grid is resident yet: the first edit builds the octree from m_grid (the same array, DESIGN.md
+// section 1, N4) and edits that.  m_grid is then stale; grid() fetches it when asked, never per edit.
+void RayTracerBVH::editVoxels(const std::vector<VoxelBrush>& brushes) {
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return;
+    }
+    m_lastEditChanged = -1;
+    if (m_numNodes <= 0) return;
+    std::vector<rto_brush> b(brushes.size());
+    for (size_t i = 0; i < brushes.size(); i++) {
+        const VoxelBrush& v = brushes[i];
+        b[i] = rto_brush{ { v.centre.x, v.centre.y, v.centre.z }, { v.extent.x, v.extent.y, v.extent.z }, v.shape, v.op };
+    }
+    const bool fromHost = !m_flatNodes.empty();
+    const float gridMin[3] = { m_grid.minX, m_grid.minY, m_grid.minZ };
+    int64_t changed = 0;
+    if (!forEachContext([&](rto_context* c) {
+            if (fromHost) {
+                int64_t numTris = 0;
+                const bool hadTris = api().download_leaf_triangles(c, nullptr, 0, nullptr, &numTris) == RTO_OK;
+                int rc = api().build_octree(c, reinterpret_cast<const uint8_t*>(m_grid.data.data()), m_grid.dimX, m_grid.dimY, m_grid.dimZ,
+                                            gridMin, m_grid.voxelSize);
+                if (rc == RTO_OK && hadTris) rc = api().build_leaf_triangles(c, nullptr, 0, 0, 0);
+                if (rc != RTO_OK) return rc;
+            }
+            return api().edit_voxels(c, b.data(), (int)b.size(), c == m_ctx ? &changed : nullptr);
+        }, "voxel edit"))
+        return;
+    m_lastEditChanged = changed;
+    if (fromHost) { m_flatNodes.clear(); m_octreeRoot = nullptr; }   // the caller's pointer tree no longer describes the scene
+    if (changed > 0 || fromHost) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+    }
+    if (changed > 0) m_gridStale = true;
+}
+
+const VoxelGrid& RayTracerBVH::grid() const {
+    if (m_gridStale && m_ctx) {
+        int dims[3] = { 0, 0, 0 };
+        static_assert(sizeof(VoxelState) == 1, "VoxelGrid.data is one byte per voxel");
+        if (api().download_voxels(m_ctx, reinterpret_cast<uint8_t*>(m_grid.data.data()), (int64_t)m_grid.data.size(), dims) == RTO_OK)
+            m_gridStale = false;
+        else {
+            m_lastError = api().last_error(m_ctx);
+            std::cerr << "[RayTracerBVH] grid download failed: " << m_lastError << std::endl;
+        }
+    }
+    return m_grid;
 }

@@ -70,6 +70,17 @@ struct TriangleHit {
     bool hit() const { return tri >= 0; }
 };
 
+// A voxel edit (rto_brush, include/rto_hip.h): a sphere (radius extent.x) or an axis-aligned box
+// (half-sizes extent) in world units that carves voxels (-> EMPTY) or fills them (-> FILLED).
+struct VoxelBrush {
+    enum Shape { Sphere = RTO_BRUSH_SPHERE, Box = RTO_BRUSH_BOX };
+    enum Op { Carve = RTO_EDIT_CARVE, Fill = RTO_EDIT_FILL };
+    rto_host::vec3 centre;
+    rto_host::vec3 extent;
+    int shape;
+    int op;
+};
+
 class RayTracerBVH {
 public:
     enum QueryMode { First = RTO_QUERY_FIRST, Closest = RTO_QUERY_CLOSEST, Any = RTO_QUERY_ANY };
@@ -115,6 +126,14 @@ public:
     // The triangle renderSceneTriangles shows at pixel (px, py) (row 0 = top): the render's own ray and its FIRST rule
     // (rto_query_triangle_pixels_host), with the surface point, barycentrics and normal.  false (and out a miss) when nothing is hit.
     bool pickSurface(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, TriangleHit& out);
+    // Scene edits: the brushes, in order, on the grid every GPU holds; the octree (and the leaf triangles, if resident) is then
+    // rebuilt there, as setOctreeFromGrid would build it from the edited grid.  After setOctree() the first edit builds the octree
+    // from the grid given to it.  flatNodes() is empty afterwards and buildLeafTriangles() uses the resident grid.  The reference's
+    // click-to-carve: pickSurface (or pick), then editVoxels({{hit.point, vec3(r), VoxelBrush::Sphere, VoxelBrush::Carve}}).
+    void editVoxels(const std::vector<VoxelBrush>& brushes);
+    int64_t lastEditChanged() const { return m_lastEditChanged; }   // voxels the last editVoxels changed; -1: it failed
+    // The current grid: what setOctree / setOctreeFromGrid got, with every edit applied (downloaded when first asked after an edit).
+    const VoxelGrid& grid() const;
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid
@@ -141,7 +160,9 @@ private:
     bool render(const Camera& camera, int width, int height, float aspect, float fovDeg);
 
     OctreeNode* m_octreeRoot;
-    VoxelGrid m_grid;
+    mutable VoxelGrid m_grid;
+    mutable bool m_gridStale = false;         // the GPUs hold an edited grid that m_grid does not show yet (grid())
+    int64_t m_lastEditChanged = 0;
     std::vector<GPUNodes> m_flatNodes;
     int m_numNodes;
 

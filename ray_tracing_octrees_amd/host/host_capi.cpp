@@ -216,6 +216,22 @@ int rtoh_rt_pick_surface(RayTracerBVH* rt, const Camera* cam, int px, int py, in
     if (point) { point[0] = r.point.x; point[1] = r.point.y; point[2] = r.point.z; }
     return hit ? 1 : 0;
 }
+// brushes: n x (cx, cy, cz, ex, ey, ez) floats, shapes / ops: n ints each; the number of voxels changed (-1: the edit failed)
+int64_t rtoh_rt_edit_voxels(RayTracerBVH* rt, const float* brushes, const int* shapes, const int* ops, int n) {
+    std::vector<VoxelBrush> b((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const float* f = brushes + 6 * i;
+        b[(size_t)i] = VoxelBrush{ rto_host::vec3(f[0], f[1], f[2]), rto_host::vec3(f[3], f[4], f[5]), shapes[i], ops[i] };
+    }
+    rt->editVoxels(b);
+    return rt->lastEditChanged();
+}
+// the class's current grid (RayTracerBVH::grid()), as rtoh_grid_data: dims only when out is NULL
+void rtoh_rt_grid(const RayTracerBVH* rt, int dims[3], uint8_t* out) {
+    const VoxelGrid& g = rt->grid();
+    dims[0] = g.dimX; dims[1] = g.dimY; dims[2] = g.dimZ;
+    if (out) for (size_t i = 0; i < g.data.size(); i++) out[i] = (uint8_t)g.data[i];
+}
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }
 const char* rtoh_rt_last_error(const RayTracerBVH* rt) { return rt->lastError().c_str(); }
