@@ -513,6 +513,53 @@ int  rto_last_edit_ms(const rto_context* ctx, float ms[3]);
 /* Pure host function, no device: the quantised brush of the rule above for this grid, or RTO_E_INVALID. */
 int  rto_brush_quantize(const rto_brush* brush, const float grid_min[3], float voxel_size, int64_t cq[3], int64_t eq[3]);
 
+/* ---- lit render -----------------------------------------------------------
+ * The box render's frame with a shadow ray and ambient occlusion per hit pixel, computed on the device in one stream (DESIGN.md
+ * section 12).  Rule:
+ *   primary hit   the FIRST box query on the frame's pixel ray (rto_render_device's rule, window (0, 1e30)): leaf, tHit =
+ *                 max(0, tNear), entry face.  Like the queries, the lit render ignores rto_update_frustum.
+ *   ndotl         shade_term's Lambert term against lightNeg = -normalize(light_dir), normalised as the renders do.
+ *   origin        a = face >> 1, sigma = +1 if (face & 1) else -1 (sigma e_a is the entry face's outward normal); p = o + d tHit;
+ *                 eps = voxelSize * 1e-3f + 2^-18 * max(|p.x|, |p.y|, |p.z|); so = p except so[a] = the leaf's float plane on axis
+ *                 a (max plane if sigma > 0, min plane otherwise) + sigma eps.
+ *   shadow        (shadow != 0, face >= 0, ndotl > 0) one ray from so towards lightNeg, window (0, 1e30), the ANY rule: S = 0 when it
+ *                 hits, else 1.
+ *   AO            (K = ao_samples in 1..64, face >= 0) K rays from so, window (0, ao_radius], the ANY rule.  T = rto_ao_directions
+ *                 (64 unit vectors, z > 0, cosine-weighted Hammersley); h = mix32(x * 0x8da6b343 ^ y * 0xd8163841 ^ seed * 0xcb1ab31f)
+ *                 in uint32, mix32(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16.  Sample s uses
+ *                 t = T[(h + (64 s) / K) & 63]; the world direction has component a = sigma t.z, component (a + 1) % 3 = t.x negated
+ *                 when bit 6 of h is set, component (a + 2) % 3 = t.y negated when bit 7 is set.  occ = rays that hit;
+ *                 A = (float)(K - occ) / (float)K.
+ *   otherwise     S = A = 1 (K = 0, no shadow ray cast, or face = -1: the camera inside a solid leaf).
+ *   colour        d = S ? ndotl : 0, amb = 0.1f * A, RGBA = (1.0f d + amb, 0.8f d + amb, 0.6f d + amb, 1); a miss is (0, 0, 0, 1).
+ *                 shadow = 0, K = 0 and light_dir = (-1, -1, -1) give rto_render_device's frame (culling off) bit for bit.
+ *   vis           (optional, int32 per pixel) -1 for a miss, else occ + 256 * (shadow ray cast and blocked).
+ * Whole frames only.  RTO_E_INVALID: a NULL frame, lighting or output, a misaligned device buffer (d_rgba 16 bytes, d_vis 4), K
+ * outside 0..64, K > 0 with an ao_radius that is not finite and positive, a light_dir that is zero, not finite or not normalisable
+ * in float, reserved != 0, a width or height below 1, or a frame too large for 32-bit ray indices: width * height * (K + 1) + 128
+ * and 64 * (8x8 tiles of the frame) + 256 must both be below 2^32; RTO_E_NO_OCTREE: nothing uploaded; RTO_E_UNSUPPORTED: an array
+ * of more than one node without a descriptor tree (a non-canonical upload).  A tree that is one leaf is rendered (its box is the
+ * walk).  rto_set_kernel does not apply.  The device form is asynchronous on hip_stream and keeps its work buffers
+ * on the context (a frame larger than any before allocates them, and then must not be stream-captured; one set per context, so
+ * lit frames on different streams of one context must not run at the same time). */
+#define RTO_AO_MAX_SAMPLES 64
+typedef struct rto_lighting {       /* 32 bytes */
+    float    light_dir[3];          /* direction the light travels; (-1, -1, -1) is the renders' light */
+    int32_t  shadow;                /* != 0: cast the shadow ray */
+    int32_t  ao_samples;            /* K, 0..RTO_AO_MAX_SAMPLES */
+    float    ao_radius;             /* AO window's t_max, world units (the directions are unit vectors) */
+    uint32_t seed;
+    int32_t  reserved;              /* 0 */
+} rto_lighting;
+
+int  rto_render_lit_device(rto_context* ctx, const rto_frame* frame, const rto_lighting* lighting, void* d_rgba,
+                           int32_t* d_vis /* may be NULL */, void* hip_stream);
+int  rto_render_lit_host(rto_context* ctx, const rto_frame* frame, const rto_lighting* lighting, float* host_rgba,
+                         int32_t* host_vis /* may be NULL */);
+/* The 64 AO directions T (x, y, z per entry): entry i is u = (i + 0.5) / 64, phi = 2 pi (bitrev6(i) + 0.5) / 64,
+ * (sqrt(u) cos phi, sqrt(u) sin phi, sqrt(1 - u)) computed in double and rounded once to float.  Pure host function. */
+int  rto_ao_directions(float out[192]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

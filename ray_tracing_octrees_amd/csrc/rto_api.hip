@@ -150,6 +150,12 @@ struct rto_context {
     int buildPath = 0;         // 0 = automatic (Morton-order build where it applies), 1 = level-by-level build (rto_debug_set_build_path)
     float buildUploadMs = -1.f;
     float editMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_voxels: brushes, octree rebuild, triangle rebuild (-1: not run)
+
+    // lit render (rto_lit.inc): compacted hit records and their verdict counters for frames of up to litCap pixels, the hit count
+    int4* d_litRec = nullptr;
+    unsigned* d_litAcc = nullptr;
+    unsigned* d_litCount = nullptr;
+    size_t litCap = 0;
 };
 
 static thread_local std::string g_createError;
@@ -291,6 +297,9 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_visibleCount);
     (void)hipFree(c->d_start);
     (void)hipFree(c->d_sortViolations);
+    (void)hipFree(c->d_litRec);
+    (void)hipFree(c->d_litAcc);
+    (void)hipFree(c->d_litCount);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ringStop) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2681,3 +2690,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_query.inc"
 #include "rto_tri_query.inc"
 #include "rto_edit.inc"
+#include "rto_lit.inc"

@@ -85,23 +85,33 @@ __device__ __forceinline__ void store_hit(const QuerySrc& Q, int64_t i, bool hit
 //   CLOSEST the ray's own octant first (k_closest_near_first's order), a node cut when tNear > min(best, t_hi) -- a child's tNear is
 //           never below its parent's --, equal tHit resolved by the LIFO pop order (pops_before).
 //   ANY     the same order, ends at the first accepted leaf.
-template <int QMODE, bool PIXELS>
-__global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc Q, const uint2* __restrict__ desc,
-                                                       const int* __restrict__ descFirstChild) {
-    extern __shared__ uint2 lds_stack[];   // [wave][level][lane] entries, then [wave][level][lane] descriptor indices
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
-    const int levels = P.depth;
-    uint2* stk = lds_stack + (size_t)wave * levels * kWave + lane;
-    unsigned* stkNode = reinterpret_cast<unsigned*>(lds_stack + (size_t)waves * levels * kWave) + (size_t)wave * levels * kWave + lane;
-    const int64_t i = Q.base + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const Geo G = geo_of(P);
-    const float kEps = __uint_as_float(1u), kBelow1e30 = __uint_as_float(0x7149f2c9u);
+// desc_walk is that walk for one lane; k_query_desc and the lit render's kernels (rto_lit.inc) call it.
 
-    Ray r;
-    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
-    float tlo = 0.0f, thi = 0.0f;
+// The two LDS stacks of the calling lane: `levels` entries of each per lane, [wave][level][lane] (dynamic LDS of
+// kBlock / kWave * levels * kWave * 12 bytes, <= 64,512 B at depth 20).
+__device__ __forceinline__ void desc_stacks(uint2* lds, int levels, uint2*& stk, unsigned*& stkNode) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
+    stk = lds + (size_t)wave * levels * kWave + lane;
+    stkNode = reinterpret_cast<unsigned*>(lds + (size_t)waves * levels * kWave) + (size_t)wave * levels * kWave + lane;
+}
+
+// What a descriptor walk found: the accepted leaf's position and size, tHit, its child slot j in the parent whose descriptor
+// index is `node` (the leaf's array index is descFirstChild[node] + j).
+struct DescHit {
+    bool hit;
+    float t;
+    int x, y, z, size, j;
+    unsigned node;
+};
+
+// The walk of one ray (r, window [tlo, thi]) under rule QMODE.  Called by every lane of the wave together (the risky-ray vote is a
+// wave ballot); `valid` false: the lane takes no part and gets a miss.
+template <int QMODE>
+__device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G, const Ray r, float tlo, float thi, bool valid,
+                                             const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode) {
+    const float kEps = __uint_as_float(1u), kBelow1e30 = __uint_as_float(0x7149f2c9u);
     bool active = false;
-    if (i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi)) {
+    if (valid) {
         float tNear, tFar, a0, a1, a2, a3, a4, a5;
         active = slab_exact(G, r, 0, 0, 0, P.rootSize, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
         if (QMODE != kQueryFirst) active = active && !(tNear > thi);
@@ -185,10 +195,30 @@ __global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc 
             break;
         }
     }
+    DescHit out;
+    out.hit = hit; out.t = best; out.x = bx; out.y = by; out.z = bz; out.size = bs; out.j = bj; out.node = bnode;
+    return out;
+}
+
+template <int QMODE, bool PIXELS>
+__global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc Q, const uint2* __restrict__ desc,
+                                                       const int* __restrict__ descFirstChild) {
+    extern __shared__ uint2 lds_stack[];   // [wave][level][lane] entries, then [wave][level][lane] descriptor indices
+    uint2* stk;
+    unsigned* stkNode;
+    desc_stacks(lds_stack, P.depth, stk, stkNode);
+    const int64_t i = Q.base + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const Geo G = geo_of(P);
+
+    Ray r;
+    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
+    float tlo = 0.0f, thi = 0.0f;
+    const bool valid = i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi);
+    const DescHit w = desc_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode);
     if (i < Q.n) {
-        const int node = hit ? descFirstChild[bnode] + bj : -1;
-        const int face = hit ? query_face(G, r, bx, by, bz, bs, best) : -1;
-        store_hit(Q, i, hit, best, node, face, bs, bx, by, bz);
+        const int node = w.hit ? descFirstChild[w.node] + w.j : -1;
+        const int face = w.hit ? query_face(G, r, w.x, w.y, w.z, w.size, w.t) : -1;
+        store_hit(Q, i, w.hit, w.t, node, face, w.size, w.x, w.y, w.z);
     }
 }
 

@@ -38,6 +38,7 @@ SYMBOLS = (
     "rto_query_rays_device", "rto_query_rays_host", "rto_query_pixels_device", "rto_query_pixels_host",
     "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
     "rto_edit_voxels", "rto_download_voxels", "rto_last_edit_ms", "rto_brush_quantize",
+    "rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions",
 )
 SPLIT_MAX_FRAMES = 32
 QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
@@ -55,6 +56,7 @@ BRUSH_SPHERE, BRUSH_BOX = 0, 1
 EDIT_CARVE, EDIT_FILL = 0, 1
 EDIT_MAX_BRUSHES = 65536
 BRUSH_DTYPE = np.dtype([("centre", "<f4", (3,)), ("extent", "<f4", (3,)), ("shape", "<i4"), ("op", "<i4")])
+AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
 
@@ -86,6 +88,34 @@ class TriHit(C.Structure):
 
 class Brush(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("extent", C.c_float * 3), ("shape", C.c_int32), ("op", C.c_int32)]
+
+
+# struct rto_lighting, 32 bytes: the lit render (rto_render_lit_*)
+class Lighting(C.Structure):
+    _fields_ = [("light_dir", C.c_float * 3), ("shadow", C.c_int32), ("ao_samples", C.c_int32), ("ao_radius", C.c_float),
+                ("seed", C.c_uint32), ("reserved", C.c_int32)]
+
+
+def make_lighting(light_dir=(-1.0, -1.0, -1.0), shadow=True, ao_samples=0, ao_radius=1.0, seed=0) -> Lighting:
+    """An rto_lighting: light_dir is the direction the light travels ((-1, -1, -1) is the renders' light)."""
+    L = Lighting()
+    for a in range(3):
+        L.light_dir[a] = _f(light_dir[a])
+    L.shadow = 1 if shadow else 0
+    L.ao_samples = int(ao_samples)
+    L.ao_radius = _f(ao_radius)
+    L.seed = int(seed) & 0xFFFFFFFF
+    L.reserved = 0
+    return L
+
+
+def ao_directions() -> np.ndarray:
+    """rto_ao_directions: the lit render's 64 AO directions, (64, 3) float32 (pure host function)."""
+    out = np.zeros((AO_MAX_SAMPLES, 3), np.float32)
+    rc = load().rto_ao_directions(out.ctypes.data)
+    if rc != RTO_OK:
+        raise RtoError(rc, "rto_ao_directions failed")
+    return out
 
 
 class Hit(C.Structure):
@@ -280,6 +310,9 @@ def load():
     L.rto_download_voxels.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
     L.rto_last_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_brush_quantize.argtypes = [vp, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rto_render_lit_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp, vp]
+    L.rto_render_lit_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp]
+    L.rto_ao_directions.argtypes = [vp]
     _lib = L
     return L
 
@@ -579,6 +612,26 @@ class Context:
     def query_pixels_device(self, mode: int, frame: Frame, d_xy: int, n: int, d_hits: int, stream: int = 0):
         self._check(self._L.rto_query_pixels_device(self._h, int(mode), C.byref(frame), C.c_void_p(d_xy) if d_xy else None, int(n),
                                                     C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    # -- lit render ----------------------------------------------------------
+    def render_lit_host(self, frame: Frame, lighting: Lighting | None = None, vis: bool = False, **kw):
+        """The box render's frame with a shadow ray and ambient occlusion (rto_render_lit_host).  lighting: a Lighting, or
+        make_lighting's keywords.  Returns the (H, W, 4) float32 frame, or (frame, (H, W) int32 visibility) with vis=True."""
+        L = lighting if lighting is not None else make_lighting(**kw)
+        out = np.empty((frame.height, frame.width, 4), np.float32)
+        v = np.empty((frame.height, frame.width), np.int32) if vis else None
+        self._check(self._L.rto_render_lit_host(self._h, C.byref(frame), C.byref(L), out.ctypes.data,
+                                                v.ctypes.data if vis else None))
+        return (out, v) if vis else out
+
+    def render_lit_device(self, frame: Frame, lighting: Lighting, d_rgba: int, d_vis: int = 0, stream: int = 0):
+        """Asynchronous: the lit frame into d_rgba (W*H*16 bytes) and, if d_vis, the visibility into d_vis (W*H int32)."""
+        self._check(self._L.rto_render_lit_device(self._h, C.byref(frame), C.byref(lighting), C.c_void_p(d_rgba) if d_rgba else None,
+                                                  C.c_void_p(d_vis) if d_vis else None, C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def ao_directions() -> np.ndarray:
+        return ao_directions()
 
     # -- triangle queries (the resident leaf triangles) --------------------
     def query_triangles(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:

@@ -118,6 +118,9 @@ def load():
     L.rtoh_rt_last_error.restype = C.c_char_p
     L.rtoh_rt_intersect_rays.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_intersect_rays.restype = None
+    L.rtoh_rt_render_scene_lit.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                           C.c_float, C.c_uint32]
+    L.rtoh_rt_render_scene_lit.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
     L.rtoh_rt_intersect_triangles.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp, _vp]
@@ -368,6 +371,14 @@ class RayTracerBVH:
 
     def renderSceneTriangles(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, shadow: bool = True):
         load().rtoh_rt_render_scene_triangles(self._h, camera._h, width, height, _f(aspect), _f(fovDeg), 1 if shadow else 0)
+
+    def renderSceneLit(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, lightDir=(-1.0, -1.0, -1.0),
+                       shadow: bool = True, aoSamples: int = 0, aoRadius: float = 1.0, seed: int = 0):
+        """Addition: RayTracerBVH::renderSceneLit -- renderSceneCompute's frame with a shadow ray and aoSamples ambient-occlusion
+        rays per hit pixel; read it with framebuffer()."""
+        ld = (C.c_float * 3)(*[_f(x) for x in lightDir])
+        load().rtoh_rt_render_scene_lit(self._h, camera._h, width, height, _f(aspect), _f(fovDeg), ld, 1 if shadow else 0,
+                                        int(aoSamples), _f(aoRadius), int(seed) & 0xFFFFFFFF)
 
     def framebuffer(self) -> np.ndarray | None:
         w, h = C.c_int(), C.c_int()

@@ -43,6 +43,7 @@ struct HipApi {
     decltype(&rto_download_voxels) download_voxels = nullptr;
     decltype(&rto_download_leaf_triangles) download_leaf_triangles = nullptr;
     decltype(&rto_download_nodes) download_nodes = nullptr;
+    decltype(&rto_render_lit_host) render_lit_host = nullptr;
     std::string error;
 
     bool load() {
@@ -96,6 +97,7 @@ struct HipApi {
         download_voxels = reinterpret_cast<decltype(download_voxels)>(sym("rto_download_voxels"));
         download_leaf_triangles = reinterpret_cast<decltype(download_leaf_triangles)>(sym("rto_download_leaf_triangles"));
         download_nodes = reinterpret_cast<decltype(download_nodes)>(sym("rto_download_nodes"));
+        render_lit_host = reinterpret_cast<decltype(render_lit_host)>(sym("rto_render_lit_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -322,6 +324,36 @@ void RayTracerBVH::renderSceneTriangles(const Camera& camera, int width, int hei
         return;
     }
     m_frameW = width; m_frameH = height; m_frameStale = true;
+}
+
+void RayTracerBVH::renderSceneLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting) {
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return;
+    }
+    if (m_numNodes <= 0 || width <= 0 || height <= 0) return;
+    rto_frame f;
+    const auto view = camera.getView();
+    std::memcpy(f.view, &view[0][0], sizeof f.view);
+    const auto pos = camera.getPos();
+    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
+    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    rto_lighting L;
+    L.light_dir[0] = lighting.lightDir.x; L.light_dir[1] = lighting.lightDir.y; L.light_dir[2] = lighting.lightDir.z;
+    L.shadow = lighting.shadow ? 1 : 0;
+    L.ao_samples = lighting.aoSamples;
+    L.ao_radius = lighting.aoRadius;
+    L.seed = lighting.seed;
+    L.reserved = 0;
+    m_frameW = m_frameH = 0; m_frameStale = false;
+    m_frame.resize(static_cast<size_t>(width) * height * 4);
+    if (api().render_lit_host(m_ctx, &f, &L, m_frame.data(), nullptr) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] lit render failed: " << m_lastError << std::endl;
+        m_frame.clear();
+        return;
+    }
+    m_frameW = width; m_frameH = height;
 }
 
 static RayHit to_ray_hit(const rto_hit& h) {

@@ -81,6 +81,16 @@ struct VoxelBrush {
     int op;
 };
 
+// The lit render's terms (rto_lighting, include/rto_hip.h): the direction the light travels, a shadow ray
+// per lit pixel, aoSamples (0..64) ambient-occlusion rays of length aoRadius (world units) per hit pixel, and the hash seed.
+struct Lighting {
+    rto_host::vec3 lightDir = rto_host::vec3(-1.0f, -1.0f, -1.0f);
+    bool shadow = true;
+    int aoSamples = 0;
+    float aoRadius = 1.0f;
+    uint32_t seed = 0;
+};
+
 class RayTracerBVH {
 public:
     enum QueryMode { First = RTO_QUERY_FIRST, Closest = RTO_QUERY_CLOSEST, Any = RTO_QUERY_ANY };
@@ -114,6 +124,9 @@ public:
     // of d, hits accepted for tMin <= t <= tMax.  The consumer the reference's struct Ray never had.
     void intersectRays(const std::vector<Ray>& rays, std::vector<RayHit>& hits, int mode = Closest, float tMin = 0.0f,
                        float tMax = 1e30f);
+    // renderSceneCompute's frame with a shadow ray and ambient occlusion per hit pixel (rto_render_lit_host): same framebuffer().
+    // The whole octree casts shadows, whatever the frustum culling.  With setDevices(n > 1) it renders on the first GPU alone.
+    void renderSceneLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting);
     // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.

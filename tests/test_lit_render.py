@@ -1,0 +1,538 @@
+"""The lit render (rto_render_lit_*, Context.render_lit_*, RayTracerBVH::renderSceneLit): the box render's frame with a shadow ray
+and ambient occlusion per hit pixel.  CPU: the ABI's layout, the AO table, the float32 statement (tests/lit_ref.py) against the
+oracle's frames, an analytic shadow and float64; the built assembly of the k_lit_* kernels.  GPU: frames and visibility against
+that statement, bit for bit."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import deep_scenes as ds
+import lit_ref as lr
+import query_ref as q
+import ref64
+from conftest import SPHERE_CAM, make_camera
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FOV = 45.0
+VGPR_BUDGET = 80
+# (shadow, K): K = 3, 5 and 48 do not divide 64, so a pixel's AO rays straddle waves and are summed in two pieces
+SETTINGS = ((0, 0), (1, 0), (0, 1), (1, 8), (1, 64), (1, 3), (0, 5), (1, 48))
+LIGHTS = ((-1.0, -1.0, -1.0), (0.3, -0.8, 0.45), (0.0, -1.0, 0.0))   # the renders' light, an oblique one, an axis-aligned one
+
+
+def _hip():
+    from ray_tracing_octrees_amd import hip
+    return hip
+
+
+def _table():
+    return _hip().ao_directions()
+
+
+def _rays(orc, view, pos, W, H):
+    return orc.generate_rays(view, pos, W / H, FOV, W, H).reshape(-1, 3)
+
+
+def _camera(orc, s, name):
+    """(view, pos) of an orbit camera aimed at the grid's centre: "outside", "axis" (theta = phi = 0: the view axes are the world
+    axes) or "inside" (the outside camera's view from inside the largest solid leaf)."""
+    centre = s.min.astype(np.float64) + np.array(s.grid.dims, np.float64) * float(s.voxel) / 2
+    R = float(np.float32(1.6 * float(np.array(s.grid.dims).max()) * float(s.voxel)))
+    th, ph = (0.0, 0.0) if name == "axis" else (0.6, 0.45)
+    cam = orc.Camera(th, ph, R)
+    cam.set_target(*[float(v) for v in centre.astype(np.float32)])
+    view, pos = cam.get_view(), cam.get_pos()
+    if name == "inside":
+        n = s.nodes
+        solid = np.nonzero(((n["isLeaf"] == 1) | (n["isUniform"] == 1)) & (n["isSolid"] == 1))[0]
+        big = solid[np.argmax(n["size"][solid])]
+        corner = np.array([n["x"][big], n["y"][big], n["z"][big]], np.float32)
+        pos = (s.min + (corner + np.float32(0.37) * np.float32(n["size"][big])) * s.voxel).astype(np.float32)
+    return view, pos
+
+
+# ================================================================ CPU
+def test_lighting_struct_matches_the_header():
+    """ctypes rto_lighting is the header's: 32 bytes, the fields in its order and offsets; the new symbols and constants."""
+    hip = _hip()
+    L = hip.Lighting
+    assert C.sizeof(L) == 32
+    offs = {name: getattr(L, name).offset for name, _ in L._fields_}
+    assert offs == {"light_dir": 0, "shadow": 12, "ao_samples": 16, "ao_radius": 20, "seed": 24, "reserved": 28}
+    hdr = open(os.path.join(ROOT, "include", "rto_hip.h")).read()
+    body = re.search(r"typedef struct rto_lighting \{(.*?)\} rto_lighting;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"(float|int32_t|uint32_t)\s+(\w+)(\[3\])?;", body)
+    assert [f[1] for f in fields] == ["light_dir", "shadow", "ao_samples", "ao_radius", "seed", "reserved"]
+    assert [(f[0], f[2]) for f in fields] == [("float", "[3]"), ("int32_t", ""), ("int32_t", ""), ("float", ""), ("uint32_t", ""), ("int32_t", "")]
+    assert re.search(r"#define RTO_AO_MAX_SAMPLES\s+64\b", hdr) and hip.AO_MAX_SAMPLES == 64
+    for sym in ("rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions"):
+        assert sym in hip.SYMBOLS
+
+
+def test_ao_table_is_the_formula():
+    """rto_ao_directions: 64 unit vectors (within 2^-22) in the +z hemisphere, each component within 1 ulp of the float64 formula
+    (cosine-weighted Hammersley with bit-reversed azimuths) and equal to its correctly rounded value."""
+    t = _table()
+    assert t.shape == (64, 3) and t.dtype == np.float32
+    assert (t[:, 2] > 0).all()
+    assert np.abs(np.linalg.norm(t.astype(np.float64), axis=1) - 1.0).max() <= 2.0 ** -22
+    f64 = lr.ao_table64()
+    ulp = np.spacing(np.abs(f64).astype(np.float32)).astype(np.float64)
+    assert (np.abs(t.astype(np.float64) - f64) <= ulp).all()
+    assert (t == f64.astype(np.float32)).all()
+    # the hemisphere is covered: every octant of azimuth holds 8 entries
+    oct_ = ((np.arctan2(t[:, 1], t[:, 0]) + np.pi) // (np.pi / 4)).astype(int) % 8
+    assert (np.bincount(oct_, minlength=8) == 8).all()
+
+
+@pytest.mark.parametrize("scene,cam", [("sphere64", SPHERE_CAM), ("sphere64", (0.3, 0.2, 0.1)), ("odd", "outside"),
+                                       ("calgary", "calgary_oblique")])
+def test_statement_without_terms_is_the_oracle_frame(orc, scenes, camera, scene, cam):
+    """lit_ref with shadow off and K = 0 (default light) is orc.render's frame bit for bit; the visibility is -1 / 0."""
+    s = scenes(scene)
+    if isinstance(cam, tuple):
+        view, pos = make_camera(orc, *cam)
+    elif cam.startswith("calgary"):
+        view, pos = camera(cam)
+    else:
+        view, pos = _camera(orc, s, cam)
+    W, H = 80, 60
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    img, vis = lr.lit_frame(T, s.voxel, pos, _rays(orc, view, pos, W, H), W, H, _table(), shadow=False, K=0)
+    want, _ = orc.render(s.nodes, s.min, s.voxel, view, pos, W / H, FOV, W, H)
+    assert img.tobytes() == want.reshape(H, W, 4).tobytes()
+    assert ((vis >= 0) == (want.reshape(H, W, 4)[..., 0] > 0.05)).all() and set(np.unique(vis)) <= {-1, 0}
+    assert (vis == 0).any()
+
+
+def _floor_pillar():
+    """A 32^3 grid (voxel 1, origin 0): a floor slab y in [0, 2) and a pillar x, z in [14, 18), y in [2, 20)."""
+    from oracle import orc
+    data = np.zeros((32, 32, 32), np.uint8)            # (z, y, x)
+    data[:, 0:2, :] = 1
+    data[14:18, 2:20, 14:18] = 1
+    g = orc.Grid((32, 32, 32), np.zeros(3, np.float32), np.float32(1.0), data)
+    return g, orc.build_flat_octree(g)
+
+
+def test_shadow_and_ao_of_a_pillar_on_a_floor():
+    """Rays straight down onto the floor, light from above at an angle: the shadowed floor points are exactly those the pillar's
+    analytic shadow covers (away from its edge by half a voxel); AO counts are 0 on the open floor and > 0 beside the pillar."""
+    g, nodes = _floor_pillar()
+    T = q.Tree32(nodes, g.min, g.voxel_size)
+    light = (0.5, -1.0, 0.3)                            # travels down, towards +x and +z: shadows fall towards -x, -z
+    xs, zs = np.meshgrid(np.arange(0.25, 32, 0.5), np.arange(0.25, 32, 0.5))
+    px, pz = xs.ravel(), zs.ravel()
+    keep = ~((px > 13.5) & (px < 18.5) & (pz > 13.5) & (pz < 18.5))          # the pillar's top, and its edge, is not floor
+    px, pz = px[keep], pz[keep]
+    o = np.stack([px, np.full_like(px, 30.0), pz], 1).astype(np.float32)
+    d = np.broadcast_to(np.float32([0, -1, 0]), o.shape).copy()
+    ix, iz = np.floor(px).astype(int), np.floor(pz).astype(int)
+    rgba, vis = lr.lit32(T, g.voxel_size, o, d, ix, iz, _table(), light_dir=light, shadow=True, K=16, radius=4.0, seed=3)
+    assert (vis >= 0).all()
+    # analytic: from (px, 2, pz) along (-0.5, 1, -0.3) u, u in [0, 18], the pillar is x, z in [14, 18]
+    def overlap(margin):
+        lo = np.maximum.reduce([np.zeros_like(px), 2 * (px - 18) - margin, (pz - 18) / 0.3 - margin])
+        hi = np.minimum.reduce([np.full_like(px, 18.0), 2 * (px - 14) + margin, (pz - 14) / 0.3 + margin])
+        return hi - lo
+    inside, outside = overlap(-0.5) > 0, overlap(0.5) < 0
+    shadowed = vis >= 256
+    assert inside.sum() > 50 and outside.sum() > 1000
+    assert shadowed[inside].all() and not shadowed[outside].any()
+    lit = ~shadowed
+    assert (rgba[shadowed, 0] < rgba[lit, 0].min()).all()         # a shadowed floor point is darker than every lit one
+    # AO: K = 64 takes the whole table (smaller K take one stride class of it), so every floor point next to
+    # the pillar sees it, and no point more than 4 voxels from it does
+    _, vis64 = lr.lit32(T, g.voxel_size, o, d, ix, iz, _table(), light_dir=light, shadow=False, K=64, radius=4.0, seed=3)
+    occ = vis64 & 255
+    dist = np.maximum(np.maximum(14 - px, px - 18), np.maximum(14 - pz, pz - 18))          # Chebyshev distance to the pillar
+    far, corner = dist > 4.01, dist < 1.0
+    assert far.sum() > 100 and corner.sum() > 10
+    assert (occ[far] == 0).all() and (occ[corner] > 0).all()
+    assert (vis64 < 256).all() and ((vis & 255)[far] == 0).all()
+
+
+@pytest.mark.parametrize("scene", ["sphere64", "odd"])
+def test_statement_against_float64_on_robust_rays(orc, scenes, scene):
+    """lit_ref's decisions against float64: primary hits (Octree64's FIRST) and every shadow / AO verdict (Octree64Q's ANY on the
+    same secondary rays) agree where float64 calls them robust; the robust share is large."""
+    s = scenes(scene)
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    Q = q.Octree64Q(s.nodes, s.min, s.voxel)
+    view, pos = _camera(orc, s, "outside")
+    W, H = 48, 36
+    rd = _rays(orc, view, pos, W, H)
+    rays = {}
+    yy, xx = np.mgrid[0:H, 0:W]
+    r32 = q.query32(T, pos, rd)[q.FIRST]
+    lr.lit32(T, s.voxel, pos, rd, xx.ravel(), yy.ravel(), _table(), light_dir=(0.3, -0.8, 0.45), shadow=True, K=8,
+             radius=4 * float(s.voxel), seed=5, rays_out=rays)
+    first, _ = ref64.render_boxes64(ref64.Octree64(s.nodes, s.min, s.voxel), pos, rd)
+    rob = first["robust"]
+    assert rob.mean() > 0.9 and (r32["node"] == first["leaf"])[rob].all()
+    for kind, tmax in (("shadow", 1e30), ("ao", float(np.float32(4 * float(s.voxel))))):
+        o, d, got = rays[kind]
+        w = Q.trace_windows(o.astype(np.float64), d.astype(np.float64), 0.0, tmax)[q.ANY]
+        assert w["robust"].mean() > 0.8, (kind, w["robust"].mean())
+        assert (got == w["hit"])[w["robust"]].all(), kind
+    assert rays["ao"][2].any() and (~rays["ao"][2]).any()
+
+
+def test_lit_kernels_keep_their_budgets():
+    """The built assembly (the product's flags): the two k_lit_* kernels without scratch instructions, spills or v_mfma, within
+    80 VGPRs; the query kernels are still 12."""
+    import shutil
+    import subprocess
+    import tempfile
+    import test_isa_contract as isa
+    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+    if not hipcc:
+        pytest.skip("no hipcc in this environment")
+    from ray_tracing_octrees_amd import _build
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "rto.s")
+        flags = [f for f in _build.HIP_FLAGS if f not in ("-fPIC", "-shared")]
+        subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(isa.CSRC, "rto_api.hip"), "-o", out],
+                       check=True, stderr=subprocess.DEVNULL)
+        asm = open(out).read()
+    meta = isa.kernel_meta(asm)
+    names = [k for k in meta if "k_lit_" in k]
+    assert len(names) == 2, names
+    assert len([k for k in meta if "k_query_" in k]) == 12
+    for k in names:
+        m = meta[k]
+        assert m["scratch"] == 0 and m["vgpr_spill"] == 0 and m["sgpr_spill"] == 0, (k, m)
+        assert m["vgpr"] <= VGPR_BUDGET, (k, m)
+        ins = isa.body(asm, k[len("_ZN3rto"):])
+        assert not any(t.startswith(("scratch_", "buffer_load", "buffer_store")) or "v_mfma" in t for t in ins), k
+
+
+# ================================================================ GPU
+gpu = pytest.mark.gpu
+
+
+def _rto():
+    import ray_tracing_octrees_amd as rto
+    return rto
+
+
+def _light(light=(-1.0, -1.0, -1.0), shadow=0, K=0, radius=1.0, seed=0):
+    return _hip().make_lighting(light, bool(shadow), K, radius, seed)
+
+
+def _equal(got, want, what):
+    g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert g.shape == w.shape, what
+    neq = (g.view(np.uint32) != w.view(np.uint32)).reshape(g.shape[0], g.shape[1], -1).any(-1)
+    assert not neq.any(), f"{what}: {int(neq.sum())} pixels differ, e.g. {np.argwhere(neq)[:4].tolist()}"
+
+
+@gpu
+@pytest.mark.parametrize("scene", ["sphere64", "odd", "calgary"])
+@pytest.mark.parametrize("cam", ["outside", "inside", "axis"])
+def test_frames_match_the_statement(ctx, orc, scenes, scene, cam):
+    """RGBA and visibility bit for bit against lit_ref: every (shadow, K) setting, the three lights, two seeds where AO runs."""
+    rto = _rto()
+    s = scenes(scene)
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    view, pos = _camera(orc, s, cam)
+    W, H = 40, 30
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    rd = _rays(orc, view, pos, W, H)
+    radius = float(np.float32(4 * float(s.voxel)))
+    hits = 0
+    for light in LIGHTS:
+        for sh, K in SETTINGS:
+            for seed in ((0, 0x9E3779B9) if K else (0,)):
+                img, vis = ctx.render_lit_host(f, _light(light, sh, K, radius, seed), vis=True)
+                want, wvis = lr.lit_frame(T, s.voxel, pos, rd, W, H, _table(), light_dir=light, shadow=sh, K=K, radius=radius, seed=seed)
+                what = f"{scene}/{cam} light {light} shadow {sh} K {K} seed {seed}"
+                _equal(img, want, what)
+                assert (vis == wvis).all(), f"{what}: visibility differs at {int((vis != wvis).sum())} pixels"
+                hits += int((vis >= 0).sum())
+    assert hits > 0
+
+
+@gpu
+@pytest.mark.parametrize("scene,cams", [("sphere256", [SPHERE_CAM]), ("calgary", ["calgary_default", "calgary_oblique"])])
+def test_no_terms_is_the_box_render_at_1080p(ctx, orc, scenes, camera, scene, cams):
+    """Configs 2 and 4 at 1920x1080: shadow off, K = 0 and the default light give rto_render_device's frame bit for bit."""
+    rto = _rto()
+    s = scenes(scene)
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    W, H = 1920, 1080
+    for cam in cams:
+        view, pos = make_camera(orc, *cam) if isinstance(cam, tuple) else camera(cam)
+        f = rto.make_frame(view, pos, W / H, FOV, W, H)
+        img, vis = ctx.render_lit_host(f, _light(), vis=True)
+        want = ctx.render_host(f)
+        _equal(img, want, f"{scene} {cam}")
+        assert ((vis >= 0) == (want[..., 0] > 0.05)).all()
+
+
+@gpu
+@pytest.mark.parametrize("K", [8, 5])
+def test_config2_lit_frame_on_a_seeded_sample(ctx, orc, scenes, K):
+    """Config 2 at 1920x1080 with the shadow ray and K = 8 or 5 (pixels straddling waves): 65,536 seeded pixels equal lit_ref
+    bit for bit."""
+    rto = _rto()
+    s = scenes("sphere256")
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    W, H = 1920, 1080
+    view, pos = make_camera(orc, *SPHERE_CAM)
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    radius = float(np.float32(4 * float(s.voxel)))
+    img, vis = ctx.render_lit_host(f, _light(shadow=1, K=K, radius=radius, seed=11), vis=True)
+    rng = np.random.default_rng(2024)
+    lit_rows = np.nonzero((vis >= 0).any(1))[0]
+    pick = rng.choice(W * H, 1 << 16, replace=False)
+    pick[: 1 << 14] = (rng.choice(lit_rows, 1 << 14) * W + rng.integers(0, W, 1 << 14))     # a quarter from rows with geometry
+    pick = np.unique(pick)
+    x, y = pick % W, pick // W
+    rd = _rays(orc, view, pos, W, H)[pick]
+    want, wvis = lr.lit32(q.Tree32(s.nodes, s.min, s.voxel), s.voxel, pos, rd, x, y, _table(), shadow=1, K=K, radius=radius, seed=11)
+    got = img.reshape(-1, 4)[pick]
+    assert got.tobytes() == want.tobytes(), f"{int((got != want).any(1).sum())} of {len(pick)} pixels differ"
+    assert (vis.reshape(-1)[pick] == wvis).all()
+    assert (wvis > 0).sum() > 100 and (wvis >= 0).sum() > 5000
+
+
+@gpu
+@pytest.mark.parametrize("kind,d", [("frac", 11), ("far", 16), ("tenth", 19), ("frac", 20)])
+def test_deep_octrees(ctx, orc, kind, d):
+    """Depth 11-20 trees (tests/deep_scenes.py) at a small size: every camera of the scene, shadow and K = 8, bit for bit."""
+    rto = _rto()
+    s = ds.scene(kind, d)
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    W, H = 32, 24
+    radius = float(np.float32(4 * float(s.voxel)))
+    lit = 0
+    for name, view, pos in s.cameras(orc):
+        f = rto.make_frame(view, pos, W / H, FOV, W, H)
+        img, vis = ctx.render_lit_host(f, _light((0.3, -0.8, 0.45), 1, 8, radius, 1), vis=True)
+        want, wvis = lr.lit_frame(T, s.voxel, pos, _rays(orc, view, pos, W, H), W, H, _table(), light_dir=(0.3, -0.8, 0.45),
+                                  shadow=1, K=8, radius=radius, seed=1)
+        _equal(img, want, f"{kind}{d} {name}")
+        assert (vis == wvis).all(), f"{kind}{d} {name}: visibility"
+        lit += int((vis >= 0).sum())
+    assert lit > 0
+
+
+@gpu
+def test_carving_the_occluder_lights_its_shadow(ctx, orc):
+    """Floor and pillar built on the GPU; a box brush carves the pillar's middle: the frame equals lit_ref on the edited tree
+    (rto_download_nodes), and pixels that were in shadow are lit."""
+    rto = _rto()
+    hip = _hip()
+    g, nodes = _floor_pillar()
+    ctx.build_octree(g.data, g.min, g.voxel_size)
+    cam = orc.Camera(0.9, 0.9, 60.0)
+    cam.set_target(16.0, 2.0, 16.0)
+    view, pos = cam.get_view(), cam.get_pos()
+    W, H = 64, 48
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    rd = _rays(orc, view, pos, W, H)
+    L = _light((0.5, -1.0, 0.3), 1, 4, 3.0, 2)
+    before, vb = ctx.render_lit_host(f, L, vis=True)
+    T = q.Tree32(ctx.download_nodes(), g.min, g.voxel_size)
+    want, wv = lr.lit_frame(T, g.voxel_size, pos, rd, W, H, _table(), light_dir=(0.5, -1.0, 0.3), shadow=1, K=4, radius=3.0, seed=2)
+    _equal(before, want, "before the edit")
+    assert (vb == wv).all()
+    changed = ctx.edit_voxels(hip.make_brushes([[16.0, 11.0, 16.0]], [[3.0, 7.0, 3.0]], hip.BRUSH_BOX, hip.EDIT_CARVE))
+    assert changed > 0
+    after, va = ctx.render_lit_host(f, L, vis=True)
+    T = q.Tree32(ctx.download_nodes(), g.min, g.voxel_size)
+    want, wv = lr.lit_frame(T, g.voxel_size, pos, rd, W, H, _table(), light_dir=(0.5, -1.0, 0.3), shadow=1, K=4, radius=3.0, seed=2)
+    _equal(after, want, "after the edit")
+    assert (va == wv).all()
+    assert ((vb >= 256) & (va >= 0) & (va < 256)).sum() > 5
+
+
+@gpu
+def test_same_seed_same_bytes_and_device_form(ctx, orc, scenes):
+    """Two frames with the same seed are identical bytes (the compaction order does not show); the device form on a caller's
+    stream, with and without the visibility buffer, gives the host form's bytes; another seed changes some AO pixels."""
+    torch = pytest.importorskip("torch")
+    rto = _rto()
+    s = scenes("calgary")
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    W, H = 320, 180
+    view, pos = make_camera(orc, 0.6, 0.5, 3500.0)
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    L = _light((0.3, -0.8, 0.45), 1, 8, 40.0, 7)
+    a, va = ctx.render_lit_host(f, L, vis=True)
+    b, vb = ctx.render_lit_host(f, L, vis=True)
+    assert a.tobytes() == b.tobytes() and va.tobytes() == vb.tobytes()
+    other = torch.cuda.Stream()
+    d_rgba = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda")
+    d_vis = torch.zeros(W * H, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.render_lit_device(f, L, d_rgba.data_ptr(), d_vis.data_ptr(), other.cuda_stream)
+    other.synchronize()
+    assert d_rgba.cpu().numpy().tobytes() == a.tobytes() and d_vis.cpu().numpy().tobytes() == va.tobytes()
+    d_rgba.zero_()
+    torch.cuda.synchronize()
+    ctx.render_lit_device(f, L, d_rgba.data_ptr(), 0, other.cuda_stream)
+    other.synchronize()
+    assert d_rgba.cpu().numpy().tobytes() == a.tobytes()
+    c, vc = ctx.render_lit_host(f, _light((0.3, -0.8, 0.45), 1, 8, 40.0, 8), vis=True)
+    assert ((vc & 255) != (va & 255)).any() and ((vc >= 256) == (va >= 256)).all()
+
+
+@gpu
+def test_error_codes(ctx, orc, scenes):
+    """RTO_E_INVALID for every bad argument the header lists, RTO_E_NO_OCTREE on a fresh context, RTO_E_UNSUPPORTED for a
+    non-canonical array; a refused call leaves the next frame unchanged."""
+    torch = pytest.importorskip("torch")
+    rto = _rto()
+    hip = _hip()
+    s = scenes("sphere64")
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    view, pos = make_camera(orc, *SPHERE_CAM)
+    f = rto.make_frame(view, pos, 4 / 3, FOV, 32, 24)
+    good = _light((-1.0, -1.0, -1.0), 1, 4, 0.05, 0)
+    ref = ctx.render_lit_host(f, good)
+    Lib, h = ctx._L, ctx._h
+    out = np.zeros((24, 32, 4), np.float32)
+
+    def rc(L, frame=f, buf=out):
+        return Lib.rto_render_lit_host(h, C.byref(frame) if frame is not None else None, C.byref(L) if L is not None else None,
+                                       buf.ctypes.data if buf is not None else None, None)
+
+    assert rc(good) == hip.RTO_OK
+    assert rc(None) == hip.RTO_E_INVALID
+    assert rc(good, frame=None) == hip.RTO_E_INVALID
+    assert rc(good, buf=None) == hip.RTO_E_INVALID
+    bad = []
+    for field, value in (("ao_samples", -1), ("ao_samples", 65), ("reserved", 1)):
+        L = _light((-1.0, -1.0, -1.0), 1, 4, 0.05, 0)
+        setattr(L, field, value)
+        bad.append(L)
+    for radius in (0.0, -1.0, float("inf"), float("nan")):
+        bad.append(_light((-1.0, -1.0, -1.0), 0, 4, radius, 0))
+    for light in ((0.0, 0.0, 0.0), (float("nan"), -1.0, 0.0), (float("inf"), -1.0, 0.0), (1e-30, 0.0, 0.0)):
+        bad.append(_light(light, 1, 0, 1.0, 0))
+    for L in bad:
+        assert rc(L) == hip.RTO_E_INVALID, (list(L.light_dir), L.shadow, L.ao_samples, L.ao_radius, L.reserved)
+    assert rc(_light((-1.0, -1.0, -1.0), 1, 0, float("nan"), 0)) == hip.RTO_OK          # K = 0: the radius is not used
+    d_rgba = torch.zeros(32 * 24 * 4 + 4, dtype=torch.float32, device="cuda")
+    d_vis = torch.zeros(32 * 24 + 1, dtype=torch.int32, device="cuda")
+    dev = Lib.rto_render_lit_device
+    assert dev(h, C.byref(f), C.byref(good), C.c_void_p(d_rgba.data_ptr() + 4), None, None) == hip.RTO_E_INVALID
+    assert dev(h, C.byref(f), C.byref(good), C.c_void_p(d_rgba.data_ptr()), C.c_void_p(d_vis.data_ptr() + 2), None) == hip.RTO_E_INVALID
+    assert dev(h, C.byref(f), C.byref(good), None, None, None) == hip.RTO_E_INVALID
+    assert Lib.rto_ao_directions(None) == hip.RTO_E_INVALID
+    # frames too large for the 32-bit ray indices: refused before anything is allocated
+    for W, H, K in ((65536, 65536, 0), (8192, 8192, 64), (46341, 46341, 1)):       # 2^32 + 128, 65 * 2^26, 2 * 46341^2 ray indices
+        big = rto.make_frame(view, pos, W / H, FOV, W, H)
+        assert rc(_light((-1.0, -1.0, -1.0), 1, K, 0.05, 0), frame=big) == hip.RTO_E_INVALID, (W, H, K)
+        assert dev(h, C.byref(big), C.byref(_light((-1.0, -1.0, -1.0), 1, K, 0.05, 0)), C.c_void_p(d_rgba.data_ptr()), None, None) \
+            == hip.RTO_E_INVALID, (W, H, K)
+    wide = rto.make_frame(view, pos, 4 / 3, FOV, 0, 24)
+    assert rc(good, frame=wide) == hip.RTO_E_INVALID
+    assert ctx.render_lit_host(f, good).tobytes() == ref.tobytes()
+    fresh = rto.Context(0)
+    try:
+        with pytest.raises(hip.RtoError) as e:
+            fresh.render_lit_host(f, good)
+        assert e.value.code == hip.RTO_E_NO_OCTREE
+        perm = s.nodes.copy()
+        rng = np.random.default_rng(5)
+        n = len(perm)
+        p = np.concatenate([[0], 1 + rng.permutation(n - 1)])
+        moved = np.zeros_like(perm)
+        moved[p] = perm
+        moved["child"] = np.where(moved["child"] >= 0, p[np.maximum(moved["child"], 0)], -1)
+        fresh.upload_octree(moved, s.min, s.voxel)
+        assert fresh.info().canonical == 0
+        with pytest.raises(hip.RtoError) as e:
+            fresh.render_lit_host(f, good)
+        assert e.value.code == hip.RTO_E_UNSUPPORTED
+    finally:
+        fresh.close()
+
+
+@gpu
+def test_drop_in_render_scene_lit(orc, scenes):
+    """RayTracerBVH::renderSceneLit through host.py fills framebuffer() with the C ABI's lit frame."""
+    rto = _rto()
+    W, H = 96, 72
+    grid = rto.VoxelGrid.test_sphere(64)
+    root = rto.createOctreeFromVoxelGrid(grid)
+    rt = rto.RayTracerBVH()
+    rt.ensureComputeInitialized()
+    rt.setOctree(root, grid)
+    s = scenes("sphere64")
+    cam = rto.Camera(*SPHERE_CAM)
+    rt.renderSceneLit(cam, W, H, W / H, FOV, lightDir=(0.3, -0.8, 0.45), shadow=True, aoSamples=8, aoRadius=0.05, seed=4)
+    img = rt.framebuffer()
+    assert img is not None and img.shape == (H, W, 4)
+    ctx = rto.Context(0)
+    try:
+        ctx.upload_octree(s.nodes, s.min, s.voxel)
+        f = rto.make_frame(cam.getView(), cam.getPos(), W / H, FOV, W, H)
+        want = ctx.render_lit_host(f, _light((0.3, -0.8, 0.45), 1, 8, 0.05, 4))
+    finally:
+        ctx.close()
+    assert img.tobytes() == want.tobytes()
+    rt.renderSceneCompute(cam, W, H, W / H, FOV)
+    rt.renderSceneLit(cam, W, H, W / H, FOV, shadow=False, aoSamples=0)
+    lit0 = rt.framebuffer()
+    rt.renderSceneCompute(cam, W, H, W / H, FOV)
+    assert lit0.tobytes() == rt.framebuffer().tobytes()
+    rto.freeOctree(root)
+
+
+@gpu
+def test_trees_that_are_one_leaf(ctx, orc):
+    """A tree that is a single leaf (no descriptors): uploaded solid or empty, and built on the GPU from a full grid.  The frame
+    equals lit_ref; without terms it is rto_render_device's; a camera inside the solid leaf sees face -1 (no secondary rays)."""
+    rto = _rto()
+    hip = _hip()
+    gmin, vs = np.float32([-1.0, -1.0, -1.0]), np.float32(0.25)
+    W, H = 40, 30
+    cam = orc.Camera(0.6, 0.45, 6.0)
+    cam.set_target(0.0, 0.0, 0.0)
+    view, pos = cam.get_view(), cam.get_pos()
+    inside = np.float32([0.1, -0.2, 0.3])
+    solid = np.zeros(1, hip.NODE_DTYPE)
+    solid["size"], solid["isLeaf"], solid["isUniform"], solid["isSolid"], solid["child"] = 8, 1, 1, 1, -1
+    empty = solid.copy()
+    empty["isSolid"] = 0
+    cases = [("uploaded solid", lambda: ctx.upload_octree(solid, gmin, vs), solid),
+             ("uploaded empty", lambda: ctx.upload_octree(empty, gmin, vs), empty),
+             ("built full grid", lambda: ctx.build_octree(np.ones((8, 8, 8), np.uint8), gmin, vs), solid)]
+    for name, load, nodes in cases:
+        load()
+        assert ctx.info().num_nodes == 1, name
+        T = q.Tree32(nodes, gmin, vs)
+        for p in (pos, inside):
+            f = rto.make_frame(view, p, W / H, FOV, W, H)
+            rd = _rays(orc, view, p, W, H)
+            for light, sh, K in (((-1.0, -1.0, -1.0), 0, 0), ((0.3, -0.8, 0.45), 1, 8), ((0.0, -1.0, 0.0), 1, 5)):
+                img, vis = ctx.render_lit_host(f, _light(light, sh, K, 0.5, 9), vis=True)
+                want, wvis = lr.lit_frame(T, vs, p, rd, W, H, _table(), light_dir=light, shadow=sh, K=K, radius=0.5, seed=9)
+                _equal(img, want, f"{name} {p} {light} {sh} {K}")
+                assert (vis == wvis).all(), name
+                if sh == 0 and K == 0:
+                    _equal(img, ctx.render_host(f), f"{name}: render")
+            if nodes is solid:
+                assert (vis >= 0).any()
+                if p is inside:
+                    assert (vis == 0).all()
+            else:
+                assert (vis == -1).all()
