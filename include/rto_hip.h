@@ -513,6 +513,59 @@ int  rto_last_edit_ms(const rto_context* ctx, float ms[3]);
 /* Pure host function, no device: the quantised brush of the rule above for this grid, or RTO_E_INVALID. */
 int  rto_brush_quantize(const rto_brush* brush, const float grid_min[3], float voxel_size, int64_t cq[3], int64_t eq[3]);
 
+/* ---- mesh voxelization ----------------------------------------------------
+ * Builds the resident grid from a triangle mesh on the GPU, then the octree from it: the rule of the
+ * reference's loadCSVDataIntoVoxelGrid (S/BuildingLoader.cpp:153-290), bit for bit.  xyz: n_verts rows x, y, z (double); tris:
+ * n_tris faces of three row indices into xyz (the host layer, host/BuildingLoader.cpp, resolves the CSV's mesh and vertex numbers).
+ *   grid (AUTO)   over the rows whose three coordinates are finite, in double: min / max, padded by (double)voxel_size on both
+ *                 sides; dim = (size_t)ceil((max - min) / voxel_size).  If a dim exceeds 1000: scale = (float)max(dimX / 1000,
+ *                 dimY / 1000, dimZ / 1000) in integer (size_t) division, voxel_size *= scale in float (a dim of 1001..1999 gives
+ *                 scale 1: no change), and the dims are recomputed.  grid_min = (float)min.
+ *   grid (FIXED)  params' dims, grid_min and voxel_size.
+ *   per face      vertices rounded to float (a, b, c = rows tris[3f], tris[3f + 1], tris[3f + 2]); a face with a non-finite vertex is
+ *                 skipped.  All float, one IEEE operation per operator: start = max(0, (int)((triMin - grid_min) / voxel_size)),
+ *                 end = min(dim - 1, (int)((triMax - grid_min) / voxel_size) + 1) per axis, (int) truncating.  Each voxel i of
+ *                 [start, end]^3 is FILLED when its centre p = grid_min + ((float)i + 0.5f) * voxel_size passes the reference's
+ *                 isPointInTriangle (S/BuildingLoader.cpp:131-151): v0 = c - a, v1 = b - a, v2 = p - a, dot(x, y) = (x.x y.x +
+ *                 x.y y.y) + x.z y.z, denom = d00 d11 - d01 d01, rejected when |denom| < 1e-7f, inv = 1.0f / denom,
+ *                 u = (d11 d02 - d01 d12) inv, v = (d00 d12 - d01 d02) inv, inside when u >= 0 && v >= 0 && u + v <= 1.
+ *                 The grid is the OR over faces (face order does not matter).  A prism test: the plane distance is bounded only
+ *                 by the face's box.
+ *   recentring    recenter_passes times (0..2; S/main.cpp:376-422 runs twice on the CSV path, :1039 and :1074): lo / hi = float
+ *                 min / max over the FILLED voxels of their centres, grid_min -= 0.5f * (lo + hi); no FILLED voxel: no change.
+ * On success the context is in the state rto_build_octree(grid, grid_min, voxel_size) leaves (nodes, descriptors, info, scene
+ * bounds; frustum culling off; the grid kept resident, so rto_download_voxels, rto_edit_voxels and rto_build_leaf_triangles(NULL)
+ * work), on the build path rto_debug_set_build_path chose; triangles != 0 then also builds the leaf triangles as
+ * rto_build_leaf_triangles(NULL) does.  result (may be NULL) gets the grid after recentring.
+ * RTO_E_INVALID: NULL params, n_verts or n_tris < 0, NULL xyz / tris with n > 0, a row index outside [0, n_verts), an unknown
+ * mode, recenter_passes outside 0..2, a voxel_size that is not finite and positive, a FIXED grid with a dim below 1 or a non-finite
+ * grid_min, a face whose (int) casts above would overflow (undefined in the reference), an AUTO grid that is empty (no face, or
+ * no row with finite coordinates: the reference returns an empty grid, which rto_build_octree refuses), or a grid above the
+ * build's size limit (a dim above 2^20).  Every error leaves the context untouched.  Synchronous on the context's stream. */
+#define RTO_VOXELIZE_AUTO  0
+#define RTO_VOXELIZE_FIXED 1
+typedef struct rto_voxelize_params {   /* 40 bytes */
+    int32_t mode;                      /* RTO_VOXELIZE_* */
+    float   voxel_size;                /* AUTO: the requested size (the grid's may be scaled up); FIXED: the grid's */
+    int32_t dims[3];                   /* FIXED only */
+    float   grid_min[3];               /* FIXED only */
+    int32_t recenter_passes;           /* 0, 1 or 2 */
+    int32_t triangles;                 /* != 0: also build the leaf triangles */
+} rto_voxelize_params;
+typedef struct rto_voxelize_result {   /* 48 bytes */
+    int32_t dims[3];
+    float   grid_min[3];               /* after recentring */
+    float   voxel_size;
+    int32_t reserved;
+    int64_t filled;                    /* FILLED voxels of the grid */
+    int64_t pairs;                     /* (face, voxel) pairs tested: the voxels of the faces' boxes, degenerate faces excluded */
+} rto_voxelize_result;
+
+int  rto_voxelize_mesh(rto_context* ctx, const double* xyz, int64_t n_verts, const int32_t* tris, int64_t n_tris,
+                       const rto_voxelize_params* params, rto_voxelize_result* result /* may be NULL */);
+/* Device time in ms of the last rto_voxelize_mesh: face setup + scan, fill, recentring reduction, octree build (-1: not run). */
+int  rto_last_voxelize_ms(const rto_context* ctx, float ms[4]);
+
 /* ---- lit render -----------------------------------------------------------
  * The box render's frame with a shadow ray and ambient occlusion per hit pixel, computed on the device in one stream (DESIGN.md
  * section 12).  Rule:

@@ -19,11 +19,11 @@ from .hip import (KERNEL_AUTO, KERNEL_GENERIC, KERNEL_PACKED, KERNEL_PACKED_PERS
                   RtoError, make_frame)
 from .host import (Camera, MarchingCubesRenderer, OctreeNode, RayTracerBVH, VoxelGrid, buildLeafTriangles,
                    createOctreeFromVoxelGrid,
-                   freeOctree, getVoxelSafe, loadVoxelGrid, loadVoxelGridPartial, localMC, saveVoxelGrid)
+                   freeOctree, getVoxelSafe, loadCSVDataIntoVoxelGrid, loadVoxelGrid, loadVoxelGridPartial, localMC, saveVoxelGrid)
 
 __all__ = [
     "RayTracerBVH", "VoxelGrid", "OctreeNode", "Camera", "createOctreeFromVoxelGrid", "freeOctree",
-    "getVoxelSafe", "loadVoxelGrid", "loadVoxelGridPartial", "saveVoxelGrid", "localMC", "MarchingCubesRenderer", "buildLeafTriangles",
+    "getVoxelSafe", "loadCSVDataIntoVoxelGrid", "loadVoxelGrid", "loadVoxelGridPartial", "saveVoxelGrid", "localMC", "MarchingCubesRenderer", "buildLeafTriangles",
     "Context", "Frame", "Partition", "RtoError", "make_frame", "NODE_DTYPE",
     "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_PACKED", "KERNEL_PACKED_PERSISTENT", "KERNEL_PACKED_V1", "KERNEL_PACKED_V3", "hip", "host",
 ]

@@ -150,6 +150,7 @@ struct rto_context {
     int buildPath = 0;         // 0 = automatic (Morton-order build where it applies), 1 = level-by-level build (rto_debug_set_build_path)
     float buildUploadMs = -1.f;
     float editMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_voxels: brushes, octree rebuild, triangle rebuild (-1: not run)
+    float voxelizeMs[4] = { -1.f, -1.f, -1.f, -1.f };   // the last rto_voxelize_mesh: setup + scan, fill, recentre, octree build
 
     // lit render (rto_lit.inc): compacted hit records and their verdict counters for frames of up to litCap pixels, the hit count
     int4* d_litRec = nullptr;
@@ -2690,4 +2691,5 @@ int rto_synchronize(rto_context* c) {
 #include "rto_query.inc"
 #include "rto_tri_query.inc"
 #include "rto_edit.inc"
+#include "rto_voxelize.inc"
 #include "rto_lit.inc"

@@ -39,6 +39,7 @@ SYMBOLS = (
     "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
     "rto_edit_voxels", "rto_download_voxels", "rto_last_edit_ms", "rto_brush_quantize",
     "rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions",
+    "rto_voxelize_mesh", "rto_last_voxelize_ms",
 )
 SPLIT_MAX_FRAMES = 32
 QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
@@ -88,6 +89,20 @@ class TriHit(C.Structure):
 
 class Brush(C.Structure):
     _fields_ = [("centre", C.c_float * 3), ("extent", C.c_float * 3), ("shape", C.c_int32), ("op", C.c_int32)]
+
+
+# struct rto_voxelize_params (40 bytes) / rto_voxelize_result (48 bytes): mesh voxelization (rto_voxelize_mesh)
+VOXELIZE_AUTO, VOXELIZE_FIXED = 0, 1
+
+
+class VoxelizeParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("voxel_size", C.c_float), ("dims", C.c_int32 * 3), ("grid_min", C.c_float * 3),
+                ("recenter_passes", C.c_int32), ("triangles", C.c_int32)]
+
+
+class VoxelizeResult(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("grid_min", C.c_float * 3), ("voxel_size", C.c_float), ("reserved", C.c_int32),
+                ("filled", C.c_int64), ("pairs", C.c_int64)]
 
 
 # struct rto_lighting, 32 bytes: the lit render (rto_render_lit_*)
@@ -313,6 +328,8 @@ def load():
     L.rto_render_lit_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp, vp]
     L.rto_render_lit_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp]
     L.rto_ao_directions.argtypes = [vp]
+    L.rto_voxelize_mesh.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(VoxelizeParams), C.POINTER(VoxelizeResult)]
+    L.rto_last_voxelize_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -773,6 +790,37 @@ class Context:
         """Device ms of the last edit: (brushes, octree rebuild, triangle rebuild); -1 for a step that did not run."""
         ms = (C.c_float * 3)()
         self._check(self._L.rto_last_edit_ms(self._h, ms))
+        return tuple(ms)
+
+    # -- mesh voxelization -----------------------------------------------------
+    def voxelize_mesh(self, xyz, tris, voxel_size, grid=None, recenter=0, triangles=False) -> VoxelizeResult:
+        """rto_voxelize_mesh: xyz (n, 3) rows (float64), tris (m, 3) row indices; grid None = AUTO (the reference's grid from
+        voxel_size), else FIXED (dims (x, y, z), grid_min, voxel_size).  recenter: 0, 1 or 2 passes; triangles: also build the
+        leaf triangles.  The octree is then resident, as build_octree of the voxelized grid leaves it."""
+        v = np.ascontiguousarray(np.asarray(xyz, np.float64).reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(tris, np.int32).reshape(-1, 3))
+        p = VoxelizeParams()
+        p.voxel_size = _f(voxel_size)
+        p.recenter_passes = int(recenter)
+        p.triangles = 1 if triangles else 0
+        if grid is None:
+            p.mode = VOXELIZE_AUTO
+        else:
+            dims, gmin, vs = grid
+            p.mode = VOXELIZE_FIXED
+            p.voxel_size = _f(vs)
+            for a in range(3):
+                p.dims[a] = int(dims[a])
+                p.grid_min[a] = _f(gmin[a])
+        r = VoxelizeResult()
+        self._check(self._L.rto_voxelize_mesh(self._h, v.ctypes.data if len(v) else None, len(v), t.ctypes.data if len(t) else None,
+                                              len(t), C.byref(p), C.byref(r)))
+        return r
+
+    def last_voxelize_ms(self):
+        """Device ms of the last voxelization: (face setup + scan, fill, recentring reduction, octree build); -1: not run."""
+        ms = (C.c_float * 4)()
+        self._check(self._L.rto_last_voxelize_ms(self._h, ms))
         return tuple(ms)
 
     def scene_bounds(self) -> SceneBounds:

@@ -130,6 +130,9 @@ def load():
     L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
     L.rtoh_rt_edit_voxels.restype = C.c_int64
     L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
+    L.rtoh_grid_load_csv.argtypes = [C.c_char_p, C.c_char_p, C.c_float]
+    L.rtoh_grid_load_csv.restype = _vp
+    L.rtoh_rt_load_mesh.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int]
     _lib = L
     return L
 
@@ -185,6 +188,12 @@ class VoxelGrid:
 
     def recenter(self) -> bool:
         return bool(load().rtoh_grid_recenter(self._h))
+
+
+def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
+    """The reference's CSV loader (host/BuildingLoader.h): the two CSVs parsed on the host, voxelized on GPU 0, not recentred.
+    No vertex row or no face row: an empty grid (dims 0)."""
+    return VoxelGrid(load().rtoh_grid_load_csv(str(vertsFilename).encode(), str(facesFilename).encode(), _f(voxelSize)))
 
 
 def getVoxelSafe(grid: VoxelGrid, x: int, y: int, z: int) -> int:
@@ -434,6 +443,14 @@ class RayTracerBVH:
         shapes = np.ascontiguousarray(b["shape"], dtype=np.int32)
         ops = np.ascontiguousarray(b["op"], dtype=np.int32)
         return int(load().rtoh_rt_edit_voxels(self._h, f.ctypes.data, shapes.ctypes.data, ops.ctypes.data, len(b)))
+
+    def loadMesh(self, xyz, tris, voxelSize, recenterPasses=0, triangles=False) -> bool:
+        """Addition: RayTracerBVH::loadMesh -- rows (n, 3) and faces (m, 3) of row indices voxelized on every GPU (AUTO grid),
+        recentred recenterPasses times, the octree built there.  False on an error (lastError)."""
+        v = np.ascontiguousarray(np.asarray(xyz, np.float64).reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(tris, np.int32).reshape(-1, 3))
+        return bool(load().rtoh_rt_load_mesh(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t), _f(voxelSize), int(recenterPasses),
+                                             1 if triangles else 0))
 
     def grid(self) -> np.ndarray:
         """Addition: RayTracerBVH::grid -- the current voxels, uint8 (dimZ, dimY, dimX), every edit applied."""

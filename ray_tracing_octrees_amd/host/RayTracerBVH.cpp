@@ -44,6 +44,7 @@ struct HipApi {
     decltype(&rto_download_leaf_triangles) download_leaf_triangles = nullptr;
     decltype(&rto_download_nodes) download_nodes = nullptr;
     decltype(&rto_render_lit_host) render_lit_host = nullptr;
+    decltype(&rto_voxelize_mesh) voxelize_mesh = nullptr;
     std::string error;
 
     bool load() {
@@ -98,6 +99,7 @@ struct HipApi {
         download_leaf_triangles = reinterpret_cast<decltype(download_leaf_triangles)>(sym("rto_download_leaf_triangles"));
         download_nodes = reinterpret_cast<decltype(download_nodes)>(sym("rto_download_nodes"));
         render_lit_host = reinterpret_cast<decltype(render_lit_host)>(sym("rto_render_lit_host"));
+        voxelize_mesh = reinterpret_cast<decltype(voxelize_mesh)>(sym("rto_voxelize_mesh"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -571,6 +573,35 @@ void RayTracerBVH::editVoxels(const std::vector<VoxelBrush>& brushes) {
         if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
     }
     if (changed > 0) m_gridStale = true;
+}
+
+bool RayTracerBVH::loadMesh(const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize, int recenterPasses,
+                            bool triangles) {
+    if (!m_computeInited) ensureComputeInitialized();
+    if (!m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return false;
+    }
+    rto_voxelize_params p;
+    std::memset(&p, 0, sizeof p);
+    p.mode = RTO_VOXELIZE_AUTO;
+    p.voxel_size = voxelSize;
+    p.recenter_passes = recenterPasses;
+    p.triangles = triangles ? 1 : 0;
+    rto_voxelize_result r;
+    if (!forEachContext([&](rto_context* c) { return api().voxelize_mesh(c, xyz, nVerts, tris, nTris, &p, c == m_ctx ? &r : nullptr); },
+                        "mesh voxelization"))
+        return false;
+    m_octreeRoot = nullptr;
+    m_flatNodes.clear();
+    m_grid.dimX = r.dims[0]; m_grid.dimY = r.dims[1]; m_grid.dimZ = r.dims[2];
+    m_grid.minX = r.grid_min[0]; m_grid.minY = r.grid_min[1]; m_grid.minZ = r.grid_min[2];
+    m_grid.voxelSize = r.voxel_size;
+    m_grid.data.assign((size_t)r.dims[0] * r.dims[1] * r.dims[2], VoxelState::EMPTY);
+    m_gridStale = true;                 // grid() fetches the voxels when asked
+    rto_octree_info info;
+    if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+    return true;
 }
 
 const VoxelGrid& RayTracerBVH::grid() const {

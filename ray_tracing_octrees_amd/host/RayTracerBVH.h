@@ -145,8 +145,15 @@ public:
     // click-to-carve: pickSurface (or pick), then editVoxels({{hit.point, vec3(r), VoxelBrush::Sphere, VoxelBrush::Carve}}).
     void editVoxels(const std::vector<VoxelBrush>& brushes);
     int64_t lastEditChanged() const { return m_lastEditChanged; }   // voxels the last editVoxels changed; -1: it failed
-    // The current grid: what setOctree / setOctreeFromGrid got, with every edit applied (downloaded when first asked after an edit).
+    // The current grid: what setOctree / setOctreeFromGrid / loadMesh made, with every edit applied (downloaded when first asked
+    // after an edit or a loadMesh).
     const VoxelGrid& grid() const;
+    // Mesh in, octree out, with no host copy of the grid (rto_voxelize_mesh): the reference's
+    // loadCSVDataIntoVoxelGrid rule on every GPU, then recenterFilledVoxels recenterPasses times (main.cpp runs it twice on the CSV
+    // path), then the octree as setOctreeFromGrid builds it; triangles: the leaf triangles too.  xyz: nVerts rows (x, y, z); tris:
+    // nTris faces of three row indices.  AUTO grid from voxelSize; false (lastError()) on any error.  grid() downloads the result.
+    bool loadMesh(const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize, int recenterPasses = 0,
+                  bool triangles = false);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

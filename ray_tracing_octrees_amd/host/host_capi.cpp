@@ -6,6 +6,7 @@
 #include <new>
 #include <string>
 
+#include "BuildingLoader.h"
 #include "CacheUtils.h"
 #include "Camera.h"
 #include "Frustum.h"
@@ -49,6 +50,10 @@ void rtoh_grid_data(const VoxelGrid* g, uint8_t* out) {
 }
 int64_t rtoh_grid_count(const VoxelGrid* g) { return (int64_t)g->data.size(); }
 int rtoh_grid_recenter(VoxelGrid* g) { return recenterFilledVoxels(*g) ? 1 : 0; }
+// loadCSVDataIntoVoxelGrid (host/BuildingLoader.h): voxelized on GPU 0
+VoxelGrid* rtoh_grid_load_csv(const char* verts, const char* faces, float voxelSize) {
+    return new VoxelGrid(loadCSVDataIntoVoxelGrid(verts, faces, voxelSize));
+}
 int rtoh_get_voxel_safe(const VoxelGrid* g, int x, int y, int z) { return (int)getVoxelSafe(*g, x, y, z); }
 
 // ---------------------------------------------------------------- octree
@@ -241,6 +246,10 @@ void rtoh_rt_grid(const RayTracerBVH* rt, int dims[3], uint8_t* out) {
     const VoxelGrid& g = rt->grid();
     dims[0] = g.dimX; dims[1] = g.dimY; dims[2] = g.dimZ;
     if (out) for (size_t i = 0; i < g.data.size(); i++) out[i] = (uint8_t)g.data[i];
+}
+int rtoh_rt_load_mesh(RayTracerBVH* rt, const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize,
+                      int recenterPasses, int triangles) {
+    return rt->loadMesh(xyz, nVerts, tris, nTris, voxelSize, recenterPasses, triangles != 0) ? 1 : 0;
 }
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }
