@@ -120,6 +120,9 @@ def lib():
     L.orc_render_triangles.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _f32p, C.c_float, _f32p, _f32p, C.c_float,
                                        C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(_Stats), C.c_int]
     L.orc_max_threads.restype = C.c_int
+    L.orc_voxelize_fill.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, _f32p, C.c_float, C.c_void_p,
+                                    C.POINTER(C.c_int64)]
+    L.orc_voxelize_fill.restype = C.c_int
     _lib = L
     return L
 
@@ -398,6 +401,22 @@ def render_triangles(nodes, tris, tri_offset, grid_min, voxel_size, view, cam_po
 
 def max_threads() -> int:
     return lib().orc_max_threads()
+
+
+def voxelize_fill(xyz, tris, dims, grid_min, voxel_size, grid=True):
+    """orc_voxelize_fill: the fill of rto_voxelize_mesh on a given grid (dims (x, y, z), grid_min, voxel_size), the C statement of
+    tests/voxelize_ref.fill.  (grid uint8 [dimZ, dimY, dimX] or None when grid=False, pairs, overflow flag)."""
+    v = np.ascontiguousarray(np.asarray(xyz, np.float64).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(tris, np.int32).reshape(-1, 3))
+    d = np.ascontiguousarray([int(x) for x in dims], np.int32)
+    out = np.empty((int(d[2]), int(d[1]), int(d[0])), np.uint8) if grid else None
+    pairs = C.c_int64()
+    rc = lib().orc_voxelize_fill(v.ctypes.data if len(v) else None, len(v), t.ctypes.data if len(t) else None, len(t),
+                                 d.ctypes.data, _f32(grid_min), float(np.float32(voxel_size)),
+                                 out.ctypes.data if grid else None, C.byref(pairs))
+    if rc < 0:
+        raise ValueError("orc_voxelize_fill: a face names a row outside the rows given")
+    return out, int(pairs.value), bool(rc)
 
 
 # ---------------------------------------------------------------- real reference (optional)

@@ -1128,3 +1128,116 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
         }
     if (stats) { stats->rays = (uint64_t)W * H; stats->pops = pops; stats->hits = hits; stats->capped = capped; stats->internal = 0; stats->max_stack = 0; stats->overflow = overflow; }
 }
+
+/* ------------------------------------------------------------------ */
+/* mesh voxelization: the fill of rto_voxelize_mesh (rto_oracle.h)     */
+/* ------------------------------------------------------------------ */
+
+typedef struct vox_face {
+    float a[3], e0[3], e1[3];
+    float d00, d01, d11, inv;
+    int64_t lo[3], n[3];
+} vox_face;
+
+/* glm 0.9.9.7 compute_dot: tmp = a * b; (tmp.x + tmp.y) + tmp.z */
+static inline float vox_dot(const float a[3], const float b[3]) {
+    float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
+    float xy = x + y;
+    return xy + z;
+}
+
+static inline int vox_int_ok(float t) { return t >= -2147483648.0f && t < 2147483648.0f; }
+
+/* One face: 1 = voxels to test (F filled in), 0 = none (non-finite vertex, empty box, degenerate), -1 = a box cast overflows. */
+static int vox_face_setup(const double* xyz, const int32_t* tri, const int32_t dims[3], const float gmin[3], float vs, vox_face* F) {
+    float v[3][3];
+    int finite = 1;
+    for (int k = 0; k < 3; k++)
+        for (int a = 0; a < 3; a++) {
+            v[k][a] = (float)xyz[3 * (int64_t)tri[k] + a];
+            finite = finite && isfinite(v[k][a]);
+        }
+    if (!finite) return 0;
+    int ok = 1;
+    for (int a = 0; a < 3; a++) {
+        float mn = v[0][a], mx = v[0][a];
+        for (int k = 1; k < 3; k++) { mn = v[k][a] < mn ? v[k][a] : mn; mx = v[k][a] > mx ? v[k][a] : mx; }
+        float dmn = mn - gmin[a], dmx = mx - gmin[a];
+        float ts = dmn / vs, te = dmx / vs;
+        if (!vox_int_ok(ts) || !vox_int_ok(te)) { ok = 0; continue; }
+        int64_t s = (int64_t)(int32_t)ts, e = (int64_t)(int32_t)te + 1;          /* C casts truncate toward zero */
+        if (s < 0) s = 0;
+        if (e > (int64_t)dims[a] - 1) e = (int64_t)dims[a] - 1;
+        F->lo[a] = s;
+        F->n[a] = e - s + 1 > 0 ? e - s + 1 : 0;
+        F->a[a] = v[0][a];
+        F->e0[a] = v[2][a] - v[0][a];                                            /* v0 = c - a */
+        F->e1[a] = v[1][a] - v[0][a];                                            /* v1 = b - a */
+    }
+    if (!ok) return -1;
+    F->d00 = vox_dot(F->e0, F->e0);
+    F->d01 = vox_dot(F->e0, F->e1);
+    F->d11 = vox_dot(F->e1, F->e1);
+    float dd = F->d00 * F->d11, oo = F->d01 * F->d01;
+    float denom = dd - oo;
+    if (fabsf(denom) < 1e-7f) return 0;
+    F->inv = 1.0f / denom;
+    return F->n[0] > 0 && F->n[1] > 0 && F->n[2] > 0;
+}
+
+int orc_voxelize_fill(const double* xyz, int64_t nv, const int32_t* tris, int64_t nf, const int32_t dims[3], const float gmin[3],
+                      float vs, uint8_t* out, int64_t* pairs) {
+    for (int64_t i = 0; i < 3 * nf; i++)
+        if (tris[i] < 0 || (int64_t)tris[i] >= nv) return -1;
+    const int64_t sy = dims[0], sz = (int64_t)dims[0] * dims[1], nvox = sz * dims[2];
+    if (out) {
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < nvox; i += 1 << 20) memset(out + i, 0, (size_t)(nvox - i < (1 << 20) ? nvox - i : (1 << 20)));
+    }
+    vox_face* F = (vox_face*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(vox_face));
+    int64_t* layer = (int64_t*)malloc((size_t)(nf + 1) * sizeof(int64_t));     /* prefix of the boxes' z extents */
+    if (!F || !layer) { free(F); free(layer); return -1; }
+    int bad = 0;
+    int64_t total = 0;
+#pragma omp parallel for schedule(static) reduction(| : bad) reduction(+ : total)
+    for (int64_t f = 0; f < nf; f++) {
+        int r = vox_face_setup(xyz, tris + 3 * f, dims, gmin, vs, &F[f]);
+        if (r < 0) bad = 1;
+        if (r <= 0) F[f].n[0] = F[f].n[1] = F[f].n[2] = 0;
+        total += F[f].n[0] * F[f].n[1] * F[f].n[2];
+    }
+    *pairs = total;
+    layer[0] = 0;
+    for (int64_t f = 0; f < nf; f++) layer[f + 1] = layer[f] + F[f].n[2];
+    if (out && !bad) {
+        /* one work item per (face, z layer of its box), so a face of 10^9 voxels spreads over the threads like 10^6 small ones */
+        const int64_t items = layer[nf];
+#pragma omp parallel for schedule(dynamic, 16)
+        for (int64_t it = 0; it < items; it++) {
+            int64_t lo = 0, hi = nf - 1;                                    /* largest f with layer[f] <= it */
+            while (lo < hi) {
+                int64_t mid = lo + (hi - lo + 1) / 2;
+                if (layer[mid] <= it) lo = mid; else hi = mid - 1;
+            }
+            const vox_face* G = &F[lo];
+            const int64_t iz = G->lo[2] + (it - layer[lo]);
+            const float pz = gmin[2] + ((float)iz + 0.5f) * vs;
+            for (int64_t iy = G->lo[1]; iy < G->lo[1] + G->n[1]; iy++) {
+                const float py = gmin[1] + ((float)iy + 0.5f) * vs;
+                for (int64_t ix = G->lo[0]; ix < G->lo[0] + G->n[0]; ix++) {
+                    const float px = gmin[0] + ((float)ix + 0.5f) * vs;
+                    const float w[3] = { px - G->a[0], py - G->a[1], pz - G->a[2] };
+                    const float d02 = vox_dot(G->e0, w), d12 = vox_dot(G->e1, w);
+                    const float un = G->d11 * d02, um = G->d01 * d12;
+                    const float vn = G->d00 * d12, vm = G->d01 * d02;
+                    const float u = (un - um) * G->inv;
+                    const float v = (vn - vm) * G->inv;
+                    if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f) out[ix + iy * sy + iz * sz] = 1;
+                }
+            }
+        }
+    }
+    free(F);
+    free(layer);
+    return bad;
+}

@@ -158,6 +158,17 @@ void orc_render_triangles(const orc_node* nodes, int64_t n, const float* tris, c
                           const float gridMin[3], float voxelSize, const float view[16], const float camPos[3],
                           float aspect, float fovDeg, int W, int H, int shadow, float* out, orc_stats* stats, int nthreads);
 
+/* ---- mesh voxelization: the fill of rto_voxelize_mesh (include/rto_hip.h) ----------------------------
+ * The per-face and per-voxel rule of tests/voxelize_ref.py (face_terms, fill), which is pinned to the reference's
+ * loadCSVDataIntoVoxelGrid: float vertices, the voxel box [max(0, (int)t_min), min(dim - 1, (int)t_max + 1)] with truncating
+ * casts, the prism test at every voxel centre of the box in glm's dot order.  A face with a non-finite vertex, an empty box or
+ * |denom| < 1e-7f has no voxels.  OpenMP over (face, z layer of its box); the writes are byte stores of 1.
+ * xyz: nv rows (double); tris: nf faces of row indices; out: dims[0] * dims[1] * dims[2] bytes (x fastest), cleared here, or
+ * NULL to count only.  *pairs: the (face, voxel) pairs tested.  Returns 1 when a finite face's box casts would overflow int (the
+ * library refuses the mesh; out is then left cleared), 0 otherwise, -1 for a row index outside [0, nv) or no memory. */
+int orc_voxelize_fill(const double* xyz, int64_t nv, const int32_t* tris, int64_t nf, const int32_t dims[3], const float gmin[3],
+                      float vs, uint8_t* out, int64_t* pairs);
+
 int orc_max_threads(void);
 
 #ifdef __cplusplus

@@ -96,6 +96,18 @@ def test_fresh_reference_equals_the_rule_on_random_meshes():
             grid, d, m, v, _ = vr.voxelize(pts, [f[1:] for f in faces], vox)
             assert tuple(dims) == d and _bits(gmin) == _bits(m) and _bits(vs) == _bits(v), k
             assert np.array_equal(grid.reshape(-1), data), k
+        # the AUTO families of tests/voxelize_families.py: the rescale's edges with NaN rows and degenerate faces, and a mesh
+        # whose every face is degenerate (FIXED grids have no counterpart in the reference)
+        import voxelize_families as vf
+        autos = {f"auto_{d}": vf.auto_edges(d) for d in vf.AUTO_EDGE_DIMS}
+        autos["all_degenerate_auto"] = vf.empty_all_degenerate(auto=True)
+        for name, c in autos.items():
+            rows = [(1, i, *map(float, p)) for i, p in enumerate(c.xyz)]
+            vcsv, fcsv = mgv.to_csv(rows, [(1, *map(int, t)) for t in c.tris])
+            dims, gmin, vs, data = mgv.run_ref(exe, tmp, vcsv, fcsv, c.voxel)
+            grid, d, m, v, _ = vr.voxelize(c.xyz, c.tris, c.voxel)
+            assert tuple(dims) == d and _bits(gmin) == _bits(m) and _bits(vs) == _bits(v), name
+            assert np.array_equal(grid.reshape(-1), data), name
 
 
 def test_voxelize_abi_layout_and_exports():

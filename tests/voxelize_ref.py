@@ -115,11 +115,13 @@ def recenter(grid, gmin, vs, passes=1):
     """recenterFilledVoxels applied `passes` times: the float32 grid_min after it."""
     gmin = np.asarray(gmin, np.float32).copy()
     vs = f32(vs)
-    nz = np.nonzero(grid)
-    if len(nz[0]) == 0:
-        return gmin
-    lo = [int(nz[2 - a].min()) for a in range(3)]
-    hi = [int(nz[2 - a].max()) for a in range(3)]
+    lo, hi = [], []
+    for a in range(3):                                       # grid is [z, y, x]: axis a is array axis 2 - a
+        occ = np.flatnonzero(grid.any(axis=tuple(k for k in range(3) if k != 2 - a)))
+        if len(occ) == 0:
+            return gmin
+        lo.append(int(occ[0]))
+        hi.append(int(occ[-1]))
     for _ in range(passes):
         for a in range(3):
             clo = gmin[a] + (f32(lo[a]) + f32(0.5)) * vs
