@@ -15,6 +15,7 @@ static int lean_block(int path);
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace rto;

@@ -1,5 +1,5 @@
 // rto_lit.inc -- the lit render (include/rto_hip.h, rto_render_lit_*): the box render's frame with a shadow ray and ambient
-// occlusion per hit pixel, all on the device.  Included at the end of rto_api.hip, after rto_query.inc (desc_walk).
+// occlusion per hit pixel, all on the device.  Included at the end of rto_api.hip, after rto_query.inc (box_walk: desc_walk under the box rule).
 //
 // Rule (DESIGN.md section 12).  The primary hit is the FIRST box query on the frame's pixel ray; the secondary origin is the hit
 // point p = o + d tHit with its coordinate on the entry face's axis a replaced by the leaf's own plane + sigma eps (sigma = +1 for
@@ -12,7 +12,7 @@
 //                    are compacted (one ballot and one atomic per wave) into 32-byte records.
 //   k_lit_secondary  persistent waves over the secondary rays of the compacted hits: the shadow rays first, one per hit, then,
 //                    from the next multiple of 64, K AO rays per hit in adjacent lanes.  Each ray is built in registers from its
-//                    record (no ray is stored) and walked by desc_walk<ANY>.  A hit's verdicts are summed in the wave (ballot +
+//                    record (no ray is stored) and walked by box_walk<ANY>.  A hit's verdicts are summed in the wave (ballot +
 //                    popcount over its lanes) and added to its counter with one atomic per piece (+1 << 16 per piece); the
 //                    piece that completes the count shades the pixel.
 
@@ -80,13 +80,13 @@ struct LitArgs {
     const rto_node* nodes;
 };
 
-// desc_walk, or for a tree that is one leaf the root's own test: the slab test with tNear < 1e30 (and, outside FIRST, tNear <= t_hi),
+// box_walk, or for a tree that is one leaf the root's own test: the slab test with tNear < 1e30 (and, outside FIRST, tNear <= t_hi),
 // then tHit = max(0, tNear) <= tFar and <= t_hi if the leaf is solid -- what the walk of a one-node array does under every rule.
-// L.rootLeaf is the same for every lane, so the ballot inside desc_walk still sees the whole wave.
+// L.rootLeaf is the same for every lane, so the ballot inside the walk still sees the whole wave.
 template <int QMODE>
 __device__ __forceinline__ DescHit lit_walk(const RenderParams& P, const Geo& G, const Ray r, float thi, bool valid, const LitArgs& L,
                                             const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode) {
-    if (!L.rootLeaf) return desc_walk<QMODE>(P, G, r, 0.0f, thi, valid, desc, stk, stkNode);
+    if (!L.rootLeaf) return box_walk<QMODE>(P, G, r, 0.0f, thi, valid, desc, stk, stkNode);
     DescHit w;
     w.hit = false; w.t = 1e30f; w.x = w.y = w.z = 0; w.size = P.rootSize; w.j = 0; w.node = 0;
     if (valid && L.nodes[0].isSolid == 1) {
@@ -293,7 +293,7 @@ static int render_lit(rto_context* c, const rto_frame* f, const rto_lighting* Lt
     A.seed = Lt->seed;
     A.rootLeaf = c->numNodes == 1 ? 1 : 0;
     A.nodes = c->d_nodes;
-    const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * (sizeof(uint2) + sizeof(unsigned));   // <= 64,512 B (depth 20)
+    const size_t lds = desc_stack_bytes(P.depth);
     RTO_HIP(c, hipMemsetAsync(c->d_litCount, 0, sizeof(unsigned), s));
     const int64_t tiles = (int64_t)P.tilesX * P.tilesY;
     hipLaunchKernelGGL(k_lit_primary, dim3((unsigned)((tiles + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), lds, s, P, A, c->d_desc);

@@ -82,21 +82,28 @@ __device__ __forceinline__ void store_hit(const QuerySrc& Q, int64_t i, bool hit
 //           popped except, at a leaf, the children below the path on each level: pops = 1 + 8 entered - sum of the path's child
 //           indices, and that sum is popcount(x) + 2 popcount(y) + 4 popcount(z) of the leaf's position (the path's bits).  A hit
 //           past 512 pops is a miss (the render's loop ended first); past 8 entered > 511 + 7 depth no later hit can be in reach.
-//   CLOSEST the ray's own octant first (k_closest_near_first's order), a node cut when tNear > min(best, t_hi) -- a child's tNear is
-//           never below its parent's --, equal tHit resolved by the LIFO pop order (pops_before).
-//   ANY     the same order, ends at the first accepted leaf.
-// desc_walk is that walk for one lane; k_query_desc and the lit render's kernels (rto_lit.inc) call it.
+//   CLOSEST the ray's own octant first (k_closest_near_first's order); ANY the same order, ends at the first accepted leaf.
+// desc_walk is that walk for one lane.  What a query kind adds is its leaf rule:
+//   kPrune      may a box be cut by t?  Then the root, the child verdicts' far clamp and every popped box (internal ones too) are
+//               held against min(closest(), t_hi) -- a child's tNear is never below its parent's; otherwise only leaves are slab-
+//               tested at the pop, at the default clamps;
+//   leaves(d.x) the leaf children of a descriptor that can hold a hit;
+//   closest()   the t a pruning rule holds boxes against (the best hit so far);
+//   leaf(..)    a popped leaf whose box passed: true when it holds an accepted hit, which the rule has then recorded.
+// BoxRule is the box queries' (the lit render's too), TriRule (rto_tri_query.inc) the triangle queries'.
 
-// The two LDS stacks of the calling lane: `levels` entries of each per lane, [wave][level][lane] (dynamic LDS of
-// kBlock / kWave * levels * kWave * 12 bytes, <= 64,512 B at depth 20).
+// The two LDS stacks of the calling lane: `levels` entries of each per lane, [wave][level][lane].
 __device__ __forceinline__ void desc_stacks(uint2* lds, int levels, uint2*& stk, unsigned*& stkNode) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
     stk = lds + (size_t)wave * levels * kWave + lane;
     stkNode = reinterpret_cast<unsigned*>(lds + (size_t)waves * levels * kWave) + (size_t)wave * levels * kWave + lane;
 }
 
-// What a descriptor walk found: the accepted leaf's position and size, tHit, its child slot j in the parent whose descriptor
-// index is `node` (the leaf's array index is descFirstChild[node] + j).
+// Their dynamic LDS for a workgroup of kBlock: 12 bytes per wave, level and lane, 61,440 B at depth 20.
+static size_t desc_stack_bytes(int levels) { return (size_t)(kBlock / kWave) * levels * kWave * (sizeof(uint2) + sizeof(unsigned)); }
+
+// What a box walk found: the accepted leaf's position and size, tHit, its child slot j in the parent whose descriptor index is
+// `node` (the leaf's array index is descFirstChild[node] + j).
 struct DescHit {
     bool hit;
     float t;
@@ -104,17 +111,42 @@ struct DescHit {
     unsigned node;
 };
 
-// The walk of one ray (r, window [tlo, thi]) under rule QMODE.  Called by every lane of the wave together (the risky-ray vote is a
-// wave ballot); `valid` false: the lane takes no part and gets a miss.
+// Solid leaves; tHit = max(t_lo, tNear) is the box's own, so CLOSEST and ANY cut every box past the best hit or the window.
 template <int QMODE>
-__device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G, const Ray r, float tlo, float thi, bool valid,
-                                             const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode) {
+struct BoxRule {
+    static constexpr bool kPrune = QMODE != kQueryFirst;
+    DescHit best;
+    __device__ __forceinline__ BoxRule() { best.hit = false; best.t = 1e30f; best.x = best.y = best.z = best.size = best.j = 0; best.node = 0; }
+    __device__ __forceinline__ static unsigned leaves(unsigned dx) { return dx & 0xffu; }
+    __device__ __forceinline__ float closest() const { return best.t; }
+    // CLOSEST in the octant order: equal tHit goes to the leaf the reference's LIFO order pops first (pops_before)
+    __device__ __forceinline__ bool leaf(const Ray&, float tlo, float thi, float tNear, float tFar, int x, int y, int z, int size, int j,
+                                              const unsigned* node) {
+        const float tHit = gmax(tlo, tNear);
+        bool take = tHit <= tFar && tHit <= thi;
+        if (QMODE == kQueryClosest) {
+            // plain booleans, as in k_closest_near_first (a short-circuit form lost updates in this divergent loop there)
+            const bool nearer = tHit < best.t;
+            const bool tie = tHit == best.t;                       // only after a hit: best.t starts at 1e30 > t_hi
+            const bool first = pops_before(x, y, z, best.x, best.y, best.z);
+            take = take && (nearer || (tie && first));
+        }
+        if (take) { best.t = tHit; best.x = x; best.y = y; best.z = z; best.size = size; best.j = j; best.node = *node; }
+        return take;
+    }
+};
+
+// The walk of one ray (r, window [tlo, thi]) in mode QMODE under leaf rule R; true: R holds the hit.  Called by every lane of the
+// wave together (the risky-ray vote is a wave ballot); `valid` false: the lane takes no part and gets a miss.
+template <int QMODE, class Rule>
+__device__ __forceinline__ bool desc_walk(const RenderParams& P, const Geo& G, const Ray r, float tlo, float thi, bool valid,
+                                          const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode, Rule& R) {
     const float kEps = __uint_as_float(1u), kBelow1e30 = __uint_as_float(0x7149f2c9u);
     bool active = false;
     if (valid) {
         float tNear, tFar, a0, a1, a2, a3, a4, a5;
         active = slab_exact(G, r, 0, 0, 0, P.rootSize, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
-        if (QMODE != kQueryFirst) active = active && !(tNear > thi);
+        if (Rule::kPrune) active = active && !(tNear > thi);
     }
     const bool risky = active && !(__builtin_isfinite(r.ix) && __builtin_isfinite(r.iy) && __builtin_isfinite(r.iz) &&
                                    __builtin_isfinite(r.ox) && __builtin_isfinite(r.oy) && __builtin_isfinite(r.oz) &&
@@ -125,9 +157,6 @@ __device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G
     const unsigned flip = QMODE == kQueryFirst ? 0u : ((r.dx < 0.0f ? 1u : 0u) | (r.dy < 0.0f ? 2u : 0u) | (r.dz < 0.0f ? 4u : 0u));
 
     bool hit = false, enter = active;
-    float best = 1e30f;
-    int bx = 0, by = 0, bz = 0, bs = 0, bj = 0;
-    unsigned bnode = 0;
     unsigned cur = 0, lvlPending = 0;
     int cx = 0, cy = 0, cz = 0, bpos = P.depth - 1;
     int entered = 0;
@@ -141,9 +170,9 @@ __device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G
             if (anyRisky) fail8 = child_fail_mask_exact(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, cx, cy, cz, 1 << bpos);
             else fail8 = child_fail_mask_fast<true, false>(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, sgnX, sgnY, sgnZ,
                                                            cx, cy, cz, (float)(1 << bpos), kEps,
-                                                           QMODE == kQueryFirst ? kBelow1e30 : gmax(kEps, gmin(best, thi)));   // the pop re-tests exactly
+                                                           Rule::kPrune ? gmax(kEps, gmin(R.closest(), thi)) : kBelow1e30);   // the pop re-tests exactly
             const unsigned im = (d.x >> 8) & 0xffu;
-            unsigned cand = ((d.x | im) & 0xffu) & ~fail8;       // solid leaves and internal children whose box the ray meets
+            unsigned cand = ((Rule::leaves(d.x) | im) & 0xffu) & ~fail8;   // candidate leaves and internal children whose box the ray meets
             if (QMODE != kQueryFirst) cand = flip_children(cand, flip);
             stk[bpos * kWave] = make_uint2(cand | (im << 8), d.y);
             stkNode[bpos * kWave] = cur;
@@ -165,10 +194,10 @@ __device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G
         const bool internal = (im & bit) != 0;
         float tNear = 0.0f, tFar = 0.0f;
         bool pass = true;
-        if (QMODE != kQueryFirst || !internal) {
+        if (Rule::kPrune || !internal) {
             float a0, a1, a2, a3, a4, a5;
             pass = slab_exact(G, r, chx, chy, chz, h, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
-            if (QMODE != kQueryFirst) pass = pass && !(tNear > gmin(best, thi));
+            if (Rule::kPrune) pass = pass && !(tNear > gmin(R.closest(), thi));
         }
         if (!pass) continue;
         if (internal) {
@@ -176,18 +205,11 @@ __device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G
             cx = chx; cy = chy; cz = chz; bpos = Lb - 1; enter = true;
             continue;
         }
-        const float tHit = gmax(tlo, tNear);
-        const bool ok = tHit <= tFar && tHit <= thi;
+        const bool got = R.leaf(r, tlo, thi, tNear, tFar, chx, chy, chz, h, j, stkNode + Lb * kWave);
         if (QMODE == kQueryClosest) {
-            // plain booleans, as in k_closest_near_first (a short-circuit form lost updates in this divergent loop there)
-            const bool nearer = tHit < best;
-            const bool tie = tHit == best;                         // only after a hit: best starts at 1e30 > t_hi
-            const bool first = pops_before(chx, chy, chz, bx, by, bz);
-            if (ok && (nearer || (tie && first))) {
-                best = tHit; hit = true; bx = chx; by = chy; bz = chz; bs = h; bj = j; bnode = stkNode[Lb * kWave];
-            }
-        } else if (ok) {
-            best = tHit; hit = true; bx = chx; by = chy; bz = chz; bs = h; bj = j; bnode = stkNode[Lb * kWave];
+            hit = hit || got;                                      // a plain boolean: got is computed above
+        } else if (got) {
+            hit = true;
             if (QMODE == kQueryFirst) {
                 const int pops = 1 + 8 * entered - (__builtin_popcount(chx) + 2 * __builtin_popcount(chy) + 4 * __builtin_popcount(chz));
                 if (pops > kMaxTraversalSteps) hit = false;        // S/RT:254: the loop ended before this pop
@@ -195,9 +217,16 @@ __device__ __forceinline__ DescHit desc_walk(const RenderParams& P, const Geo& G
             break;
         }
     }
-    DescHit out;
-    out.hit = hit; out.t = best; out.x = bx; out.y = by; out.z = bz; out.size = bs; out.j = bj; out.node = bnode;
-    return out;
+    return hit;
+}
+
+// The box walk of one lane, as k_query_desc and the lit render's kernels (rto_lit.inc) ask for it.
+template <int QMODE>
+__device__ __forceinline__ DescHit box_walk(const RenderParams& P, const Geo& G, const Ray r, float tlo, float thi, bool valid,
+                                            const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode) {
+    BoxRule<QMODE> R;
+    R.best.hit = desc_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode, R);
+    return R.best;
 }
 
 template <int QMODE, bool PIXELS>
@@ -214,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc 
     r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
     float tlo = 0.0f, thi = 0.0f;
     const bool valid = i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi);
-    const DescHit w = desc_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode);
+    const DescHit w = box_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode);
     if (i < Q.n) {
         const int node = w.hit ? descFirstChild[w.node] + w.j : -1;
         const int face = w.hit ? query_face(G, r, w.x, w.y, w.z, w.size, w.t) : -1;
@@ -292,28 +321,32 @@ static int query_check(rto_context* c, const char* fn, int mode, int64_t n, cons
     return RTO_OK;
 }
 
-template <bool PIXELS>
-static int launch_query(rto_context* c, int mode, const RenderParams& P, QuerySrc Q, hipStream_t s) {
+// The launches of one query call, box or triangle: chunks of kQueryChunk rays, the descriptor kernels (workgroups of kBlock) on a
+// canonical tree unless RTO_KERNEL_GENERIC is set, the node kernels (one wave) otherwise.  launch(mode as a compile-time constant,
+// desc, grid, block, lds, Q of the chunk) names the family's kernel.
+template <class Launch>
+static int launch_query(rto_context* c, int mode, int depth, QuerySrc Q, Launch launch) {
     const bool desc = c->canonical && c->numInternal > 0 && c->kernelMode != RTO_KERNEL_GENERIC;
-    const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * (sizeof(uint2) + sizeof(unsigned));   // <= 64,512 B (depth 20)
+    const int block = desc ? kBlock : kQueryNodesBlock;
+    const size_t lds = desc ? desc_stack_bytes(depth) : (size_t)kStackCap * kQueryNodesBlock * sizeof(int);
     for (int64_t off = 0; off < Q.n; off += kQueryChunk) {
         Q.base = off;
-        const int64_t rays = std::min(Q.n - off, kQueryChunk);
-        const dim3 grid((unsigned)((rays + kBlock - 1) / kBlock)), block(kBlock);
-        const dim3 gridN((unsigned)((rays + kQueryNodesBlock - 1) / kQueryNodesBlock)), blockN(kQueryNodesBlock);
-        const size_t ldsN = (size_t)kStackCap * kQueryNodesBlock * sizeof(int);
-        if (desc) {
-            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_query_desc<kQueryFirst, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
-            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_query_desc<kQueryClosest, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
-            else hipLaunchKernelGGL((k_query_desc<kQueryAny, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
-        } else {
-            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_query_nodes<kQueryFirst, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
-            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_query_nodes<kQueryClosest, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
-            else hipLaunchKernelGGL((k_query_nodes<kQueryAny, PIXELS>), gridN, blockN, ldsN, s, P, Q, c->d_nodes);
-        }
+        const dim3 grid((unsigned)((std::min(Q.n - off, kQueryChunk) + block - 1) / block));
+        if (mode == RTO_QUERY_FIRST) launch(std::integral_constant<int, kQueryFirst>(), desc, grid, dim3(block), lds, Q);
+        else if (mode == RTO_QUERY_CLOSEST) launch(std::integral_constant<int, kQueryClosest>(), desc, grid, dim3(block), lds, Q);
+        else launch(std::integral_constant<int, kQueryAny>(), desc, grid, dim3(block), lds, Q);
         RTO_HIP(c, hipGetLastError());
     }
     return RTO_OK;
+}
+
+template <bool PIXELS>
+static int launch_box_query(rto_context* c, int mode, const RenderParams& P, const QuerySrc& Q0, hipStream_t s) {
+    return launch_query(c, mode, P.depth, Q0, [&](auto m, bool desc, dim3 grid, dim3 block, size_t lds, const QuerySrc& Q) {
+        constexpr int M = decltype(m)::value;
+        if (desc) hipLaunchKernelGGL((k_query_desc<M, PIXELS>), grid, block, lds, s, P, Q, c->d_desc, c->d_descFirstChild);
+        else hipLaunchKernelGGL((k_query_nodes<M, PIXELS>), grid, block, lds, s, P, Q, c->d_nodes);
+    });
 }
 
 static int query_rays(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_hit* d_hits, hipStream_t s) {
@@ -322,7 +355,7 @@ static int query_rays(rto_context* c, int mode, const rto_ray* d_rays, int64_t n
     RenderParams P;
     std::memset(&P, 0, sizeof P);
     query_geometry(c, P);
-    return launch_query<false>(c, mode, P, QuerySrc{ d_rays, nullptr, d_hits, n, 0 }, s);
+    return launch_box_query<false>(c, mode, P, QuerySrc{ d_rays, nullptr, d_hits, n, 0 }, s);
 }
 
 static int query_pixels(rto_context* c, int mode, const rto_frame* f, const int32_t* d_xy, int64_t n, rto_hit* d_hits, hipStream_t s) {
@@ -330,65 +363,58 @@ static int query_pixels(rto_context* c, int mode, const rto_frame* f, const int3
     RenderParams P;
     const int rc = fill_params(c, f, nullptr, P, s);             // the renders' ray tables and inverse view: bit-identical rays
     if (rc != RTO_OK) return rc;
-    return launch_query<true>(c, mode, P, QuerySrc{ nullptr, d_xy, d_hits, n, 0 }, s);
+    return launch_box_query<true>(c, mode, P, QuerySrc{ nullptr, d_xy, d_hits, n, 0 }, s);
+}
+
+// One entry of the C ABI: `pixels` (xy pairs of `frame`) or rays, `tris` (the leaf triangles must be resident) or boxes.  The checks
+// come in the order the ABI promises; n == 0 is RTO_OK whatever is resident.  run(d_in, d_hits, stream) is the device form, called
+// on `stream` for a *_device entry; a *_host entry (`host`) stages `in` and the hits through stream-ordered scratch around it on
+// the context's stream and waits.
+template <class In, class Hit, class Run>
+static int query_entry(rto_context* c, const char* fn, int mode, bool pixels, const rto_frame* frame, bool tris, const In* in, int64_t n,
+                       Hit* hits, bool host, void* stream, Run run) {
+    if (!c) return RTO_E_INVALID;
+    int rc = query_check(c, fn, mode, n, in, hits);
+    if (rc != RTO_OK || n == 0) return rc;
+    if (pixels && !frame) return fail(c, RTO_E_INVALID, std::string(fn) + ": frame is NULL");
+    if (tris && (c->numNodes <= 0 || !c->d_triOffset || !c->d_tris))
+        return fail(c, RTO_E_NO_OCTREE, std::string(fn) + ": no leaf triangles resident (rto_build_leaf_triangles / rto_upload_leaf_triangles)");
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, std::string(fn) + ": no octree uploaded");
+    RTO_HIP(c, hipSetDevice(c->device));
+    if (!host) return run(in, hits, (hipStream_t)stream);
+    const size_t nIn = (size_t)n * (pixels ? 2 : 1);
+    BuildScratch scratch(c->stream);
+    In* d_in = nullptr;
+    Hit* d_hits = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_in, nIn));
+    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
+    RTO_HIP(c, hipMemcpyAsync(d_in, in, nIn * sizeof(In), hipMemcpyHostToDevice, c->stream));
+    if ((rc = run(d_in, d_hits, c->stream)) != RTO_OK) return rc;
+    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(Hit), hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
+    return RTO_OK;
 }
 
 extern "C" {
 
 int rto_query_rays_device(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_hit* d_hits, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_rays_device", mode, n, d_rays, d_hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_rays_device: no octree uploaded");
-    RTO_HIP(c, hipSetDevice(c->device));
-    return query_rays(c, mode, d_rays, n, d_hits, (hipStream_t)hip_stream);
+    return query_entry(c, "rto_query_rays_device", mode, false, nullptr, false, d_rays, n, d_hits, false, hip_stream,
+                       [=](const rto_ray* r, rto_hit* h, hipStream_t s) { return query_rays(c, mode, r, n, h, s); });
 }
 
 int rto_query_rays_host(rto_context* c, int mode, const rto_ray* rays, int64_t n, rto_hit* hits) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_rays_host", mode, n, rays, hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_rays_host: no octree uploaded");
-    RTO_HIP(c, hipSetDevice(c->device));
-    BuildScratch scratch(c->stream);
-    rto_ray* d_rays = nullptr;
-    rto_hit* d_hits = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_rays, (size_t)n));
-    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
-    RTO_HIP(c, hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rto_ray), hipMemcpyHostToDevice, c->stream));
-    if ((rc = query_rays(c, mode, d_rays, n, d_hits, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_hit), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return query_entry(c, "rto_query_rays_host", mode, false, nullptr, false, rays, n, hits, true, nullptr,
+                       [=](const rto_ray* r, rto_hit* h, hipStream_t s) { return query_rays(c, mode, r, n, h, s); });
 }
 
 int rto_query_pixels_device(rto_context* c, int mode, const rto_frame* frame, const int32_t* d_xy, int64_t n, rto_hit* d_hits, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_pixels_device", mode, n, d_xy, d_hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_pixels_device: frame is NULL");
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_pixels_device: no octree uploaded");
-    RTO_HIP(c, hipSetDevice(c->device));
-    return query_pixels(c, mode, frame, d_xy, n, d_hits, (hipStream_t)hip_stream);
+    return query_entry(c, "rto_query_pixels_device", mode, true, frame, false, d_xy, n, d_hits, false, hip_stream,
+                       [=](const int32_t* xy, rto_hit* h, hipStream_t s) { return query_pixels(c, mode, frame, xy, n, h, s); });
 }
 
 int rto_query_pixels_host(rto_context* c, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_hit* hits) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_pixels_host", mode, n, xy, hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_pixels_host: frame is NULL");
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_query_pixels_host: no octree uploaded");
-    RTO_HIP(c, hipSetDevice(c->device));
-    BuildScratch scratch(c->stream);
-    int32_t* d_xy = nullptr;
-    rto_hit* d_hits = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_xy, (size_t)n * 2));
-    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
-    RTO_HIP(c, hipMemcpyAsync(d_xy, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if ((rc = query_pixels(c, mode, frame, d_xy, n, d_hits, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_hit), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return query_entry(c, "rto_query_pixels_host", mode, true, frame, false, xy, n, hits, true, nullptr,
+                       [=](const int32_t* d_xy, rto_hit* h, hipStream_t s) { return query_pixels(c, mode, frame, d_xy, n, h, s); });
 }
 
 }  // extern "C"

@@ -73,104 +73,46 @@ __device__ __forceinline__ void store_tri_hit(rto_tri_hit* __restrict__ hits, in
     }
 }
 
-// ================================================================ canonical trees: the descriptor walk
-// k_query_desc's walk with the triangle render's interesting children: internal children and the leaf children that own triangles
-// (descriptor bits 24..31, k_desc_trimask), minus the 8 exact verdicts of child_fail_mask_fast (child_fail_mask_exact for a wave
-// holding a non-finite value) at the default clamps -- the render's box rule, whatever the mode, since no mode prunes by t.  A leaf
-// child is re-tested with slab_exact when popped, then its triangles d_triOffset[leaf] .. d_triOffset[leaf + 1] are tested by its
-// own lane (leaf = descFirstChild[parent's descriptor] + child).
-//   FIRST   children pop 7 .. 0; the pop count of a leaf is k_query_desc's 1 + 8 entered - (popcount(x) + 2 popcount(y) +
-//           4 popcount(z)); the first leaf with an accepted triangle ends the walk, a miss if it came past 512 pops.
-//   CLOSEST the ray's own octant first (a convenience: the tie rule is by index, the walk exhaustive).
-//   ANY     the same order, ends at the first leaf with an accepted triangle.
+// The triangle queries' leaf rule for desc_walk (rto_query.inc).  The candidate leaves of a descriptor are the ones
+// that own triangles (bits 24..31, k_desc_trimask); a popped leaf whose box passes has its triangles d_triOffset[leaf] ..
+// d_triOffset[leaf + 1] tested by its own lane.  No box is pruned by t (the header says why): every mode walks with the render's box
+// rule at the default clamps and CLOSEST visits every reachable triangle leaf -- in the ray's own octant order, a convenience only:
+// the tie rule is by index.
+struct TriRule {
+    static constexpr bool kPrune = false;
+    const int* __restrict__ descFirstChild;
+    const float* __restrict__ tris;
+    const int* __restrict__ triOffset;
+    TriBest B;
+    __device__ __forceinline__ TriRule(const int* dfc, const float* t, const int* off) : descFirstChild(dfc), tris(t), triOffset(off) {
+        B.t = 1e30f; B.u = B.v = 0.0f; B.tri = -1; B.leaf = -1;
+    }
+    __device__ __forceinline__ static unsigned leaves(unsigned dx) { return dx >> 24; }
+    __device__ __forceinline__ float closest() const { return 1e30f; }      // never read: kPrune is false
+    __device__ __forceinline__ bool leaf(const Ray& r, float tlo, float thi, float, float, int, int, int, int, int j, const unsigned* node) {
+        const int leaf = descFirstChild[*node] + j;
+        return tri_leaf(tris, triOffset[leaf], triOffset[leaf + 1], leaf, r, tlo, thi, B);
+    }
+};
+
+// Canonical trees: desc_walk under TriRule.  FIRST is the render's rule (trace_triangles' pop order and 512-pop cap).
 template <int QMODE, bool PIXELS>
 __global__ __launch_bounds__(kBlock) void k_triq_desc(RenderParams P, QuerySrc Q, rto_tri_hit* __restrict__ hits,
                                                       const uint2* __restrict__ desc, const int* __restrict__ descFirstChild,
                                                       const float* __restrict__ tris, const int* __restrict__ triOffset) {
     extern __shared__ uint2 lds_stack[];   // [wave][level][lane] entries, then [wave][level][lane] descriptor indices
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
-    const int levels = P.depth;
-    uint2* stk = lds_stack + (size_t)wave * levels * kWave + lane;
-    unsigned* stkNode = reinterpret_cast<unsigned*>(lds_stack + (size_t)waves * levels * kWave) + (size_t)wave * levels * kWave + lane;
+    uint2* stk;
+    unsigned* stkNode;
+    desc_stacks(lds_stack, P.depth, stk, stkNode);
     const int64_t i = Q.base + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const Geo G = geo_of(P);
-    const float kEps = __uint_as_float(1u), kBelow1e30 = __uint_as_float(0x7149f2c9u);
-
     Ray r;
     r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
     float tlo = 0.0f, thi = 0.0f;
-    bool active = false;
-    if (i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi)) {
-        float tNear, tFar, a0, a1, a2, a3, a4, a5;
-        active = slab_exact(G, r, 0, 0, 0, P.rootSize, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
-    }
-    const bool risky = active && !(__builtin_isfinite(r.ix) && __builtin_isfinite(r.iy) && __builtin_isfinite(r.iz) &&
-                                   __builtin_isfinite(r.ox) && __builtin_isfinite(r.oy) && __builtin_isfinite(r.oz) &&
-                                   __builtin_isfinite(r.dx) && __builtin_isfinite(r.dy) && __builtin_isfinite(r.dz));
-    const bool anyRisky = __builtin_amdgcn_ballot_w64(risky) != 0ull;
-    const unsigned sgnX = (unsigned)((int)__float_as_uint(r.ix) >> 31), sgnY = (unsigned)((int)__float_as_uint(r.iy) >> 31),
-                   sgnZ = (unsigned)((int)__float_as_uint(r.iz) >> 31);
-    const unsigned flip = QMODE == kQueryFirst ? 0u : ((r.dx < 0.0f ? 1u : 0u) | (r.dy < 0.0f ? 2u : 0u) | (r.dz < 0.0f ? 4u : 0u));
-
-    bool hit = false, enter = active;
-    TriBest B;
-    B.t = 1e30f; B.u = B.v = 0.0f; B.tri = -1; B.leaf = -1;
-    unsigned cur = 0, lvlPending = 0;
-    int cx = 0, cy = 0, cz = 0, bpos = P.depth - 1;
-    int entered = 0;
-    const int capEntered = kMaxTraversalSteps - 1 + 7 * P.depth;      // FIRST: 8 entered above this puts every later leaf past the cap
-    while (active) {
-        if (enter) {
-            entered++;
-            if (QMODE == kQueryFirst && 8 * entered > capEntered) break;
-            const uint2 d = desc[cur];
-            unsigned fail8;
-            if (anyRisky) fail8 = child_fail_mask_exact(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, cx, cy, cz, 1 << bpos);
-            else fail8 = child_fail_mask_fast<true, false>(G.gx, G.gy, G.gz, G.vs, r.ox, r.oy, r.oz, r.ix, r.iy, r.iz, sgnX, sgnY, sgnZ,
-                                                           cx, cy, cz, (float)(1 << bpos), kEps, kBelow1e30);
-            const unsigned im = (d.x >> 8) & 0xffu;
-            unsigned cand = ((d.x >> 24) | im) & ~fail8 & 0xffu;     // triangle leaves and internal children whose box the ray meets
-            if (QMODE != kQueryFirst) cand = flip_children(cand, flip);
-            stk[bpos * kWave] = make_uint2(cand | (im << 8), d.y);
-            stkNode[bpos * kWave] = cur;
-            lvlPending = cand ? (lvlPending | (1u << bpos)) : (lvlPending & ~(1u << bpos));
-            enter = false;
-        }
-        if (lvlPending == 0) break;
-        const int Lb = __builtin_ctz(lvlPending);                  // the deepest node with children left: LIFO
-        const uint2 e = stk[Lb * kWave];
-        const int k = QMODE == kQueryFirst ? 31 - __builtin_clz(e.x & 0xffu) : __builtin_ctz(e.x & 0xffu);
-        const unsigned left = e.x ^ (1u << k);
-        stk[Lb * kWave].x = left;
-        if ((left & 0xffu) == 0) lvlPending &= ~(1u << Lb);
-        const int j = k ^ (int)flip;
-        const unsigned bit = 1u << j;
-        const int h = 1 << Lb, keep = ~(2 * h - 1);
-        const int chx = (cx & keep) + ((j & 1) ? h : 0), chy = (cy & keep) + ((j & 2) ? h : 0), chz = (cz & keep) + ((j & 4) ? h : 0);
-        const unsigned im = (e.x >> 8) & 0xffu;
-        if (im & bit) {
-            cur = e.y + (unsigned)__builtin_popcount(im & (bit - 1u));
-            cx = chx; cy = chy; cz = chz; bpos = Lb - 1; enter = true;
-            continue;
-        }
-        {
-            float tNear, tFar, a0, a1, a2, a3, a4, a5;
-            if (!(slab_exact(G, r, chx, chy, chz, h, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f))) continue;
-        }
-        const int leaf = descFirstChild[stkNode[Lb * kWave]] + j;
-        const bool got = tri_leaf(tris, triOffset[leaf], triOffset[leaf + 1], leaf, r, tlo, thi, B);
-        if (QMODE == kQueryClosest) {
-            hit = hit || got;
-        } else if (got) {
-            hit = true;
-            if (QMODE == kQueryFirst) {
-                const int pops = 1 + 8 * entered - (__builtin_popcount(chx) + 2 * __builtin_popcount(chy) + 4 * __builtin_popcount(chz));
-                if (pops > kMaxTraversalSteps) hit = false;        // the render's loop ended before this pop
-            }
-            break;
-        }
-    }
-    if (i < Q.n) store_tri_hit(hits, i, hit, B, r, tris);
+    const bool valid = i < Q.n && query_ray<PIXELS>(P, Q, i, r, tlo, thi);
+    TriRule R(descFirstChild, tris, triOffset);
+    const bool hit = desc_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode, R);
+    if (i < Q.n) store_tri_hit(hits, i, hit, R.B, r, tris);
 }
 
 // ================================================================ any array, or RTO_KERNEL_GENERIC: node by node
@@ -221,34 +163,12 @@ __global__ __launch_bounds__(kQueryNodesBlock) void k_triq_nodes(RenderParams P,
 
 // ---------------------------------------------------------------- host side
 template <bool PIXELS>
-static int launch_tri_query(rto_context* c, int mode, const RenderParams& P, QuerySrc Q, rto_tri_hit* hits, hipStream_t s) {
-    const bool desc = c->canonical && c->numInternal > 0 && c->kernelMode != RTO_KERNEL_GENERIC;
-    const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * (sizeof(uint2) + sizeof(unsigned));   // <= 61,440 B (depth 20)
-    const size_t ldsN = (size_t)kStackCap * kQueryNodesBlock * sizeof(int);
-    for (int64_t off = 0; off < Q.n; off += kQueryChunk) {
-        Q.base = off;
-        const int64_t rays = std::min(Q.n - off, kQueryChunk);
-        const dim3 grid((unsigned)((rays + kBlock - 1) / kBlock)), block(kBlock);
-        const dim3 gridN((unsigned)((rays + kQueryNodesBlock - 1) / kQueryNodesBlock)), blockN(kQueryNodesBlock);
-        if (desc) {
-            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_triq_desc<kQueryFirst, PIXELS>), grid, block, lds, s, P, Q, hits, c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset);
-            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_triq_desc<kQueryClosest, PIXELS>), grid, block, lds, s, P, Q, hits, c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset);
-            else hipLaunchKernelGGL((k_triq_desc<kQueryAny, PIXELS>), grid, block, lds, s, P, Q, hits, c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset);
-        } else {
-            if (mode == RTO_QUERY_FIRST) hipLaunchKernelGGL((k_triq_nodes<kQueryFirst, PIXELS>), gridN, blockN, ldsN, s, P, Q, hits, c->d_nodes, c->d_tris, c->d_triOffset);
-            else if (mode == RTO_QUERY_CLOSEST) hipLaunchKernelGGL((k_triq_nodes<kQueryClosest, PIXELS>), gridN, blockN, ldsN, s, P, Q, hits, c->d_nodes, c->d_tris, c->d_triOffset);
-            else hipLaunchKernelGGL((k_triq_nodes<kQueryAny, PIXELS>), gridN, blockN, ldsN, s, P, Q, hits, c->d_nodes, c->d_tris, c->d_triOffset);
-        }
-        RTO_HIP(c, hipGetLastError());
-    }
-    return RTO_OK;
-}
-
-// The checks every entry shares after query_check: something to trace against.
-static int tri_query_ready(rto_context* c, const char* fn) {
-    if (c->numNodes <= 0 || !c->d_triOffset || !c->d_tris)
-        return fail(c, RTO_E_NO_OCTREE, std::string(fn) + ": no leaf triangles resident (rto_build_leaf_triangles / rto_upload_leaf_triangles)");
-    return RTO_OK;
+static int launch_tri_query(rto_context* c, int mode, const RenderParams& P, const QuerySrc& Q0, rto_tri_hit* hits, hipStream_t s) {
+    return launch_query(c, mode, P.depth, Q0, [&](auto m, bool desc, dim3 grid, dim3 block, size_t lds, const QuerySrc& Q) {
+        constexpr int M = decltype(m)::value;
+        if (desc) hipLaunchKernelGGL((k_triq_desc<M, PIXELS>), grid, block, lds, s, P, Q, hits, c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset);
+        else hipLaunchKernelGGL((k_triq_nodes<M, PIXELS>), grid, block, lds, s, P, Q, hits, c->d_nodes, c->d_tris, c->d_triOffset);
+    });
 }
 
 static int tri_query_rays(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_tri_hit* d_hits, hipStream_t s) {
@@ -271,60 +191,24 @@ static int tri_query_pixels(rto_context* c, int mode, const rto_frame* f, const 
 extern "C" {
 
 int rto_query_triangles_device(rto_context* c, int mode, const rto_ray* d_rays, int64_t n, rto_tri_hit* d_hits, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_triangles_device", mode, n, d_rays, d_hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if ((rc = tri_query_ready(c, "rto_query_triangles_device")) != RTO_OK) return rc;
-    RTO_HIP(c, hipSetDevice(c->device));
-    return tri_query_rays(c, mode, d_rays, n, d_hits, (hipStream_t)hip_stream);
+    return query_entry(c, "rto_query_triangles_device", mode, false, nullptr, true, d_rays, n, d_hits, false, hip_stream,
+                       [=](const rto_ray* r, rto_tri_hit* h, hipStream_t s) { return tri_query_rays(c, mode, r, n, h, s); });
 }
 
 int rto_query_triangles_host(rto_context* c, int mode, const rto_ray* rays, int64_t n, rto_tri_hit* hits) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_triangles_host", mode, n, rays, hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if ((rc = tri_query_ready(c, "rto_query_triangles_host")) != RTO_OK) return rc;
-    RTO_HIP(c, hipSetDevice(c->device));
-    BuildScratch scratch(c->stream);
-    rto_ray* d_rays = nullptr;
-    rto_tri_hit* d_hits = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_rays, (size_t)n));
-    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
-    RTO_HIP(c, hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(rto_ray), hipMemcpyHostToDevice, c->stream));
-    if ((rc = tri_query_rays(c, mode, d_rays, n, d_hits, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_tri_hit), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return query_entry(c, "rto_query_triangles_host", mode, false, nullptr, true, rays, n, hits, true, nullptr,
+                       [=](const rto_ray* r, rto_tri_hit* h, hipStream_t s) { return tri_query_rays(c, mode, r, n, h, s); });
 }
 
 int rto_query_triangle_pixels_device(rto_context* c, int mode, const rto_frame* frame, const int32_t* d_xy, int64_t n,
                                      rto_tri_hit* d_hits, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_triangle_pixels_device", mode, n, d_xy, d_hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_triangle_pixels_device: frame is NULL");
-    if ((rc = tri_query_ready(c, "rto_query_triangle_pixels_device")) != RTO_OK) return rc;
-    RTO_HIP(c, hipSetDevice(c->device));
-    return tri_query_pixels(c, mode, frame, d_xy, n, d_hits, (hipStream_t)hip_stream);
+    return query_entry(c, "rto_query_triangle_pixels_device", mode, true, frame, true, d_xy, n, d_hits, false, hip_stream,
+                       [=](const int32_t* xy, rto_tri_hit* h, hipStream_t s) { return tri_query_pixels(c, mode, frame, xy, n, h, s); });
 }
 
 int rto_query_triangle_pixels_host(rto_context* c, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_tri_hit* hits) {
-    if (!c) return RTO_E_INVALID;
-    int rc = query_check(c, "rto_query_triangle_pixels_host", mode, n, xy, hits);
-    if (rc != RTO_OK || n == 0) return rc;
-    if (!frame) return fail(c, RTO_E_INVALID, "rto_query_triangle_pixels_host: frame is NULL");
-    if ((rc = tri_query_ready(c, "rto_query_triangle_pixels_host")) != RTO_OK) return rc;
-    RTO_HIP(c, hipSetDevice(c->device));
-    BuildScratch scratch(c->stream);
-    int32_t* d_xy = nullptr;
-    rto_tri_hit* d_hits = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_xy, (size_t)n * 2));
-    RTO_HIP(c, scratch.alloc(&d_hits, (size_t)n));
-    RTO_HIP(c, hipMemcpyAsync(d_xy, xy, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if ((rc = tri_query_pixels(c, mode, frame, d_xy, n, d_hits, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rto_tri_hit), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return query_entry(c, "rto_query_triangle_pixels_host", mode, true, frame, true, xy, n, hits, true, nullptr,
+                       [=](const int32_t* d_xy, rto_tri_hit* h, hipStream_t s) { return tri_query_pixels(c, mode, frame, d_xy, n, h, s); });
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -17,17 +18,31 @@ def _hipcc():
     return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 
 
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
+_ASM = []
+
+
+def built_asm():
+    """The assembly of rto_api.hip under the product's own flags, compiled once per test run; None where there is no hipcc."""
     hipcc = _hipcc()
     if not hipcc:
+        return None
+    if not _ASM:
+        from ray_tracing_octrees_amd import _build
+        flags = [f for f in _build.HIP_FLAGS if f not in ("-fPIC", "-shared")]           # the product's own flags
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "rto.s")
+            subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, "rto_api.hip"), "-o", out],
+                           check=True, stderr=subprocess.DEVNULL)
+            _ASM.append(open(out).read())
+    return _ASM[0]
+
+
+@pytest.fixture(scope="module")
+def asm():
+    text = built_asm()
+    if text is None:
         pytest.skip("no hipcc in this environment")
-    from ray_tracing_octrees_amd import _build
-    out = tmp_path_factory.mktemp("isa") / "rto.s"
-    flags = [f for f in _build.HIP_FLAGS if f not in ("-fPIC", "-shared")]           # the product's own flags
-    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, "rto_api.hip"), "-o", str(out)],
-                   check=True, stderr=subprocess.DEVNULL)
-    return out.read_text()
+    return text
 
 
 def kernel_meta(asm_text):
@@ -161,7 +176,7 @@ def test_tie_update_of_the_closest_hit_kernel_has_no_lane_mask_operand():
 
 def test_no_short_circuit_updates_with_calls_inside_divergent_loops():
     """The shape that was miscompiled -- `a || (b && c && f(..))` deciding an update -- must not reappear in device code."""
-    for name in ("rto_device.hip.h",):
+    for name in ("rto_device.hip.h", "rto_query.inc", "rto_tri_query.inc", "rto_lit.inc"):
         src = open(os.path.join(CSRC, name)).read()
         src = re.sub(r"//[^\n]*", "", src)
         bad = re.findall(r"if\s*\([^;{}]*\|\|\s*\([^;{}()]*&&[^;{}()]*&&[^;{}]*\w+\([^;{}]*\)\s*\)\s*\)\s*\{?[^;]*=", src)

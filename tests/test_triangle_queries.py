@@ -160,20 +160,10 @@ def test_tri_hit_layout_and_exports():
 def test_triangle_query_kernels_keep_their_budgets():
     """The built assembly (the product's flags): the 12 k_triq_* kernels without scratch instructions, spills or v_mfma; the
     descriptor kernels within DESIGN.md section 10's VGPR budget."""
-    import shutil
-    import subprocess
-    import tempfile
     import test_isa_contract as isa
-    from ray_tracing_octrees_amd import _build
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if not hipcc:
+    asm = isa.built_asm()
+    if asm is None:
         pytest.fail("no hipcc: the budget cannot be checked")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "rto.s")
-        flags = [f for f in _build.HIP_FLAGS if f not in ("-fPIC", "-shared")]
-        subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(isa.CSRC, "rto_api.hip"), "-o", out],
-                       check=True, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
     meta = isa.kernel_meta(asm)
     names = [k for k in meta if "k_triq_" in k]
     assert len(names) == 12, names                                    # {desc, nodes} x {FIRST, CLOSEST, ANY} x {rays, pixels}

@@ -185,16 +185,9 @@ def test_edit_kernels_keep_their_budgets():
     """The built assembly (the product's flags): both k_edit_brushes forms without scratch, spills or v_mfma, within the VGPR budget;
     the 16-byte form moves rows with dwordx4 loads and stores."""
     import test_isa_contract as isa
-    from ray_tracing_octrees_amd import _build
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if not hipcc:
+    asm = isa.built_asm()
+    if asm is None:
         pytest.fail("no hipcc: the budget cannot be checked")
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "rto.s")
-        flags = [f for f in _build.HIP_FLAGS if f not in ("-fPIC", "-shared")]
-        subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(isa.CSRC, "rto_api.hip"), "-o", out],
-                       check=True, stderr=subprocess.DEVNULL)
-        asm = open(out).read()
     meta = isa.kernel_meta(asm)
     names = [k for k in meta if "k_edit_brushes" in k]
     assert len(names) == 2, names
