@@ -613,6 +613,45 @@ int  rto_render_lit_host(rto_context* ctx, const rto_frame* frame, const rto_lig
  * (sqrt(u) cos phi, sqrt(u) sin phi, sqrt(1 - u)) computed in double and rounded once to float.  Pure host function. */
 int  rto_ao_directions(float out[192]);
 
+/* ---- lit render of the triangle surface -----------------------------------
+ * rto_render_triangles_device's frame with a shadow ray and ambient occlusion per hit pixel, computed on the device in one stream
+ * (DESIGN.md section 14): the lit render above on the resident leaf triangles.  rto_lighting is the lit render's.  All arithmetic
+ * is float32, one IEEE operation per operator, in the order written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  Rule:
+ *   primary hit   the FIRST triangle query on the frame's pixel ray, window (0, 1e30): rto_query_triangle_pixels_*'s record (t,
+ *                 triangle, owning leaf, u, v, and n = the stored face normal, negated when dot(n, d) > 0).  This is
+ *                 rto_render_triangles_device's hit.  Like the queries, the frame ignores rto_update_frustum.
+ *   ndotl         max(0, dot(n, lightNeg)), glm's max ((a < b) ? b : a), lightNeg = -normalize(light_dir) as rto_render_lit_* has it.
+ *   origin        p = o + d t; eps = voxelSize * 1e-3f + 2^-18 * max(|p.x|, |p.y|, |p.z|); h = eps - dot(p - v0, n) with v0 the
+ *                 triangle's first vertex; so = p + n h (the triangle render's shadow origin).  Shadow and AO rays start there.
+ *   shadow        (shadow != 0, ndotl > 0) one ray from so along lightNeg, window (0, 1e30), the ANY triangle rule: S = 0 when it
+ *                 hits, else 1.
+ *   AO            (K = ao_samples in 1..64) K rays from so, window (0, ao_radius], the ANY triangle rule.  T, h and the entry
+ *                 t = T[(h + (64 s) / K) & 63] of sample s are the lit render's; x' = t.x negated when bit 6 of h is set, y' = t.y
+ *                 negated when bit 7 is set, z' = t.z.  The frame around n (Duff et al., "Building an Orthonormal Basis,
+ *                 Revisited"): s = (n.z < 0) ? -1 : 1; a = -1 / (s + n.z); b = (n.x * n.y) * a;
+ *                 U = (1 + ((s * n.x) * n.x) * a, s * b, (-s) * n.x); V = (b, s + (n.y * n.y) * a, -n.y); per component c:
+ *                 dir[c] = (x' * U[c] + y' * V[c]) + z' * n[c].  The direction is not renormalised (a stored normal is unit only
+ *                 to rounding) and the window is in the ray's own parameter, as in every query.  occ = rays that hit;
+ *                 A = (float)(K - occ) / (float)K.
+ *   misses        a shadow or AO ray whose origin or direction has a NaN or infinite component is a miss (stored normals that
+ *                 are zero, huge or not finite are accepted input).
+ *   otherwise     S = A = 1 (K = 0, no shadow ray cast).
+ *   colour, vis   the lit render's: d = S ? ndotl : 0, amb = 0.1f * A, RGBA = (1.0f d + amb, 0.8f d + amb, 0.6f d + amb, 1); a miss
+ *                 is (0, 0, 0, 1); vis = -1 for a miss, else occ + 256 * (shadow ray cast and blocked).
+ * shadow = 0, K = 0 and light_dir = (-1, -1, -1) give rto_render_triangles_device(shadow = 0)'s frame (culling off) bit for bit;
+ * shadow = 1, K = 0 gives its shadow = 1 frame on every pixel whose shadow ray has the same verdict under FIRST (the render's walk,
+ * with its 512-pop cap) and ANY (no cap).
+ * Whole frames only.  The errors are rto_render_lit_*'s, checked first and in its order (RTO_E_INVALID, RTO_E_NO_OCTREE: nothing
+ * uploaded, RTO_E_UNSUPPORTED: a non-canonical array of more than one node), then RTO_E_NO_OCTREE when no leaf triangles are
+ * resident (rto_build_leaf_triangles / rto_upload_leaf_triangles).  A tree that is one leaf owns no triangles: every pixel is a
+ * miss.  rto_set_kernel does not apply.  The device form is asynchronous on hip_stream and shares the lit render's work buffers
+ * on the context (same rules: a frame larger than any before allocates them and must not be stream-captured; lit frames of either
+ * kind on different streams of one context must not run at the same time). */
+int  rto_render_lit_triangles_device(rto_context* ctx, const rto_frame* frame, const rto_lighting* lighting, void* d_rgba,
+                                     int32_t* d_vis /* may be NULL */, void* hip_stream);
+int  rto_render_lit_triangles_host(rto_context* ctx, const rto_frame* frame, const rto_lighting* lighting, float* host_rgba,
+                                   int32_t* host_vis /* may be NULL */);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

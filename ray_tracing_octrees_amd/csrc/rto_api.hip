@@ -2694,3 +2694,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_edit.inc"
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"
+#include "rto_tri_lit.inc"

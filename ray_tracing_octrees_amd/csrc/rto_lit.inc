@@ -264,17 +264,12 @@ static int lit_check(rto_context* c, const char* fn, const rto_frame* f, const r
     return RTO_OK;
 }
 
-static int render_lit(rto_context* c, const rto_frame* f, const rto_lighting* Lt, float4* d_rgba, int32_t* d_vis, hipStream_t s) {
-    RenderParams P;
-    int rc = fill_params(c, f, nullptr, P, s);
-    if (rc != RTO_OK) return rc;
-    const rtmath::vec3 l = rtmath::normalize(rtmath::vec3(Lt->light_dir[0], Lt->light_dir[1], Lt->light_dir[2]));   // fill_params' order
-    P.lightNeg[0] = -l.x; P.lightNeg[1] = -l.y; P.lightNeg[2] = -l.z;
-    for (int a = 0; a < 3; a++) { const volatile float q = 1.0f / P.lightNeg[a]; P.lightInv[a] = q; }
-    const size_t pixels = (size_t)P.W * (size_t)P.H;                 // lit_check bounded pixels * (K + 1) + 128 below 2^32
+// The work buffers of a lit frame of `pixels` pixels (32-byte records, verdict counters, the hit count), kept on the context and
+// grown with the frame; the triangle form (rto_tri_lit.inc) shares them: its records are 32 bytes too.
+static int lit_reserve(rto_context* c, const char* fn, size_t pixels, hipStream_t s) {
     if (c->litCap < pixels || !c->d_litCount) {
         if (stream_is_capturing(s))
-            return fail(c, RTO_E_UNSUPPORTED, "rto_render_lit_device: a larger frame allocates its work buffers; render one such frame "
+            return fail(c, RTO_E_UNSUPPORTED, std::string(fn) + ": a larger frame allocates its work buffers; render one such frame "
                                               "before hipStreamBeginCapture");
         (void)hipFree(c->d_litRec); c->d_litRec = nullptr;           // hipFree waits for the device: no frame still reads them
         (void)hipFree(c->d_litAcc); c->d_litAcc = nullptr;
@@ -284,6 +279,18 @@ static int render_lit(rto_context* c, const rto_frame* f, const rto_lighting* Lt
         if (!c->d_litCount) RTO_HIP(c, hipMalloc(&c->d_litCount, sizeof(unsigned)));
         c->litCap = pixels;
     }
+    return RTO_OK;
+}
+
+static int render_lit(rto_context* c, const rto_frame* f, const rto_lighting* Lt, float4* d_rgba, int32_t* d_vis, hipStream_t s) {
+    RenderParams P;
+    int rc = fill_params(c, f, nullptr, P, s);
+    if (rc != RTO_OK) return rc;
+    const rtmath::vec3 l = rtmath::normalize(rtmath::vec3(Lt->light_dir[0], Lt->light_dir[1], Lt->light_dir[2]));   // fill_params' order
+    P.lightNeg[0] = -l.x; P.lightNeg[1] = -l.y; P.lightNeg[2] = -l.z;
+    for (int a = 0; a < 3; a++) { const volatile float q = 1.0f / P.lightNeg[a]; P.lightInv[a] = q; }
+    const size_t pixels = (size_t)P.W * (size_t)P.H;                 // lit_check bounded pixels * (K + 1) + 128 below 2^32
+    if ((rc = lit_reserve(c, "rto_render_lit_device", pixels, s)) != RTO_OK) return rc;
     LitArgs A;
     A.rec = c->d_litRec; A.acc = c->d_litAcc; A.count = c->d_litCount;
     A.rgba = d_rgba; A.vis = d_vis;
@@ -304,6 +311,24 @@ static int render_lit(rto_context* c, const rto_frame* f, const rto_lighting* Lt
         hipLaunchKernelGGL(k_lit_secondary, dim3((unsigned)blocks), dim3(kBlock), lds, s, P, A, c->d_desc);
         RTO_HIP(c, hipGetLastError());
     }
+    return RTO_OK;
+}
+
+// A *_host entry of a lit render: render(d_rgba, d_vis) on the context's stream into stream-ordered scratch, copied out, waited for.
+template <class Render>
+static int lit_frame_to_host(rto_context* c, const rto_frame* frame, float* host_rgba, int32_t* host_vis, Render render) {
+    int rc;
+    RTO_HIP(c, hipSetDevice(c->device));
+    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
+    BuildScratch scratch(c->stream);
+    float4* d_rgba = nullptr;
+    int32_t* d_vis = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_rgba, pixels));
+    if (host_vis) RTO_HIP(c, scratch.alloc(&d_vis, pixels));
+    if ((rc = render(d_rgba, d_vis)) != RTO_OK) return rc;
+    RTO_HIP(c, hipMemcpyAsync(host_rgba, d_rgba, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (host_vis) RTO_HIP(c, hipMemcpyAsync(host_vis, d_vis, pixels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
     return RTO_OK;
 }
 
@@ -330,18 +355,7 @@ int rto_render_lit_host(rto_context* c, const rto_frame* frame, const rto_lighti
     if (!c) return RTO_E_INVALID;
     int rc = lit_check(c, "rto_render_lit_host", frame, lighting, host_rgba);
     if (rc != RTO_OK) return rc;
-    RTO_HIP(c, hipSetDevice(c->device));
-    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
-    BuildScratch scratch(c->stream);
-    float4* d_rgba = nullptr;
-    int32_t* d_vis = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_rgba, pixels));
-    if (host_vis) RTO_HIP(c, scratch.alloc(&d_vis, pixels));
-    if ((rc = render_lit(c, frame, lighting, d_rgba, d_vis, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(host_rgba, d_rgba, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (host_vis) RTO_HIP(c, hipMemcpyAsync(host_vis, d_vis, pixels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return lit_frame_to_host(c, frame, host_rgba, host_vis, [=](float4* d_rgba, int32_t* d_vis) { return render_lit(c, frame, lighting, d_rgba, d_vis, c->stream); });
 }
 
 }  // extern "C"

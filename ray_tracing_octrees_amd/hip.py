@@ -39,6 +39,7 @@ SYMBOLS = (
     "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
     "rto_edit_voxels", "rto_download_voxels", "rto_last_edit_ms", "rto_brush_quantize",
     "rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions",
+    "rto_render_lit_triangles_device", "rto_render_lit_triangles_host",
     "rto_voxelize_mesh", "rto_last_voxelize_ms",
 )
 SPLIT_MAX_FRAMES = 32
@@ -327,6 +328,8 @@ def load():
     L.rto_brush_quantize.argtypes = [vp, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rto_render_lit_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp, vp]
     L.rto_render_lit_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp]
+    L.rto_render_lit_triangles_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp, vp]
+    L.rto_render_lit_triangles_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp]
     L.rto_ao_directions.argtypes = [vp]
     L.rto_voxelize_mesh.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(VoxelizeParams), C.POINTER(VoxelizeResult)]
     L.rto_last_voxelize_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -645,6 +648,22 @@ class Context:
         """Asynchronous: the lit frame into d_rgba (W*H*16 bytes) and, if d_vis, the visibility into d_vis (W*H int32)."""
         self._check(self._L.rto_render_lit_device(self._h, C.byref(frame), C.byref(lighting), C.c_void_p(d_rgba) if d_rgba else None,
                                                   C.c_void_p(d_vis) if d_vis else None, C.c_void_p(stream) if stream else None))
+
+    def render_lit_triangles_host(self, frame: Frame, lighting: Lighting | None = None, vis: bool = False, **kw):
+        """The triangle render's frame with a shadow ray and ambient occlusion (rto_render_lit_triangles_host); arguments and
+        result as render_lit_host."""
+        L = lighting if lighting is not None else make_lighting(**kw)
+        out = np.empty((frame.height, frame.width, 4), np.float32)
+        v = np.empty((frame.height, frame.width), np.int32) if vis else None
+        self._check(self._L.rto_render_lit_triangles_host(self._h, C.byref(frame), C.byref(L), out.ctypes.data,
+                                                          v.ctypes.data if vis else None))
+        return (out, v) if vis else out
+
+    def render_lit_triangles_device(self, frame: Frame, lighting: Lighting, d_rgba: int, d_vis: int = 0, stream: int = 0):
+        """Asynchronous: the lit triangle frame into d_rgba (W*H*16 bytes) and, if d_vis, the visibility into d_vis (W*H int32)."""
+        self._check(self._L.rto_render_lit_triangles_device(self._h, C.byref(frame), C.byref(lighting),
+                                                            C.c_void_p(d_rgba) if d_rgba else None, C.c_void_p(d_vis) if d_vis else None,
+                                                            C.c_void_p(stream) if stream else None))
 
     @staticmethod
     def ao_directions() -> np.ndarray:

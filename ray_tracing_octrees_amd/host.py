@@ -121,6 +121,8 @@ def load():
     L.rtoh_rt_render_scene_lit.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int,
                                            C.c_float, C.c_uint32]
     L.rtoh_rt_render_scene_lit.restype = None
+    L.rtoh_rt_render_surface_lit.argtypes = L.rtoh_rt_render_scene_lit.argtypes
+    L.rtoh_rt_render_surface_lit.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
     L.rtoh_rt_intersect_triangles.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp, _vp]
@@ -388,6 +390,14 @@ class RayTracerBVH:
         ld = (C.c_float * 3)(*[_f(x) for x in lightDir])
         load().rtoh_rt_render_scene_lit(self._h, camera._h, width, height, _f(aspect), _f(fovDeg), ld, 1 if shadow else 0,
                                         int(aoSamples), _f(aoRadius), int(seed) & 0xFFFFFFFF)
+
+    def renderSurfaceLit(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, lightDir=(-1.0, -1.0, -1.0),
+                         shadow: bool = True, aoSamples: int = 0, aoRadius: float = 1.0, seed: int = 0):
+        """Addition: RayTracerBVH::renderSurfaceLit -- renderSceneTriangles' frame lit the same way (DESIGN.md section 14); needs
+        buildLeafTriangles().  Without triangles resident there is no frame and lastError says why."""
+        ld = (C.c_float * 3)(*[_f(x) for x in lightDir])
+        load().rtoh_rt_render_surface_lit(self._h, camera._h, width, height, _f(aspect), _f(fovDeg), ld, 1 if shadow else 0,
+                                          int(aoSamples), _f(aoRadius), int(seed) & 0xFFFFFFFF)
 
     def framebuffer(self) -> np.ndarray | None:
         w, h = C.c_int(), C.c_int()

@@ -44,6 +44,7 @@ struct HipApi {
     decltype(&rto_download_leaf_triangles) download_leaf_triangles = nullptr;
     decltype(&rto_download_nodes) download_nodes = nullptr;
     decltype(&rto_render_lit_host) render_lit_host = nullptr;
+    decltype(&rto_render_lit_triangles_host) render_lit_triangles_host = nullptr;
     decltype(&rto_voxelize_mesh) voxelize_mesh = nullptr;
     std::string error;
 
@@ -99,6 +100,7 @@ struct HipApi {
         download_leaf_triangles = reinterpret_cast<decltype(download_leaf_triangles)>(sym("rto_download_leaf_triangles"));
         download_nodes = reinterpret_cast<decltype(download_nodes)>(sym("rto_download_nodes"));
         render_lit_host = reinterpret_cast<decltype(render_lit_host)>(sym("rto_render_lit_host"));
+        render_lit_triangles_host = reinterpret_cast<decltype(render_lit_triangles_host)>(sym("rto_render_lit_triangles_host"));
         voxelize_mesh = reinterpret_cast<decltype(voxelize_mesh)>(sym("rto_voxelize_mesh"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
@@ -329,6 +331,14 @@ void RayTracerBVH::renderSceneTriangles(const Camera& camera, int width, int hei
 }
 
 void RayTracerBVH::renderSceneLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting) {
+    renderLit(camera, width, height, aspect, fovDeg, lighting, false);
+}
+
+void RayTracerBVH::renderSurfaceLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting) {
+    renderLit(camera, width, height, aspect, fovDeg, lighting, true);
+}
+
+void RayTracerBVH::renderLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting, bool surface) {
     if (!m_computeInited || !m_computeOk) {
         std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
         return;
@@ -349,9 +359,11 @@ void RayTracerBVH::renderSceneLit(const Camera& camera, int width, int height, f
     L.reserved = 0;
     m_frameW = m_frameH = 0; m_frameStale = false;
     m_frame.resize(static_cast<size_t>(width) * height * 4);
-    if (api().render_lit_host(m_ctx, &f, &L, m_frame.data(), nullptr) != RTO_OK) {
+    const int rc = surface ? api().render_lit_triangles_host(m_ctx, &f, &L, m_frame.data(), nullptr)
+                           : api().render_lit_host(m_ctx, &f, &L, m_frame.data(), nullptr);
+    if (rc != RTO_OK) {
         m_lastError = api().last_error(m_ctx);
-        std::cerr << "[RayTracerBVH] lit render failed: " << m_lastError << std::endl;
+        std::cerr << "[RayTracerBVH] lit " << (surface ? "surface " : "") << "render failed: " << m_lastError << std::endl;
         m_frame.clear();
         return;
     }

@@ -127,6 +127,9 @@ public:
     // renderSceneCompute's frame with a shadow ray and ambient occlusion per hit pixel (rto_render_lit_host): same framebuffer().
     // The whole octree casts shadows, whatever the frustum culling.  With setDevices(n > 1) it renders on the first GPU alone.
     void renderSceneLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting);
+    // renderSceneTriangles' frame (the leaf triangles' surface) lit the same way (rto_render_lit_triangles_host; DESIGN.md section
+    // 14).  Needs buildLeafTriangles(); without triangles resident it fails as intersectTriangles / pickSurface do: no frame, lastError set.
+    void renderSurfaceLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting);
     // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
@@ -177,6 +180,7 @@ public:
     const std::string& lastError() const { return m_lastError; }
 
 private:
+    void renderLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting, bool surface);
     bool render(const Camera& camera, int width, int height, float aspect, float fovDeg);
 
     OctreeNode* m_octreeRoot;

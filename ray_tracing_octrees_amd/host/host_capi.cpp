@@ -176,6 +176,16 @@ void rtoh_rt_render_scene_lit(RayTracerBVH* rt, const Camera* cam, int w, int h,
     L.seed = seed;
     rt->renderSceneLit(*cam, w, h, aspect, fovDeg, L);
 }
+void rtoh_rt_render_surface_lit(RayTracerBVH* rt, const Camera* cam, int w, int h, float aspect, float fovDeg, const float lightDir[3],
+                                int shadow, int aoSamples, float aoRadius, uint32_t seed) {
+    Lighting L;
+    L.lightDir = rto_host::vec3(lightDir[0], lightDir[1], lightDir[2]);
+    L.shadow = shadow != 0;
+    L.aoSamples = aoSamples;
+    L.aoRadius = aoRadius;
+    L.seed = seed;
+    rt->renderSurfaceLit(*cam, w, h, aspect, fovDeg, L);
+}
 int64_t rtoh_rt_num_nodes(const RayTracerBVH* rt) { return (int64_t)rt->numNodes(); }
 int rtoh_rt_framebuffer(const RayTracerBVH* rt, float* out, int64_t capacityFloats, int* w, int* h) {
     *w = rt->frameWidth(); *h = rt->frameHeight();
