@@ -477,6 +477,49 @@ int  rto_query_triangle_pixels_device(rto_context* ctx, int mode, const rto_fram
                                       rto_tri_hit* d_hits, void* hip_stream);
 int  rto_query_triangle_pixels_host(rto_context* ctx, int mode, const rto_frame* frame, const int32_t* xy, int64_t n, rto_tri_hit* hits);
 
+/* ---- span queries ---------------------------------------------------------
+ * How much solid a ray passes through: the box queries above stop at one leaf, these visit every accepted leaf of the ray and sum.
+ * One rto_span per ray.  rto_ray, the pixel rays with window (0, 1e30), the NaN and t_min > t_max misses, the 16-byte alignment of
+ * the ray and span buffers, the error codes, the order of the checks, n == 0 and the disregard of the frustum state are those of the
+ * box queries.  There is no mode.
+ *
+ * Rule.  Window: t_lo = max(t_min, 0), t_hi = min(t_max, largest float below 1e30).
+ * Acceptance of a solid leaf is the box queries': its box and every ancestor's pass the float32 slab test (tNear <= tFar &&
+ * tFar > 0, glm min / max) with tNear < 1e30, and tIn = max(t_lo, tNear) satisfies tIn <= tFar and tIn <= t_hi.
+ * For an accepted leaf tOut = min(tFar, t_hi) (glm's min); its contribution is tOut - tIn, one float32 subtraction, >= 0.
+ * Visit order (a float sum has one): depth first, the children of a node in slots i ^ flip for i = 0 .. 7 ascending, with
+ * flip = (d.x < 0) | (d.y < 0) << 1 | (d.z < 0) << 2 -- a zero or -0.0 component is "not negative".  The order CLOSEST and ANY
+ * walk in.  No pop cap.
+ * Two identities hold on every ray: (t_enter, node, face) are bit for bit the CLOSEST record of rto_query_rays_* /
+ * rto_query_pixels_* for the same ray, and leaves > 0 exactly when ANY hits.  One restriction: the tie between leaves of equal
+ * tIn goes by the leaves' positions (at the highest bit in which they differ the greater octant digit x | y << 1 | z << 2 wins),
+ * which is the LIFO pop order on every array whose child slots are the octants of the children's boxes -- every octree this
+ * library builds, in any numbering.  On an uploaded array with other slots the CLOSEST query breaks such ties by its own pop
+ * order, and (node, face) may then differ from it on rays with a tie; t_enter and everything else still agree.
+ * RTO_E_UNSUPPORTED: an uploaded non-canonical array whose walk in a ray's octant order (not the slot order rto_upload_octree
+ * bounds) could hold more than 141 stack entries -- chains of more than 20 levels; such an array stays resident and every other
+ * entry serves it.
+ * A miss -- no accepted leaf, NaN input, t_min > t_max, a pixel outside the frame -- is length 0, t_enter 1e30, t_exit 1e30,
+ * leaves 0, node -1, face -1.
+ * `leaves` counts octree leaves, not walls: a uniform solid region is one large leaf, a wall of depth-max voxels is many.  A run
+ * count is deliberately absent: on contiguous leaves tOut of one and tIn of the next are equal as real numbers only, so a merge
+ * rule on floats would split runs by one ulp near box edges; `length` has no such discontinuity. */
+typedef struct rto_span {           /* 32 bytes */
+    float   length;                 /* sum of the contributions, float32, accumulated in visit order from 0.0f; in units of d */
+    float   t_enter;                /* least tIn over the accepted leaves; 1e30f for a miss */
+    float   t_exit;                 /* greatest tOut over the accepted leaves; 1e30f for a miss */
+    int32_t leaves;                 /* number of accepted leaves */
+    int32_t node;                   /* CLOSEST's leaf for the same ray: least tIn, ties to the leaf the LIFO order pops first; -1 = miss */
+    int32_t face;                   /* its entry face, as rto_hit.face; -1 = none or miss */
+    int32_t reserved[2];            /* 0 */
+} rto_span;
+
+int  rto_query_spans_device(rto_context* ctx, const rto_ray* d_rays, int64_t n, rto_span* d_spans, void* hip_stream);
+int  rto_query_spans_host(rto_context* ctx, const rto_ray* rays, int64_t n, rto_span* spans);
+int  rto_query_span_pixels_device(rto_context* ctx, const rto_frame* frame, const int32_t* d_xy, int64_t n, rto_span* d_spans,
+                                  void* hip_stream);
+int  rto_query_span_pixels_host(rto_context* ctx, const rto_frame* frame, const int32_t* xy, int64_t n, rto_span* spans);
+
 /* ---- voxel edits ----------------------------------------------------------
  * Brushes carve (-> EMPTY = 0) or fill (-> FILLED = 1) the voxel grid rto_build_octree keeps in HBM; the octree is then rebuilt
  * from that grid on the GPU, with no host copy.  Rule, exact in integers at 1/64 voxel:

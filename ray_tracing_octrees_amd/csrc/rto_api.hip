@@ -34,6 +34,7 @@ struct rto_context {
     int64_t numInternal = 0;
     int rootSize = 0, depth = 0;
     bool canonical = false;
+    int anyOrderStackNeed = 0;      // a non-canonical array's stack need under the worst push order (walk_stack_need); 0: not such an array
     bool exactGridAllowed = true;   // rto_debug_set_exact_grid(0): the general 12-plane child test whatever the grid (tests, A/B)
     bool exactGrid = false;         // every node plane gridMin + k * voxelSize (k = 0 .. rootSize) is computed without rounding: see grid_is_exact
     float gridMin[3] = { 0, 0, 0 };
@@ -228,6 +229,7 @@ static void free_octree_arrays(rto_context* c) {
     for (auto& kv : c->orders) { kv.second.tab[0].valid = kv.second.tab[1].valid = false; kv.second.costValid = false; }
     c->numNodes = c->numInternal = 0;
     c->canonical = false; c->culling = false; c->rootVisible = 1; c->visibleNodes = 0;
+    c->anyOrderStackNeed = 0;
 }
 
 static void free_octree(rto_context* c) {
@@ -369,8 +371,12 @@ static bool build_descriptors(const rto_node* nodes, int64_t n, std::vector<uint
 // slab test passes: need(leaf) = 1, need(v) = max(1, max over pushed children c of (children pushed before c) + need(c)) -- the
 // pushed siblings below c stay on the stack while c's subtree is walked.  7 d + 1 on a full octree of depth d.  Returns RTO_OK or
 // the refusal of rto_upload_octree (child index out of range, cycle, node larger than 2^kMaxDepth, need above kStackCap).
-static int walk_stack_need(rto_context* c, const rto_node* nodes, int64_t n, int& need) {
+// anyOrder: the same need when the children may be pushed in any order (the span walk pushes them in the ray's octant order):
+// needAny(v) = max(1, max over children c of (children of v - 1) + needAny(c)), every sibling of c below it in the worst case.  It
+// refuses nothing: an array that the walks in slot order can hold is accepted, and the span entries look at anyOrder themselves.
+static int walk_stack_need(rto_context* c, const rto_node* nodes, int64_t n, int& need, int& anyOrder) {
     std::vector<int> nd((size_t)n, 0);                 // 0 unvisited, -1 on the current path, > 0 the node's need
+    std::vector<int> any((size_t)n, 1);                // the node's need under any push order, saturated above kStackCap
     std::vector<std::pair<int64_t, int>> path;         // (node, next child slot)
     nd[0] = -1;
     path.push_back({ 0, 0 });
@@ -393,10 +399,15 @@ static int walk_stack_need(rto_context* c, const rto_node* nodes, int64_t n, int
             path.push_back({ v.child[k], 0 });
             continue;
         }
-        int m = 1, pushed = 0;
+        int m = 1, pushed = 0, deepest = 0;
         if (!is_terminal(v))
             for (int i = 0; i < 8; i++)
-                if (v.child[i] >= 0) { m = std::max(m, pushed + nd[(size_t)v.child[i]]); pushed++; }
+                if (v.child[i] >= 0) {
+                    m = std::max(m, pushed + nd[(size_t)v.child[i]]);
+                    deepest = std::max(deepest, any[(size_t)v.child[i]]);
+                    pushed++;
+                }
+        any[(size_t)u] = std::min(kStackCap + 1, std::max(1, pushed - 1 + deepest));
         if (m > kStackCap)
             return fail(c, RTO_E_UNSUPPORTED, "rto_upload_octree: a traversal of this array could hold more than " +
                                                   std::to_string(kStackCap) + " stack entries (7 per level of a depth-20 octree, plus one)");
@@ -404,6 +415,7 @@ static int walk_stack_need(rto_context* c, const rto_node* nodes, int64_t n, int
         path.pop_back();
     }
     need = nd[0];
+    anyOrder = any[0];
     return RTO_OK;
 }
 
@@ -421,9 +433,10 @@ int rto_upload_octree(rto_context* c, const rto_node* nodes, int64_t n, const fl
     std::vector<int> firstChild;
     int rootSize = 0, depth = 0;
     const bool canonical = build_descriptors(nodes, n, desc, firstChild, rootSize, depth);
+    int anyOrderNeed = 0;
     if (!canonical) {   // a canonical octree has depth <= kMaxDepth, hence needs at most kStackCap entries; any other array is walked first
         int need = 0;
-        const int rc = walk_stack_need(c, nodes, n, need);
+        const int rc = walk_stack_need(c, nodes, n, need, anyOrderNeed);
         if (rc != RTO_OK) return rc;
     }
     RTO_HIP(c, hipSetDevice(c->device));
@@ -446,6 +459,7 @@ int rto_upload_octree(rto_context* c, const rto_node* nodes, int64_t n, const fl
         }
     }
     c->canonical = canonical;
+    c->anyOrderStackNeed = anyOrderNeed;
     c->rootSize = rootSize; c->depth = depth;
     if (c->canonical) {
         c->numInternal = (int64_t)desc.size();
@@ -806,6 +820,7 @@ static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
     c->numNodes = total; c->visibleNodes = total; c->numInternal = internal;
     c->rootSize = 1 << R; c->depth = R;
     c->canonical = internal > 0;                 // a one-node tree is rendered by the generic kernel
+    c->anyOrderStackNeed = 0;
     return build_cells(c);
 }
 
@@ -2691,6 +2706,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_comm.inc"
 #include "rto_query.inc"
 #include "rto_tri_query.inc"
+#include "rto_span.inc"
 #include "rto_edit.inc"
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"

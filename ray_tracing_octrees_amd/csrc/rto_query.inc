@@ -89,8 +89,10 @@ __device__ __forceinline__ void store_hit(const QuerySrc& Q, int64_t i, bool hit
 //               tested at the pop, at the default clamps;
 //   leaves(d.x) the leaf children of a descriptor that can hold a hit;
 //   closest()   the t a pruning rule holds boxes against (the best hit so far);
-//   leaf(..)    a popped leaf whose box passed: true when it holds an accepted hit, which the rule has then recorded.
-// BoxRule is the box queries' (the lit render's too), TriRule (rto_tri_query.inc) the triangle queries'.
+//   leaf(..)    a popped leaf whose box passed: true when it holds an accepted hit, which the rule has then recorded;
+//   kEveryLeaf  the rule wants every accepted leaf of the ray: the walk goes on past a hit in any mode, as CLOSEST does.
+// BoxRule is the box queries' (the lit render's too), TriRule (rto_tri_query.inc) the triangle queries', SpanRule (rto_span.inc)
+// the span queries'.
 
 // The two LDS stacks of the calling lane: `levels` entries of each per lane, [wave][level][lane].
 __device__ __forceinline__ void desc_stacks(uint2* lds, int levels, uint2*& stk, unsigned*& stkNode) {
@@ -115,6 +117,7 @@ struct DescHit {
 template <int QMODE>
 struct BoxRule {
     static constexpr bool kPrune = QMODE != kQueryFirst;
+    static constexpr bool kEveryLeaf = false;
     DescHit best;
     __device__ __forceinline__ BoxRule() { best.hit = false; best.t = 1e30f; best.x = best.y = best.z = best.size = best.j = 0; best.node = 0; }
     __device__ __forceinline__ static unsigned leaves(unsigned dx) { return dx & 0xffu; }
@@ -206,7 +209,7 @@ __device__ __forceinline__ bool desc_walk(const RenderParams& P, const Geo& G, c
             continue;
         }
         const bool got = R.leaf(r, tlo, thi, tNear, tFar, chx, chy, chz, h, j, stkNode + Lb * kWave);
-        if (QMODE == kQueryClosest) {
+        if (QMODE == kQueryClosest || Rule::kEveryLeaf) {
             hit = hit || got;                                      // a plain boolean: got is computed above
         } else if (got) {
             hit = true;
@@ -252,8 +255,9 @@ __global__ __launch_bounds__(kBlock) void k_query_desc(RenderParams P, QuerySrc 
 }
 
 // ================================================================ any array, or RTO_KERNEL_GENERIC: node by node
-// The 60-byte array with explicit child indices and a stack of kStackCap entries (rto_upload_octree bounds every walk by it) in
-// the reference's LIFO order.  The stack lives in LDS, [entry][lane] (conflict free), one wave per workgroup (36 KB): a private
+// The 60-byte array with explicit child indices and a stack of kStackCap entries in the reference's LIFO order.  rto_upload_octree
+// bounds every walk that pushes children in slot order 0 .. 7 by it (walk_stack_need); a walk in another order (k_span_nodes) is
+// bounded by the any-order need the upload records beside it, which its entries check before they launch.  The stack lives in LDS, [entry][lane] (conflict free), one wave per workgroup (36 KB): a private
 // int[kStackCap] would be scratch memory.  FIRST is the loop of k_trace_generic, CLOSEST that of k_trace_closest (a leaf replaces the best only
 // when strictly nearer: ties to the leaf popped first), ANY ends at the first accepted leaf; CLOSEST and ANY also cut nodes with
 // tNear > t_hi.

@@ -80,6 +80,7 @@ __device__ __forceinline__ void store_tri_hit(rto_tri_hit* __restrict__ hits, in
 // the tie rule is by index.
 struct TriRule {
     static constexpr bool kPrune = false;
+    static constexpr bool kEveryLeaf = false;
     const int* __restrict__ descFirstChild;
     const float* __restrict__ tris;
     const int* __restrict__ triOffset;

@@ -37,6 +37,7 @@ SYMBOLS = (
     "rto_scene_bounds_get", "rto_scene_bounds_of_nodes", "rto_split_plan_make", "rto_split_part_of_rank", "rto_split_rows_of_part", "rto_split_row_source",
     "rto_query_rays_device", "rto_query_rays_host", "rto_query_pixels_device", "rto_query_pixels_host",
     "rto_query_triangles_device", "rto_query_triangles_host", "rto_query_triangle_pixels_device", "rto_query_triangle_pixels_host",
+    "rto_query_spans_device", "rto_query_spans_host", "rto_query_span_pixels_device", "rto_query_span_pixels_host",
     "rto_edit_voxels", "rto_download_voxels", "rto_last_edit_ms", "rto_brush_quantize",
     "rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions",
     "rto_render_lit_triangles_device", "rto_render_lit_triangles_host",
@@ -53,6 +54,9 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("node", "<i4"), ("face", "<i4"), ("size", "
 # struct rto_tri_hit, 32 bytes
 TRI_HIT_DTYPE = np.dtype([("t", "<f4"), ("tri", "<i4"), ("node", "<i4"), ("u", "<f4"), ("v", "<f4"),
                           ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")])
+# struct rto_span, 32 bytes: span queries (rto_query_spans_*)
+SPAN_DTYPE = np.dtype([("length", "<f4"), ("t_enter", "<f4"), ("t_exit", "<f4"), ("leaves", "<i4"),
+                       ("node", "<i4"), ("face", "<i4"), ("reserved", "<i4", (2,))])
 # struct rto_brush, 32 bytes: voxel edits (rto_edit_voxels)
 BRUSH_SPHERE, BRUSH_BOX = 0, 1
 EDIT_CARVE, EDIT_FILL = 0, 1
@@ -137,6 +141,11 @@ def ao_directions() -> np.ndarray:
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("node", C.c_int32), ("face", C.c_int32), ("size", C.c_int32),
                 ("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Span(C.Structure):
+    _fields_ = [("length", C.c_float), ("t_enter", C.c_float), ("t_exit", C.c_float), ("leaves", C.c_int32),
+                ("node", C.c_int32), ("face", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 def make_rays(origins, dirs, t_min=0.0, t_max=1e30) -> np.ndarray:
@@ -318,6 +327,10 @@ def load():
     L.rto_query_rays_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
     L.rto_query_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
     L.rto_query_pixels_host.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp]
+    L.rto_query_spans_device.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.rto_query_spans_host.argtypes = [vp, vp, C.c_int64, vp]
+    L.rto_query_span_pixels_device.argtypes = [vp, C.POINTER(Frame), vp, C.c_int64, vp, vp]
+    L.rto_query_span_pixels_host.argtypes = [vp, C.POINTER(Frame), vp, C.c_int64, vp]
     L.rto_query_triangles_device.argtypes = [vp, C.c_int, vp, C.c_int64, vp, vp]
     L.rto_query_triangles_host.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
     L.rto_query_triangle_pixels_device.argtypes = [vp, C.c_int, C.POINTER(Frame), vp, C.c_int64, vp, vp]
@@ -632,6 +645,35 @@ class Context:
     def query_pixels_device(self, mode: int, frame: Frame, d_xy: int, n: int, d_hits: int, stream: int = 0):
         self._check(self._L.rto_query_pixels_device(self._h, int(mode), C.byref(frame), C.c_void_p(d_xy) if d_xy else None, int(n),
                                                     C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    # -- span queries ------------------------------------------------------
+    def query_spans(self, origins, dirs, t_min=0.0, t_max=1e30) -> np.ndarray:
+        """How much solid each ray passes through (rto_query_spans_host): origins (n, 3) or one origin, dirs (n, 3), t_min / t_max
+        scalars or per-ray arrays.  Returns a SPAN_DTYPE array (length 0, leaves 0, node -1, t_enter = t_exit = 1e30 for a miss)."""
+        return self.query_span_records(make_rays(origins, dirs, t_min, t_max))
+
+    def query_span_records(self, rays: np.ndarray) -> np.ndarray:
+        """The same for a RAY_DTYPE array."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        spans = np.zeros(len(rays), SPAN_DTYPE)
+        self._check(self._L.rto_query_spans_host(self._h, rays.ctypes.data, len(rays), spans.ctypes.data))
+        return spans
+
+    def query_spans_device(self, d_rays: int, n: int, d_spans: int, stream: int = 0):
+        """Asynchronous: n rto_ray records at d_rays -> n rto_span records at d_spans (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_spans_device(self._h, C.c_void_p(d_rays) if d_rays else None, int(n),
+                                                   C.c_void_p(d_spans) if d_spans else None, C.c_void_p(stream) if stream else None))
+
+    def query_span_pixels(self, frame: Frame, xy) -> np.ndarray:
+        """The renders' own rays through pixels (x, y) of `frame` (row 0 = top): xy (n, 2) int; a SPAN_DTYPE array."""
+        xy = np.ascontiguousarray(np.asarray(xy, np.int32).reshape(-1, 2))
+        spans = np.zeros(len(xy), SPAN_DTYPE)
+        self._check(self._L.rto_query_span_pixels_host(self._h, C.byref(frame), xy.ctypes.data, len(xy), spans.ctypes.data))
+        return spans
+
+    def query_span_pixels_device(self, frame: Frame, d_xy: int, n: int, d_spans: int, stream: int = 0):
+        self._check(self._L.rto_query_span_pixels_device(self._h, C.byref(frame), C.c_void_p(d_xy) if d_xy else None, int(n),
+                                                         C.c_void_p(d_spans) if d_spans else None, C.c_void_p(stream) if stream else None))
 
     # -- lit render ----------------------------------------------------------
     def render_lit_host(self, frame: Frame, lighting: Lighting | None = None, vis: bool = False, **kw):

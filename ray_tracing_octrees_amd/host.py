@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import BRUSH_DTYPE, HIT_DTYPE, NODE_DTYPE, TRI_HIT_DTYPE, RtoError, _f
+from .hip import BRUSH_DTYPE, HIT_DTYPE, NODE_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE, RtoError, _f
 
 _lib = None
 _vp = C.c_void_p
@@ -125,6 +125,10 @@ def load():
     L.rtoh_rt_render_surface_lit.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
+    L.rtoh_rt_intersect_spans.argtypes = [_vp, _vp, C.c_int64, C.c_float, C.c_float, _vp]
+    L.rtoh_rt_intersect_spans.restype = None
+    L.rtoh_rt_pick_span.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
+    L.rtoh_rt_pick_span.restype = C.c_int
     L.rtoh_rt_intersect_triangles.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float, _vp, _vp]
     L.rtoh_rt_intersect_triangles.restype = None
     L.rtoh_rt_pick_surface.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp]
@@ -421,6 +425,22 @@ class RayTracerBVH:
         """Addition: RayTracerBVH::pick -- the leaf renderSceneCompute shows at pixel (px, py): an rto_hit record, or None."""
         out = np.zeros(1, HIT_DTYPE)
         hit = load().rtoh_rt_pick(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg), out.ctypes.data)
+        return out[0] if hit else None
+
+    def intersectSpans(self, origins, dirs, tMin: float = 0.0, tMax: float = 1e30) -> np.ndarray:
+        """Addition: RayTracerBVH::intersectSpans -- the solid path length of rays (origins (n, 3) or one origin, dirs (n, 3))
+        through the resident octree; a structured array of rto_span records (hip.SPAN_DTYPE; leaves 0 = miss)."""
+        d = np.asarray(dirs, np.float32).reshape(-1, 3)
+        o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
+        rays = np.ascontiguousarray(np.concatenate([o, d], 1), dtype=np.float32)
+        spans = np.zeros(len(d), SPAN_DTYPE)
+        load().rtoh_rt_intersect_spans(self._h, rays.ctypes.data, len(d), _f(tMin), _f(tMax), spans.ctypes.data)
+        return spans
+
+    def pickSpan(self, camera: Camera, px: int, py: int, width: int, height: int, aspect: float, fovDeg: float):
+        """Addition: RayTracerBVH::pickSpan -- the span of renderSceneCompute's ray through pixel (px, py): an rto_span record, or None."""
+        out = np.zeros(1, SPAN_DTYPE)
+        hit = load().rtoh_rt_pick_span(self._h, camera._h, int(px), int(py), int(width), int(height), _f(aspect), _f(fovDeg), out.ctypes.data)
         return out[0] if hit else None
 
     def intersectTriangles(self, origins, dirs, mode: int = 1, tMin: float = 0.0, tMax: float = 1e30):

@@ -37,6 +37,8 @@ struct HipApi {
     decltype(&rto_comm_render_resident_all) comm_render_resident_all = nullptr;
     decltype(&rto_query_rays_host) query_rays_host = nullptr;
     decltype(&rto_query_pixels_host) query_pixels_host = nullptr;
+    decltype(&rto_query_spans_host) query_spans_host = nullptr;
+    decltype(&rto_query_span_pixels_host) query_span_pixels_host = nullptr;
     decltype(&rto_query_triangles_host) query_triangles_host = nullptr;
     decltype(&rto_query_triangle_pixels_host) query_triangle_pixels_host = nullptr;
     decltype(&rto_edit_voxels) edit_voxels = nullptr;
@@ -93,6 +95,8 @@ struct HipApi {
         comm_render_resident_all = reinterpret_cast<decltype(comm_render_resident_all)>(sym("rto_comm_render_resident_all"));
         query_rays_host = reinterpret_cast<decltype(query_rays_host)>(sym("rto_query_rays_host"));
         query_pixels_host = reinterpret_cast<decltype(query_pixels_host)>(sym("rto_query_pixels_host"));
+        query_spans_host = reinterpret_cast<decltype(query_spans_host)>(sym("rto_query_spans_host"));
+        query_span_pixels_host = reinterpret_cast<decltype(query_span_pixels_host)>(sym("rto_query_span_pixels_host"));
         query_triangles_host = reinterpret_cast<decltype(query_triangles_host)>(sym("rto_query_triangles_host"));
         query_triangle_pixels_host = reinterpret_cast<decltype(query_triangle_pixels_host)>(sym("rto_query_triangle_pixels_host"));
         edit_voxels = reinterpret_cast<decltype(edit_voxels)>(sym("rto_edit_voxels"));
@@ -250,16 +254,19 @@ void RayTracerBVH::ensureComputeInitialized() {
     }
 }
 
-bool RayTracerBVH::render(const Camera& camera, int width, int height, float aspect, float fovDeg) {
+// The rto_frame of a camera and a frame size: what every render, pick and lit call hands to the C ABI.
+static rto_frame frame_of(const Camera& camera, int width, int height, float aspect, float fovDeg) {
     rto_frame f;
     const auto view = camera.getView();            // rtmath::mat4 or glm::mat4: both column-major, m[col][row]
     std::memcpy(f.view, &view[0][0], sizeof f.view);
     const auto pos = camera.getPos();
     f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
-    f.aspect = aspect;
-    f.fov_deg = fovDeg;
-    f.width = width;
-    f.height = height;
+    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    return f;
+}
+
+bool RayTracerBVH::render(const Camera& camera, int width, int height, float aspect, float fovDeg) {
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
     if (width <= 0 || height <= 0) return false;
     // like the reference's texture, the frame stays on the GPU (asynchronous); framebuffer() fetches it on demand
     m_frameW = m_frameH = 0; m_frameStale = false;
@@ -315,12 +322,7 @@ void RayTracerBVH::renderSceneTriangles(const Camera& camera, int width, int hei
         return;
     }
     if (m_numNodes <= 0 || width <= 0 || height <= 0) return;
-    rto_frame f;
-    const auto view = camera.getView();
-    std::memcpy(f.view, &view[0][0], sizeof f.view);
-    const auto pos = camera.getPos();
-    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
-    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
     m_frameW = m_frameH = 0; m_frameStale = false;
     if (!renderFrame(f, shadow ? RTO_RESIDENT_TRIANGLES_SHADOW : RTO_RESIDENT_TRIANGLES)) {
         std::cerr << "[RayTracerBVH] render failed: " << m_lastError << std::endl;
@@ -344,12 +346,7 @@ void RayTracerBVH::renderLit(const Camera& camera, int width, int height, float 
         return;
     }
     if (m_numNodes <= 0 || width <= 0 || height <= 0) return;
-    rto_frame f;
-    const auto view = camera.getView();
-    std::memcpy(f.view, &view[0][0], sizeof f.view);
-    const auto pos = camera.getPos();
-    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
-    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
     rto_lighting L;
     L.light_dir[0] = lighting.lightDir.x; L.light_dir[1] = lighting.lightDir.y; L.light_dir[2] = lighting.lightDir.z;
     L.shadow = lighting.shadow ? 1 : 0;
@@ -404,12 +401,7 @@ bool RayTracerBVH::pick(const Camera& camera, int px, int py, int width, int hei
         return false;
     }
     if (m_numNodes <= 0 || width <= 0 || height <= 0) return false;
-    rto_frame f;
-    const auto view = camera.getView();
-    std::memcpy(f.view, &view[0][0], sizeof f.view);
-    const auto pos = camera.getPos();
-    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
-    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
     const int32_t xy[2] = { px, py };
     rto_hit h;
     if (api().query_pixels_host(m_ctx, RTO_QUERY_FIRST, &f, xy, 1, &h) != RTO_OK) {
@@ -418,6 +410,52 @@ bool RayTracerBVH::pick(const Camera& camera, int px, int py, int width, int hei
         return false;
     }
     out = to_ray_hit(h);
+    return out.hit();
+}
+
+static RaySpan to_ray_span(const rto_span& s) {
+    RaySpan r;
+    r.length = s.length; r.tEnter = s.t_enter; r.tExit = s.t_exit; r.leaves = s.leaves; r.node = s.node; r.face = s.face;
+    return r;
+}
+
+void RayTracerBVH::intersectSpans(const std::vector<Ray>& rays, std::vector<RaySpan>& spans, float tMin, float tMax) {
+    spans.assign(rays.size(), RaySpan());
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return;
+    }
+    if (rays.empty() || m_numNodes <= 0) return;
+    std::vector<rto_ray> in(rays.size());
+    for (size_t i = 0; i < rays.size(); i++) {
+        const Ray& r = rays[i];
+        in[i] = rto_ray{ r.origin.x, r.origin.y, r.origin.z, tMin, r.direction.x, r.direction.y, r.direction.z, tMax };
+    }
+    std::vector<rto_span> out(rays.size());
+    if (api().query_spans_host(m_ctx, in.data(), (int64_t)in.size(), out.data()) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] span query failed: " << m_lastError << std::endl;
+        return;
+    }
+    for (size_t i = 0; i < out.size(); i++) spans[i] = to_ray_span(out[i]);
+}
+
+bool RayTracerBVH::pickSpan(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RaySpan& out) {
+    out = RaySpan();
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return false;
+    }
+    if (m_numNodes <= 0 || width <= 0 || height <= 0) return false;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
+    const int32_t xy[2] = { px, py };
+    rto_span s;
+    if (api().query_span_pixels_host(m_ctx, &f, xy, 1, &s) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] pickSpan failed: " << m_lastError << std::endl;
+        return false;
+    }
+    out = to_ray_span(s);
     return out.hit();
 }
 
@@ -485,12 +523,7 @@ bool RayTracerBVH::pickSurface(const Camera& camera, int px, int py, int width, 
         return false;
     }
     if (m_numNodes <= 0 || width <= 0 || height <= 0 || px < 0 || px >= width || py < 0 || py >= height) return false;
-    rto_frame f;
-    const auto view = camera.getView();
-    std::memcpy(f.view, &view[0][0], sizeof f.view);
-    const auto pos = camera.getPos();
-    f.cam_pos[0] = pos.x; f.cam_pos[1] = pos.y; f.cam_pos[2] = pos.z;
-    f.aspect = aspect; f.fov_deg = fovDeg; f.width = width; f.height = height;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
     const int32_t xy[2] = { px, py };
     rto_tri_hit h;
     if (api().query_triangle_pixels_host(m_ctx, RTO_QUERY_FIRST, &f, xy, 1, &h) != RTO_OK) {
@@ -499,7 +532,7 @@ bool RayTracerBVH::pickSurface(const Camera& camera, int px, int py, int width, 
         return false;
     }
     if (h.tri < 0) return false;
-    out = to_triangle_hit(h, pos, pixel_direction(camera, px, py, width, height, aspect, fovDeg));
+    out = to_triangle_hit(h, camera.getPos(), pixel_direction(camera, px, py, width, height, aspect, fovDeg));
     return true;
 }
 

@@ -57,6 +57,18 @@ struct RayHit {
     bool hit() const { return node >= 0; }
 };
 
+// What a span query found (the fields of rto_span, include/rto_hip.h): the solid length the ray passes
+// through inside its window (units of d), where it first enters and last leaves solid, how many octree leaves it crosses (leaves,
+// not walls), and Closest's leaf and entry face.  A miss has length 0, leaves 0, node -1 and tEnter = tExit = 1e30.
+struct RaySpan {
+    float length = 0.0f;
+    float tEnter = 1e30f, tExit = 1e30f;
+    int leaves = 0;
+    int node = -1;
+    int face = -1;
+    bool hit() const { return leaves > 0; }
+};
+
 // What a triangle query found (the fields of rto_tri_hit, include/rto_hip.h): the accepted triangle's index in the resident
 // triangle buffer, the leaf that owns it, the ray parameter t, the hit point o + d t, the barycentrics u, v (the point is
 // (1 - u - v) v0 + u v1 + v v2) and the stored face normal turned against the ray.  A miss has tri -1 and t 1e30.
@@ -134,6 +146,12 @@ public:
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
     bool pick(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RayHit& out);
+    // Span queries (rto_query_spans_host): one RaySpan per Ray, the solid path length between tMin and tMax.
+    // Attenuation between two points: direction = b - a, tMax = 1, exp(-mu * length * |b - a|).  Fails as intersectRays does.
+    void intersectSpans(const std::vector<Ray>& rays, std::vector<RaySpan>& spans, float tMin = 0.0f, float tMax = 1e30f);
+    // The span of renderSceneCompute's own ray through pixel (px, py) (rto_query_span_pixels_host): thickness under the cursor.
+    // false (and out a miss) when the ray meets no solid; fails as pick does.
+    bool pickSpan(const Camera& camera, int px, int py, int width, int height, float aspect, float fovDeg, RaySpan& out);
     // The same queries against the resident leaf triangles (rto_query_triangles_host, DESIGN.md section 10 "Triangle queries"):
     // one TriangleHit per Ray.  First is renderSceneTriangles' rule, Closest the nearest surface, Any occlusion (a shadow ray
     // towards a point light: tMax = the distance to it in units of d).

@@ -214,6 +214,26 @@ int rtoh_rt_pick(RayTracerBVH* rt, const Camera* cam, int px, int py, int w, int
     *out = rto_hit{ r.t, r.node, r.face, r.size, r.x, r.y, r.z, 0 };
     return hit ? 1 : 0;
 }
+static rto_span to_rto_span(const RaySpan& s) {
+    return rto_span{ s.length, s.tEnter, s.tExit, s.leaves, s.node, s.face, { 0, 0 } };
+}
+// rays: n x (ox, oy, oz, dx, dy, dz); spans: n rto_span records
+void rtoh_rt_intersect_spans(RayTracerBVH* rt, const float* rays, int64_t n, float tMin, float tMax, rto_span* spans) {
+    std::vector<Ray> in((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        in[(size_t)i].origin = rto_host::vec3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+        in[(size_t)i].direction = rto_host::vec3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    }
+    std::vector<RaySpan> out;
+    rt->intersectSpans(in, out, tMin, tMax);
+    for (int64_t i = 0; i < n; i++) spans[i] = to_rto_span(out[(size_t)i]);
+}
+int rtoh_rt_pick_span(RayTracerBVH* rt, const Camera* cam, int px, int py, int w, int h, float aspect, float fovDeg, rto_span* out) {
+    RaySpan r;
+    const bool hit = rt->pickSpan(*cam, px, py, w, h, aspect, fovDeg, r);
+    *out = to_rto_span(r);
+    return hit ? 1 : 0;
+}
 static rto_tri_hit to_rto_tri_hit(const TriangleHit& h) {
     return rto_tri_hit{ h.t, h.tri, h.node, h.u, h.v, h.normal.x, h.normal.y, h.normal.z };
 }
