@@ -609,6 +609,52 @@ int  rto_voxelize_mesh(rto_context* ctx, const double* xyz, int64_t n_verts, con
 /* Device time in ms of the last rto_voxelize_mesh: face setup + scan, fill, recentring reduction, octree build (-1: not run). */
 int  rto_last_voxelize_ms(const rto_context* ctx, float ms[4]);
 
+/* ---- mesh extraction ------------------------------------------------------
+ * The triangle list the reference's renderOctree (S/main.cpp:95-208) hands to its MarchingCubes and VoxelCube display modes, made
+ * on the GPU from the resident octree.  All float32, one IEEE operation per operator.  Rule:
+ *   visibility    a leaf is emitted when its own box and every ancestor's, up to the root, pass Frustum::testAABB(min, max, margin)
+ *                 != -1 with min = gridMin + (float)xyz * voxelSize, max = min + (float)size * voxelSize (rto_update_frustum's
+ *                 arithmetic).  Hierarchical: a leaf below a culled ancestor is dropped whatever its own test says.  cull == NULL:
+ *                 every leaf is visible.  The state rto_update_frustum left is ignored, as in the queries.
+ *   order         depth first, children in slots 0..7; within a leaf the extractor's own order.
+ *   reach         the walk starts at node 0 and descends through nodes with isLeaf == 0 && isUniform == 0, as every traversal here
+ *                 does: a node with isUniform == 1 && isLeaf == 0 ends it and emits nothing, and a leaf that the array holds but
+ *                 the walk does not reach (below such a node, or an orphan) is not part of the mesh.
+ *   RTO_MESH_MC   a visible leaf i contributes the resident leaf triangles tri_offset[i] .. tri_offset[i + 1], unchanged.
+ *   RTO_MESH_CUBES  VoxelCubeRenderer::addBlockFaces (S/Renderer.cpp:64-98) on every visible leaf with isLeaf && isSolid: faces
+ *                 +X, -X, +Y, -Y, +Z, -Z; a face is exposed when its ONE test voxel -- x0 + size (or x0 - 1) on the face's axis,
+ *                 + size / 2 (integer) on the other two -- lies outside the grid's dims or is EMPTY in the resident grid.  The
+ *                 reference tests the face's centre only, and so does this: a large leaf whose face centre is covered emits no
+ *                 face.  Each face is two triangles (v0, v1, v3), (v3, v1, v2) of the corners S/Renderer.cpp:100-153 names, with
+ *                 minCorner = gridMin + (float)x0 * voxelSize, maxCorner = minCorner + (float)size * voxelSize; the normal is the
+ *                 axis unit vector with +0 zeros.
+ * A record is 12 floats: v0, v1, v2, normal.  tri_node[j] = index, in the resident array, of the leaf that owns triangle j.
+ * The result is a snapshot in a buffer the context owns: valid until the next rto_extract_mesh or rto_destroy, untouched by later
+ * edits or builds.  Synchronous on the context's stream (one count is read back).  An empty result is RTO_OK with 0 triangles.
+ * Errors, in this order, each leaving the previous mesh and the context untouched: RTO_E_INVALID (unknown kind, NULL num_tris, a
+ * plane or margin that is not finite); RTO_E_NO_OCTREE (nothing uploaded); RTO_E_UNSUPPORTED (an array of more than one node that
+ * is not canonical, or whose levels are not stored one after the other as setOctree's BFS and rto_build_octree store them); MC:
+ * RTO_E_NO_OCTREE when no leaf triangles are resident; CUBES: RTO_E_UNSUPPORTED when no grid is resident (the octree came from
+ * rto_upload_octree); RTO_E_UNSUPPORTED for more than 2^31 - 1 triangles. */
+#define RTO_MESH_MC     0   /* MarchingCubesRenderer: the resident leaf triangles */
+#define RTO_MESH_CUBES  1   /* VoxelCubeRenderer: exposed faces of the solid leaves */
+typedef struct rto_mesh_cull {      /* 100 bytes */
+    float planes[24];               /* LEFT, RIGHT, TOP, BOTTOM, NEAR, FAR as nx, ny, nz, d; normalised (rto_debug_update_frustum_planes' layout) */
+    float margin;                   /* renderOctree's extraMargin; its default is 50 */
+} rto_mesh_cull;
+
+/* Pure host function: the planes rto_update_frustum derives, Frustum(perspective(radians(fov_deg), aspect, 0.01, 5000) * view)
+ * (renderOctree builds its own the same way with fov 45, S/main.cpp:124-129). */
+int  rto_frustum_planes(const float view[16], float fov_deg, float aspect, float planes[24]);
+int  rto_extract_mesh(rto_context* ctx, int kind, const rto_mesh_cull* cull /* NULL: no culling */, int64_t* num_tris);
+/* The last mesh where it lies: num_tris records of 48 bytes and as many int32 (both may be NULL for the count alone). */
+int  rto_mesh_device(rto_context* ctx, void** d_tris, int32_t** d_tri_node, int64_t* num_tris);
+/* Copies it out; tris == NULL and tri_node == NULL: the count alone.  RTO_E_INVALID: no mesh extracted yet, capacity too small. */
+int  rto_download_mesh(rto_context* ctx, float* tris, int64_t capacity, int32_t* tri_node /* may be NULL */, int64_t* num_tris);
+/* Device time in ms of the last rto_extract_mesh: count + cull, the ranking passes, the emit kernel (-1: not run).  The read-back
+ * of the count and the growth of the output buffer lie between the last two and are in none of them. */
+int  rto_last_mesh_ms(const rto_context* ctx, float ms[3]);
+
 /* ---- lit render -----------------------------------------------------------
  * The box render's frame with a shadow ray and ambient occlusion per hit pixel, computed on the device in one stream (DESIGN.md
  * section 12).  Rule:

@@ -17,13 +17,13 @@ from __future__ import annotations
 from . import hip, host
 from .hip import (KERNEL_AUTO, KERNEL_GENERIC, KERNEL_PACKED, KERNEL_PACKED_PERSISTENT, KERNEL_PACKED_V1, KERNEL_PACKED_V3, NODE_DTYPE, Context, Frame, Partition,
                   RtoError, make_frame)
-from .host import (Camera, MarchingCubesRenderer, OctreeNode, RayTracerBVH, VoxelGrid, buildLeafTriangles,
+from .host import (Camera, MarchingCubesRenderer, OctreeNode, RayTracerBVH, VoxelCubeRenderer, VoxelGrid, buildLeafTriangles,
                    createOctreeFromVoxelGrid,
-                   freeOctree, getVoxelSafe, loadCSVDataIntoVoxelGrid, loadVoxelGrid, loadVoxelGridPartial, localMC, saveVoxelGrid)
+                   freeOctree, getVoxelSafe, loadCSVDataIntoVoxelGrid, loadVoxelGrid, loadVoxelGridPartial, localMC, renderOctree, saveVoxelGrid)
 
 __all__ = [
     "RayTracerBVH", "VoxelGrid", "OctreeNode", "Camera", "createOctreeFromVoxelGrid", "freeOctree",
-    "getVoxelSafe", "loadCSVDataIntoVoxelGrid", "loadVoxelGrid", "loadVoxelGridPartial", "saveVoxelGrid", "localMC", "MarchingCubesRenderer", "buildLeafTriangles",
+    "getVoxelSafe", "loadCSVDataIntoVoxelGrid", "loadVoxelGrid", "loadVoxelGridPartial", "saveVoxelGrid", "localMC", "MarchingCubesRenderer", "VoxelCubeRenderer", "renderOctree", "buildLeafTriangles",
     "Context", "Frame", "Partition", "RtoError", "make_frame", "NODE_DTYPE",
     "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_PACKED", "KERNEL_PACKED_PERSISTENT", "KERNEL_PACKED_V1", "KERNEL_PACKED_V3", "hip", "host",
 ]

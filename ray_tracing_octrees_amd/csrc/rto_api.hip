@@ -159,6 +159,14 @@ struct rto_context {
     unsigned* d_litAcc = nullptr;
     unsigned* d_litCount = nullptr;
     size_t litCap = 0;
+
+    // mesh extraction (rto_mesh.inc): the last mesh (a snapshot the context owns) and the first node of every tree level
+    float4* d_mesh = nullptr;
+    int* d_meshNode = nullptr;
+    int64_t meshTris = -1, meshCap = 0;       // -1: no mesh extracted yet
+    float meshMs[3] = { -1.f, -1.f, -1.f };
+    int meshLevelStart[kMaxDepth + 2] = { 0 };
+    int meshLevels = 0;                       // 0: not known for the resident array (made on first use, dropped with the arrays)
 };
 
 static thread_local std::string g_createError;
@@ -230,6 +238,7 @@ static void free_octree_arrays(rto_context* c) {
     c->numNodes = c->numInternal = 0;
     c->canonical = false; c->culling = false; c->rootVisible = 1; c->visibleNodes = 0;
     c->anyOrderStackNeed = 0;
+    c->meshLevels = 0;
 }
 
 static void free_octree(rto_context* c) {
@@ -304,6 +313,8 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_litRec);
     (void)hipFree(c->d_litAcc);
     (void)hipFree(c->d_litCount);
+    (void)hipFree(c->d_mesh);
+    (void)hipFree(c->d_meshNode);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ringStop) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2711,3 +2722,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"
 #include "rto_tri_lit.inc"
+#include "rto_mesh.inc"

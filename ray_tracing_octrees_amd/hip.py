@@ -42,7 +42,9 @@ SYMBOLS = (
     "rto_render_lit_device", "rto_render_lit_host", "rto_ao_directions",
     "rto_render_lit_triangles_device", "rto_render_lit_triangles_host",
     "rto_voxelize_mesh", "rto_last_voxelize_ms",
+    "rto_frustum_planes", "rto_extract_mesh", "rto_mesh_device", "rto_download_mesh", "rto_last_mesh_ms",
 )
+MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
 QUERY_FIRST, QUERY_CLOSEST, QUERY_ANY = 0, 1, 2
 
@@ -201,6 +203,21 @@ class SceneBounds(C.Structure):
                 ("solid_lo", C.c_int32 * 3), ("solid_hi", C.c_int32 * 3)]
 
 
+class MeshCull(C.Structure):
+    """rto_mesh_cull (include/rto_hip.h), 100 bytes: six normalised planes and renderOctree's extraMargin."""
+    _fields_ = [("planes", C.c_float * 24), ("margin", C.c_float)]
+
+
+def frustum_planes(view, fov_deg, aspect) -> np.ndarray:
+    """rto_frustum_planes (pure host): the 24 floats Frustum(perspective(radians(fov_deg), aspect, 0.01, 5000) * view) holds."""
+    v = np.ascontiguousarray(np.asarray(view, dtype=np.float32).reshape(16))
+    out = np.zeros(24, np.float32)
+    rc = load().rto_frustum_planes(v.ctypes.data_as(C.POINTER(C.c_float)), _f(fov_deg), _f(aspect), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != RTO_OK:
+        raise RtoError(rc, "rto_frustum_planes")
+    return out
+
+
 class SplitPlan(C.Structure):
     """rto_split_plan (include/rto_hip.h): everything the ranks of a screen split must agree on."""
     _fields_ = [("world", C.c_int32), ("band_rows", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_frames", C.c_int32),
@@ -346,6 +363,11 @@ def load():
     L.rto_ao_directions.argtypes = [vp]
     L.rto_voxelize_mesh.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(VoxelizeParams), C.POINTER(VoxelizeResult)]
     L.rto_last_voxelize_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_frustum_planes.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.rto_extract_mesh.argtypes = [vp, C.c_int, C.POINTER(MeshCull), C.POINTER(C.c_int64)]
+    L.rto_mesh_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_download_mesh.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.rto_last_mesh_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -882,6 +904,53 @@ class Context:
         """Device ms of the last voxelization: (face setup + scan, fill, recentring reduction, octree build); -1: not run."""
         ms = (C.c_float * 4)()
         self._check(self._L.rto_last_voxelize_ms(self._h, ms))
+        return tuple(ms)
+
+    # -- mesh extraction ---------------------------------------------------
+    @staticmethod
+    def frustum_planes(view, fov_deg, aspect) -> np.ndarray:
+        """The planes rto_update_frustum derives for this view (rto_frustum_planes, pure host): 24 float32."""
+        return frustum_planes(view, fov_deg, aspect)
+
+    def extract_mesh_count(self, kind: int, planes=None, margin: float = 50.0) -> int:
+        """rto_extract_mesh alone: the mesh stays on the device (mesh_device / download_mesh); returns its triangle count."""
+        cull = None
+        if planes is not None:
+            cull = MeshCull()
+            pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float32).reshape(24))
+            C.memmove(cull.planes, pl.ctypes.data, 96)
+            cull.margin = float(np.float32(margin)) if np.isfinite(margin) else float(margin)
+        n = C.c_int64(-1)
+        self._check(self._L.rto_extract_mesh(self._h, int(kind), C.byref(cull) if cull is not None else None, C.byref(n)))
+        return n.value
+
+    def download_mesh(self):
+        """The last extracted mesh: (tris float32 (n, 12): v0, v1, v2, normal; tri_node int32 (n,): the owning leaf)."""
+        n = C.c_int64()
+        self._check(self._L.rto_download_mesh(self._h, None, 0, None, C.byref(n)))
+        tris = np.zeros((n.value, 12), np.float32)
+        node = np.zeros(n.value, np.int32)
+        if n.value:
+            self._check(self._L.rto_download_mesh(self._h, tris.ctypes.data, n.value, node.ctypes.data, C.byref(n)))
+        return tris, node
+
+    def extract_mesh(self, kind: int, planes=None, margin: float = 50.0):
+        """The triangle list of what the planes see: kind MESH_MC (the resident leaf triangles) or MESH_CUBES
+        (exposed faces of the solid leaves), in the reference's depth-first order; planes (24 floats, frustum_planes' layout) or
+        None for no culling, margin = renderOctree's extraMargin.  Returns (tris (n, 12), tri_node (n,))."""
+        self.extract_mesh_count(kind, planes, margin)
+        return self.download_mesh()
+
+    def mesh_device(self):
+        """(device pointer of the 48-byte records, device pointer of tri_node, count) of the last extracted mesh."""
+        t, nd, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._L.rto_mesh_device(self._h, C.byref(t), C.byref(nd), C.byref(n)))
+        return t.value or 0, nd.value or 0, n.value
+
+    def last_mesh_ms(self):
+        """Device ms of the last extraction: (count + cull, ranking passes, emit); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_mesh_ms(self._h, ms))
         return tuple(ms)
 
     def scene_bounds(self) -> SceneBounds:

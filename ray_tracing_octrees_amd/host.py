@@ -139,6 +139,18 @@ def load():
     L.rtoh_grid_load_csv.argtypes = [C.c_char_p, C.c_char_p, C.c_float]
     L.rtoh_grid_load_csv.restype = _vp
     L.rtoh_rt_load_mesh.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_float, C.c_int, C.c_int]
+    L.rtoh_cube_renderer.argtypes = [_vp, _vp, _vp, C.c_int64]
+    L.rtoh_cube_renderer.restype = C.c_int64
+    L.rtoh_render_octree_planes.argtypes = [_vp, _vp, C.c_int, _vp, C.c_float, _vp, C.c_int64]
+    L.rtoh_render_octree_planes.restype = C.c_int64
+    L.rtoh_render_octree.argtypes = [_vp, _vp, C.c_int, _vp, C.c_float, C.c_float, _vp, C.c_int64]
+    L.rtoh_render_octree.restype = C.c_int64
+    L.rtoh_render_octree_planes_ms.argtypes = [_vp, _vp, C.c_int, _vp, C.c_float, C.POINTER(C.c_int64)]
+    L.rtoh_render_octree_planes_ms.restype = C.c_double
+    L.rtoh_rt_extract_mesh.argtypes = [_vp, C.c_int, _vp, C.c_float, _vp, C.c_float, C.POINTER(C.c_int64)]
+    L.rtoh_rt_extract_mesh.restype = _vp
+    L.rtoh_tris_take.argtypes = [_vp, _vp]
+    L.rtoh_tris_take.restype = None
     _lib = L
     return L
 
@@ -267,6 +279,49 @@ class MarchingCubesRenderer:
         if n:
             load().rtoh_mc_renderer(root._h, grid._h, out.ctypes.data, n)
         return out
+
+
+class VoxelCubeRenderer:
+    """453-skeleton/Renderer.h:29-55: a cube per solid leaf, the faces whose centre looks at an EMPTY voxel or out of the grid."""
+
+    def render(self, root: OctreeNode, grid: VoxelGrid) -> np.ndarray:
+        n = load().rtoh_cube_renderer(root._h, grid._h, None, 0)
+        out = np.zeros((n, 18), np.float32)
+        if n:
+            load().rtoh_cube_renderer(root._h, grid._h, out.ctypes.data, n)
+        return out
+
+
+def _tris18(call) -> np.ndarray:
+    n = call(None, 0)
+    out = np.zeros((n, 18), np.float32)
+    if n:
+        call(out.ctypes.data, n)
+    return out
+
+
+def renderOctree(root: OctreeNode, grid: VoxelGrid, renderer, camera: "Camera", aspect: float, extraMargin: float = 50.0) -> np.ndarray:
+    """453-skeleton/main.cpp:95-208 on the CPU: the depth-first walk with frustum culling, `renderer` (a MarchingCubesRenderer or
+    a VoxelCubeRenderer) on every leaf it reaches.  (n, 18) float32 as localMC returns them."""
+    kind = 1 if isinstance(renderer, VoxelCubeRenderer) else 0
+    return _tris18(lambda p, n: load().rtoh_render_octree(root._h, grid._h, kind, camera._h, _f(aspect), _f(extraMargin), p, n))
+
+
+def renderOctreePlanes(root: OctreeNode, grid: VoxelGrid, renderer, planes, extraMargin: float) -> np.ndarray:
+    """Addition: the same walk over caller-supplied planes (24 floats; None: nothing is culled)."""
+    kind = 1 if isinstance(renderer, VoxelCubeRenderer) else 0
+    pl = None if planes is None else np.ascontiguousarray(np.asarray(planes, np.float32).reshape(24))
+    return _tris18(lambda p, n: load().rtoh_render_octree_planes(root._h, grid._h, kind, None if pl is None else pl.ctypes.data,
+                                                                 _f(extraMargin), p, n))
+
+
+def renderOctreePlanesMs(root: OctreeNode, grid: VoxelGrid, renderer, planes, extraMargin: float):
+    """Addition: (milliseconds of one renderOctreePlanes walk, timed inside the library as the reference times its own; triangles)."""
+    kind = 1 if isinstance(renderer, VoxelCubeRenderer) else 0
+    pl = None if planes is None else np.ascontiguousarray(np.asarray(planes, np.float32).reshape(24))
+    n = C.c_int64(0)
+    ms = load().rtoh_render_octree_planes_ms(root._h, grid._h, kind, None if pl is None else pl.ctypes.data, _f(extraMargin), C.byref(n))
+    return float(ms), int(n.value)
 
 
 def freeOctree(root: OctreeNode | None):
@@ -481,6 +536,18 @@ class RayTracerBVH:
         t = np.ascontiguousarray(np.asarray(tris, np.int32).reshape(-1, 3))
         return bool(load().rtoh_rt_load_mesh(self._h, v.ctypes.data, len(v), t.ctypes.data, len(t), _f(voxelSize), int(recenterPasses),
                                              1 if triangles else 0))
+
+    def extractMesh(self, kind: int, camera: "Camera | None" = None, aspect: float = 1.0, extraMargin: float = 50.0, planes=None) -> np.ndarray:
+        """Addition: RayTracerBVH::extractMesh -- the list renderOctree returns for this camera (kind 0: MarchingCubesRenderer, 1:
+        VoxelCubeRenderer), made on the GPU; camera None: extractMeshPlanes over `planes` (None: nothing
+        culled).  (n, 18) float32; empty with lastError set on an error."""
+        pl = None if planes is None else np.ascontiguousarray(np.asarray(planes, np.float32).reshape(24))
+        n = C.c_int64(0)
+        lst = load().rtoh_rt_extract_mesh(self._h, int(kind), camera._h if camera is not None else None, _f(aspect),
+                                          None if pl is None else pl.ctypes.data, _f(extraMargin), C.byref(n))
+        out = np.zeros((n.value, 18), np.float32)
+        load().rtoh_tris_take(lst, out.ctypes.data)                # one extraction: copied out and freed
+        return out
 
     def grid(self) -> np.ndarray:
         """Addition: RayTracerBVH::grid -- the current voxels, uint8 (dimZ, dimY, dimX), every edit applied."""

@@ -10,6 +10,13 @@ Frustum::Frustum(const rtmath::mat4& viewProj) {
         for (int k = 0; k < 4; k++) m_planes[i][k] = flat[i * 4 + k];
 }
 
+Frustum Frustum::fromPlanes(const float planes[24]) {
+    Frustum f;
+    for (int i = 0; i < COUNT; i++)
+        for (int k = 0; k < 4; k++) f.m_planes[i][k] = planes[i * 4 + k];
+    return f;
+}
+
 int Frustum::testAABB(const vec3& min, const vec3& max, float extraMargin) const {
     const vec3 lo = min - vec3(extraMargin), hi = max + vec3(extraMargin);
     int verdict = 1;

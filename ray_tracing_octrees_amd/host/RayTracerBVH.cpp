@@ -48,6 +48,9 @@ struct HipApi {
     decltype(&rto_render_lit_host) render_lit_host = nullptr;
     decltype(&rto_render_lit_triangles_host) render_lit_triangles_host = nullptr;
     decltype(&rto_voxelize_mesh) voxelize_mesh = nullptr;
+    decltype(&rto_frustum_planes) frustum_planes = nullptr;
+    decltype(&rto_extract_mesh) extract_mesh = nullptr;
+    decltype(&rto_download_mesh) download_mesh = nullptr;
     std::string error;
 
     bool load() {
@@ -106,6 +109,9 @@ struct HipApi {
         render_lit_host = reinterpret_cast<decltype(render_lit_host)>(sym("rto_render_lit_host"));
         render_lit_triangles_host = reinterpret_cast<decltype(render_lit_triangles_host)>(sym("rto_render_lit_triangles_host"));
         voxelize_mesh = reinterpret_cast<decltype(voxelize_mesh)>(sym("rto_voxelize_mesh"));
+        frustum_planes = reinterpret_cast<decltype(frustum_planes)>(sym("rto_frustum_planes"));
+        extract_mesh = reinterpret_cast<decltype(extract_mesh)>(sym("rto_extract_mesh"));
+        download_mesh = reinterpret_cast<decltype(download_mesh)>(sym("rto_download_mesh"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -457,6 +463,53 @@ bool RayTracerBVH::pickSpan(const Camera& camera, int px, int py, int width, int
     }
     out = to_ray_span(s);
     return out.hit();
+}
+
+std::vector<MCTriangle> RayTracerBVH::extractMeshPlanes(int kind, const float* planes, float extraMargin) {
+    std::vector<MCTriangle> out;
+    m_lastError.clear();                       // an empty list with lastError() empty is an empty mesh, not a failure
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "extractMesh: compute pipeline not initialized or failed";
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return out;
+    }
+    if (m_numNodes <= 0) {
+        m_lastError = "extractMesh: no octree set";
+        return out;
+    }
+    rto_mesh_cull cull;
+    if (planes) { std::memcpy(cull.planes, planes, sizeof cull.planes); cull.margin = extraMargin; }
+    int64_t n = 0;
+    if (api().extract_mesh(m_ctx, kind, planes ? &cull : nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] extractMesh failed: " << m_lastError << std::endl;
+        return out;
+    }
+    std::vector<float> rec((size_t)n * 12);
+    if (n > 0 && api().download_mesh(m_ctx, rec.data(), n, nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] extractMesh failed: " << m_lastError << std::endl;
+        return out;
+    }
+    out.resize((size_t)n);
+    for (size_t i = 0; i < out.size(); i++) {
+        const float* r = rec.data() + 12 * i;
+        for (int v = 0; v < 3; v++) out[i].v[v] = rto_host::vec3(r[3 * v], r[3 * v + 1], r[3 * v + 2]);
+        out[i].normal[0] = out[i].normal[1] = out[i].normal[2] = rto_host::vec3(r[9], r[10], r[11]);
+    }
+    return out;
+}
+
+std::vector<MCTriangle> RayTracerBVH::extractMesh(int kind, const Camera& camera, float aspect, float extraMargin) {
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "extractMesh: compute pipeline not initialized or failed";
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return {};
+    }
+    const rto_frame f = frame_of(camera, 1, 1, aspect, 45.0f);       // renderOctree's own frustum: fov 45 (main.cpp:125)
+    float planes[24];
+    api().frustum_planes(f.view, 45.0f, aspect, planes);
+    return extractMeshPlanes(kind, planes, extraMargin);
 }
 
 // The renders' ray direction through pixel (px, py) (S/RT:338-355 in the oracle's operation order: what fill_params and

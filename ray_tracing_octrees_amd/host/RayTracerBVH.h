@@ -175,6 +175,13 @@ public:
     // nTris faces of three row indices.  AUTO grid from voxelSize; false (lastError()) on any error.  grid() downloads the result.
     bool loadMesh(const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize, int recenterPasses = 0,
                   bool triangles = false);
+    // The mesh of what the camera sees, made on the GPU (rto_extract_mesh): the list the reference's
+    // renderOctree(root, grid, renderer, camera, aspect, extraMargin) returns for MarchingCubesRenderer (kind MeshMC; needs
+    // buildLeafTriangles()) or VoxelCubeRenderer (kind MeshCubes; needs a resident grid: setOctreeFromGrid, loadMesh or an edit),
+    // in its order.  Empty, with lastError set, on an error.  extractMeshPlanes: caller-supplied planes (nullptr: nothing culled).
+    enum MeshKind { MeshMC = RTO_MESH_MC, MeshCubes = RTO_MESH_CUBES };
+    std::vector<MCTriangle> extractMesh(int kind, const Camera& camera, float aspect, float extraMargin = 50.0f);
+    std::vector<MCTriangle> extractMeshPlanes(int kind, const float* planes, float extraMargin);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

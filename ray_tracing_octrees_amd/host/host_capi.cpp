@@ -1,6 +1,7 @@
 // host_capi.cpp -- extern "C" doors onto the C++ host layer so Python (tests, bench.py) can drive the
 // same classes a C++ application would: VoxelGrid / createOctreeFromVoxelGrid / Camera / Frustum /
 // CacheUtils / RayTracerBVH.  Pure plumbing; no algorithm lives here.
+#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -94,6 +95,39 @@ int64_t rtoh_local_mc(const VoxelGrid* g, int x0, int y0, int z0, int size, floa
 int64_t rtoh_mc_renderer(const OctreeNode* root, const VoxelGrid* g, float* out, int64_t capacityTris) {
     MarchingCubesRenderer r;
     return copy_tris(r.render(root, *g, root ? root->x : 0, root ? root->y : 0, root ? root->z : 0, root ? root->size : 0), out, capacityTris);
+}
+
+// VoxelCubeRenderer over the whole tree, and renderOctree's walk (kind 0: MarchingCubesRenderer, 1: VoxelCubeRenderer) over
+// caller-supplied planes (NULL: nothing culled) or a camera's own frustum; 18 floats per triangle as above
+int64_t rtoh_cube_renderer(const OctreeNode* root, const VoxelGrid* g, float* out, int64_t capacityTris) {
+    VoxelCubeRenderer r;
+    return copy_tris(r.render(root, *g, root ? root->x : 0, root ? root->y : 0, root ? root->z : 0, root ? root->size : 0), out, capacityTris);
+}
+int64_t rtoh_render_octree_planes(const OctreeNode* root, const VoxelGrid* g, int kind, const float* planes, float margin, float* out,
+                                  int64_t capacityTris) {
+    MarchingCubesRenderer mc;
+    VoxelCubeRenderer vc;
+    Renderer& r = kind == 0 ? static_cast<Renderer&>(mc) : static_cast<Renderer&>(vc);
+    return copy_tris(renderOctreePlanes(root, *g, r, planes, margin), out, capacityTris);
+}
+// the same walk timed where it runs, as the reference times its own (main.cpp prints renderOctree's milliseconds): returns the
+// milliseconds of one walk, the list's length in *numTris; nothing is copied
+double rtoh_render_octree_planes_ms(const OctreeNode* root, const VoxelGrid* g, int kind, const float* planes, float margin, int64_t* numTris) {
+    MarchingCubesRenderer mc;
+    VoxelCubeRenderer vc;
+    Renderer& r = kind == 0 ? static_cast<Renderer&>(mc) : static_cast<Renderer&>(vc);
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<MCTriangle> tris = renderOctreePlanes(root, *g, r, planes, margin);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (numTris) *numTris = (int64_t)tris.size();
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
+int64_t rtoh_render_octree(const OctreeNode* root, const VoxelGrid* g, int kind, const Camera* cam, float aspect, float margin, float* out,
+                           int64_t capacityTris) {
+    MarchingCubesRenderer mc;
+    VoxelCubeRenderer vc;
+    Renderer& r = kind == 0 ? static_cast<Renderer&>(mc) : static_cast<Renderer&>(vc);
+    return copy_tris(renderOctree(root, *g, r, *cam, aspect, margin), out, capacityTris);
 }
 
 // leaf-triangle buffer for the triangle ray path: returns the triangle count; call with tris == NULL to size
@@ -280,6 +314,19 @@ void rtoh_rt_grid(const RayTracerBVH* rt, int dims[3], uint8_t* out) {
 int rtoh_rt_load_mesh(RayTracerBVH* rt, const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize,
                       int recenterPasses, int triangles) {
     return rt->loadMesh(xyz, nVerts, tris, nTris, voxelSize, recenterPasses, triangles != 0) ? 1 : 0;
+}
+// RayTracerBVH::extractMesh (cam != NULL) / extractMeshPlanes, once: returns the list and its length; rtoh_tris_take copies it out
+// (18 floats per triangle; out may be NULL) and frees it
+void* rtoh_rt_extract_mesh(RayTracerBVH* rt, int kind, const Camera* cam, float aspect, const float* planes, float margin, int64_t* numTris) {
+    auto* list = new std::vector<MCTriangle>(cam ? rt->extractMesh(kind, *cam, aspect, margin) : rt->extractMeshPlanes(kind, planes, margin));
+    *numTris = (int64_t)list->size();
+    return list;
+}
+void rtoh_tris_take(void* list, float* out) {
+    auto* tris = static_cast<std::vector<MCTriangle>*>(list);
+    if (!tris) return;
+    copy_tris(*tris, out, (int64_t)tris->size());
+    delete tris;
 }
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }

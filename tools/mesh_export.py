@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Extracts the mesh of a voxel grid on the GPU (Context.extract_mesh) and writes it as binary STL.
+
+    python3 tools/mesh_export.py --sphere 128 --kind cubes out.stl
+    python3 tools/mesh_export.py --cache sceneCache.bin --kind mc --camera 0.6 0.5 3500 --margin 50 out.stl
+
+Binary STL: an 80-byte header, a uint32 count, then 50 bytes per triangle -- normal, v0, v1, v2 as 12 float32 and a uint16 of
+zero: our (v0, v1, v2, normal) records reordered.  write_stl / read_stl are the round trip (read_stl returns our layout)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("v", "<f4", (9,)), ("attr", "<u2")])
+
+
+def write_stl(path, tris, header=b"ray_tracing_octrees_amd mesh"):
+    """tris: (n, 12) float32, v0, v1, v2, normal."""
+    tris = np.asarray(tris, np.float32).reshape(-1, 12)
+    rec = np.zeros(len(tris), STL_DTYPE)
+    rec["normal"] = tris[:, 9:12]
+    rec["v"] = tris[:, 0:9]
+    with open(path, "wb") as f:
+        f.write(header[:80].ljust(80, b"\0"))
+        f.write(np.uint32(len(tris)).tobytes())
+        f.write(rec.tobytes())
+
+
+def read_stl(path):
+    """(n, 12) float32 in our layout: v0, v1, v2, normal."""
+    with open(path, "rb") as f:
+        f.seek(80)
+        n = int(np.frombuffer(f.read(4), "<u4")[0])
+        rec = np.frombuffer(f.read(n * STL_DTYPE.itemsize), STL_DTYPE)
+    if len(rec) != n:
+        raise ValueError(f"{path}: {n} triangles announced, {len(rec)} present")
+    return np.ascontiguousarray(np.concatenate([rec["v"], rec["normal"]], 1), dtype=np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--sphere", type=int, metavar="DIM", help="the test shell sphere of this edge")
+    src.add_argument("--cache", metavar="FILE", help="a sceneCache.bin voxel grid")
+    ap.add_argument("--kind", choices=("mc", "cubes"), default="cubes")
+    ap.add_argument("--camera", type=float, nargs=3, metavar=("THETA", "PHI", "RADIUS"), help="cull with this orbit camera's frustum (fov 45)")
+    ap.add_argument("--aspect", type=float, default=16.0 / 9.0)
+    ap.add_argument("--margin", type=float, default=50.0)
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("out")
+    args = ap.parse_args()
+    import ray_tracing_octrees_amd as rto
+    from ray_tracing_octrees_amd import hip
+
+    grid = rto.VoxelGrid.test_sphere(args.sphere) if args.sphere else rto.loadVoxelGrid(args.cache)
+    if grid is None:
+        sys.exit(f"cannot read {args.cache}")
+    ctx = rto.Context(args.gpu)
+    ctx.build_octree(grid.data, grid.min, grid.voxelSize)
+    kind = hip.MESH_MC if args.kind == "mc" else hip.MESH_CUBES
+    if kind == hip.MESH_MC:
+        ctx.build_leaf_triangles()
+    planes = None
+    if args.camera:
+        planes = ctx.frustum_planes(rto.Camera(*args.camera).getView(), 45.0, args.aspect)
+    tris, _ = ctx.extract_mesh(kind, planes, args.margin)
+    write_stl(args.out, tris)
+    print(f"{args.out}: {len(tris)} triangles, device ms (count, rank, emit) = {ctx.last_mesh_ms()}")
+
+
+if __name__ == "__main__":
+    main()
