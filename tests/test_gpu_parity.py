@@ -1856,6 +1856,8 @@ def test_gpu_leaf_triangle_build_equals_the_host_builders(ctx, orc, scenes, scen
     """rto_build_leaf_triangles: the buffer MarchingCubesRenderer/localMC would emit per leaf, built in HBM -- the same
     bytes as the oracle's builder (itself pinned by the reference's localMC triangles) and as the product's C++ one;
     for an uploaded octree + voxels and for rto_build_octree + the voxels it kept."""
+    # These scenes never reach a candidate total of 64, 65, 2048 or above, and clip big leaves by one voxel at most: the builder's
+    # thread / wave / chunk classes and its seven clip masks are pinned one by one in tests/test_leaf_triangle_edges.py.
     s = scenes(scene)
     wt, wo = orc.build_leaf_triangles(s.grid, s.nodes)
     upload(ctx, s)
