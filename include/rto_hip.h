@@ -741,6 +741,78 @@ int  rto_render_lit_triangles_device(rto_context* ctx, const rto_frame* frame, c
 int  rto_render_lit_triangles_host(rto_context* ctx, const rto_frame* frame, const rto_lighting* lighting, float* host_rgba,
                                    int32_t* host_vis /* may be NULL */);
 
+/* ---- region queries ---------------------------------------------------------
+ * Questions about a place instead of a ray: which leaf holds a point, how much solid a brush covers, how far the nearest solid
+ * is.  No reference counterpart as an API: the click handler (S/main.cpp:646-700) answers the first by a CPU march over the dense
+ * grid.  Every result is an integer that a brute-force count over the grid reproduces bit for bit.
+ *
+ * Rule, exact in integers at 1/64 voxel, the voxel edits' quantisation:
+ *   point     pq[a] = floor((p[a] - gridMin[a]) / voxelSize * 64 + 0.5), in double from the context's float gridMin / voxelSize
+ *             (rto_point_quantize).  Invalid: a NaN or infinite component, or |pq[a]| > 2^27.
+ *   region    an rto_brush; cq, eq as rto_brush_quantize gives them.  Invalid exactly when rto_brush_quantize refuses the brush
+ *             with its `op` field set to RTO_EDIT_CARVE: the op is ignored.
+ *   invalid   records are marked in the output (below) and never make the call fail, as NaN rays are misses in the ray queries.
+ *   reach     the walk starts at node 0 and descends through nodes with isLeaf == 0 && isUniform == 0; every other node it meets
+ *             is a leaf, solid when isSolid == 1.  A leaf the walk does not reach does not exist.  rto_update_frustum is ignored.
+ *             A child's box lies inside its parent's (every octree; an uploaded array that breaks this is walked as if it held:
+ *             a subtree is dropped when its root's box is out of the question's reach).
+ *   dims      the domain: with a resident grid (rto_build_octree, rto_voxelize_mesh, after rto_edit_voxels) that grid's dims,
+ *             [0, dims[a]) per axis; for an octree from rto_upload_octree the cube [x, x + size) of node 0 on each axis.
+ * Point location: voxel i[a] = pq[a] >> 6 (floor).  The answer is the reached leaf whose box [x, x + size) holds i on every axis;
+ *   where several do (a non-canonical array) the lowest node index wins.
+ * Brush census: voxel (i0, i1, i2) is covered exactly when the edit rule says the brush touches it: D[a] = 64 (2 i[a] + 1) -
+ *   2 cq[a]; SPHERE: D0^2 + D1^2 + D2^2 <= (2 eq[0])^2; BOX: |D[a]| <= 2 eq[a] on every axis; all in int64.  On an octree built
+ *   from a grid, filled = the FILLED covered voxels of rto_download_voxels, a CARVE of the brush reports changed == filled and a
+ *   FILL changed == covered - filled.  (filled < 2^63 always: the domain holds at most 2^60 voxels of an octree of depth 20.)
+ * Nearest solid: mq = floor(max_dist / voxelSize * 64 + 0.5) in double; the record is invalid when the point is, when max_dist
+ *   is NaN or negative, or when mq > 2^28; max_dist = +inf is no limit.  A reached solid leaf's box in 1/64 units is
+ *   [64 x, 64 (x + size)] per axis, closed; c[a] = clamp(pq[a], lo, hi), dist2 = sum (pq[a] - c[a])^2 in int64.  The answer is the
+ *   least dist2 with dist2 <= mq^2, ties to the lowest node index.  dist2 == 0 exactly when pq lies in a closed solid box.
+ * Alignment (16 bytes, every buffer), n == 0 and the error codes are those of rto_query_rays_*: RTO_E_INVALID for a NULL buffer,
+ * n < 0 or a misaligned buffer, RTO_E_NO_OCTREE for nothing uploaded.  Every octree the ray queries accept is accepted: a tree that
+ * is one leaf, non-canonical arrays.  _device: asynchronous on hip_stream, device buffers, allocates nothing.  _host: synchronous,
+ * host buffers.  rto_set_kernel does not apply.
+ * Cost: a partly covered SPHERE region is counted row by row (one integer square root per row of voxels along x), so a sphere
+ * costs its cross-section in rows where it cuts a solid leaf or the domain's faces; everything else is closed form. */
+typedef struct rto_point_hit {      /* 32 bytes */
+    int32_t node;                   /* index in the resident array; -1: outside every reached leaf, or an invalid point */
+    int32_t solid;                  /* 1 when that leaf is solid; 0 otherwise and for node == -1 */
+    int32_t x, y, z, size;          /* the leaf's box, voxel units; 0 for node == -1 */
+    int32_t depth;                  /* levels below the root (nodes descended through) */
+    int32_t reserved;               /* 0 */
+} rto_point_hit;
+
+typedef struct rto_region {         /* 32 bytes */
+    int64_t filled;                 /* covered voxels inside reached solid leaves (each leaf's box clipped to dims); -1: invalid */
+    int64_t covered;                /* covered voxels inside dims; -1: invalid */
+    int32_t solid_leaves;           /* reached solid leaves holding at least one covered voxel inside dims */
+    int32_t first_node;             /* the lowest index among them; -1: none */
+    int32_t reserved[2];            /* 0 */
+} rto_region;
+
+typedef struct rto_near_point {     /* 16 bytes: the input of the nearest-solid query */
+    float x, y, z, max_dist;        /* world units; max_dist >= 0, +inf: no limit */
+} rto_near_point;
+
+typedef struct rto_nearest {        /* 32 bytes */
+    int64_t dist2;                  /* squared distance in 1/64-voxel units; -1: no solid within max_dist, or invalid */
+    int32_t node;                   /* the solid leaf; -1 with dist2 == -1 */
+    int32_t size;                   /* its size, voxel units; 0 with dist2 == -1 */
+    int32_t cq[3];                  /* the closest point c of its closed box, 1/64-voxel units; 0 with dist2 == -1 */
+    int32_t reserved;               /* 0 */
+} rto_nearest;
+
+/* points: n records of 3 floats (x, y, z), 12 bytes each; the buffer 16-byte aligned. */
+int  rto_query_points_device(rto_context* ctx, const float* d_points, int64_t n, rto_point_hit* d_hits, void* hip_stream);
+int  rto_query_points_host(rto_context* ctx, const float* points, int64_t n, rto_point_hit* hits);
+int  rto_query_regions_device(rto_context* ctx, const rto_brush* d_brushes, int64_t n, rto_region* d_regions, void* hip_stream);
+int  rto_query_regions_host(rto_context* ctx, const rto_brush* brushes, int64_t n, rto_region* regions);
+int  rto_query_nearest_device(rto_context* ctx, const rto_near_point* d_points, int64_t n, rto_nearest* d_out, void* hip_stream);
+int  rto_query_nearest_host(rto_context* ctx, const rto_near_point* points, int64_t n, rto_nearest* out);
+/* Pure host function, no device: pq of the rule above for this grid; RTO_E_INVALID for an invalid point, a NULL argument or a
+ * voxel_size that is not finite and positive. */
+int  rto_point_quantize(const float p[3], const float grid_min[3], float voxel_size, int64_t pq[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

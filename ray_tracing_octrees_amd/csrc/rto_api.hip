@@ -2723,3 +2723,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_lit.inc"
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
+#include "rto_region.inc"

@@ -43,6 +43,8 @@ SYMBOLS = (
     "rto_render_lit_triangles_device", "rto_render_lit_triangles_host",
     "rto_voxelize_mesh", "rto_last_voxelize_ms",
     "rto_frustum_planes", "rto_extract_mesh", "rto_mesh_device", "rto_download_mesh", "rto_last_mesh_ms",
+    "rto_query_points_device", "rto_query_points_host", "rto_query_regions_device", "rto_query_regions_host",
+    "rto_query_nearest_device", "rto_query_nearest_host", "rto_point_quantize",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -64,6 +66,13 @@ BRUSH_SPHERE, BRUSH_BOX = 0, 1
 EDIT_CARVE, EDIT_FILL = 0, 1
 EDIT_MAX_BRUSHES = 65536
 BRUSH_DTYPE = np.dtype([("centre", "<f4", (3,)), ("extent", "<f4", (3,)), ("shape", "<i4"), ("op", "<i4")])
+# struct rto_point_hit / rto_region / rto_near_point / rto_nearest: region queries (rto_query_points_*, _regions_*, _nearest_*)
+POINT_HIT_DTYPE = np.dtype([("node", "<i4"), ("solid", "<i4"), ("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("size", "<i4"),
+                            ("depth", "<i4"), ("reserved", "<i4")])
+REGION_DTYPE = np.dtype([("filled", "<i8"), ("covered", "<i8"), ("solid_leaves", "<i4"), ("first_node", "<i4"),
+                         ("reserved", "<i4", (2,))])
+NEAR_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("max_dist", "<f4")])
+NEAREST_DTYPE = np.dtype([("dist2", "<i8"), ("node", "<i4"), ("size", "<i4"), ("cq", "<i4", (3,)), ("reserved", "<i4")])
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -185,6 +194,27 @@ def brush_quantize(brush, grid_min, voxel_size):
     if rc != RTO_OK:
         raise RtoError(rc, "rto_brush_quantize: invalid brush")
     return tuple(cq), tuple(eq)
+
+
+def point_quantize(p, grid_min, voxel_size):
+    """rto_point_quantize: pq as a tuple of int for one point; RtoError(RTO_E_INVALID) for an invalid point."""
+    L = load()
+    pt = (C.c_float * 3)(*[_f(x) for x in p])
+    gm = (C.c_float * 3)(*[_f(x) for x in grid_min])
+    pq = (C.c_int64 * 3)()
+    rc = L.rto_point_quantize(pt, gm, _f(voxel_size), pq)
+    if rc != RTO_OK:
+        raise RtoError(rc, "rto_point_quantize: invalid point")
+    return tuple(pq)
+
+
+def make_near_points(points, max_dist=np.inf) -> np.ndarray:
+    """A NEAR_POINT_DTYPE array from (n, 3) points and one max_dist or one per point."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    r = np.zeros(len(p), NEAR_POINT_DTYPE)
+    r["x"], r["y"], r["z"] = p[:, 0], p[:, 1], p[:, 2]
+    r["max_dist"] = np.broadcast_to(np.asarray(max_dist, np.float32), len(p))
+    return r
 
 
 class Stats(C.Structure):
@@ -355,6 +385,13 @@ def load():
     L.rto_edit_voxels.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int64)]
     L.rto_download_voxels.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
     L.rto_last_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_query_points_device.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.rto_query_points_host.argtypes = [vp, vp, C.c_int64, vp]
+    L.rto_query_regions_device.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.rto_query_regions_host.argtypes = [vp, vp, C.c_int64, vp]
+    L.rto_query_nearest_device.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.rto_query_nearest_host.argtypes = [vp, vp, C.c_int64, vp]
+    L.rto_point_quantize.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64)]
     L.rto_brush_quantize.argtypes = [vp, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rto_render_lit_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp, vp]
     L.rto_render_lit_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(Lighting), vp, vp]
@@ -874,6 +911,56 @@ class Context:
         ms = (C.c_float * 3)()
         self._check(self._L.rto_last_edit_ms(self._h, ms))
         return tuple(ms)
+
+    # -- region queries --------------------------------------------------------
+    def query_points(self, points) -> np.ndarray:
+        """Which leaf holds each point (rto_query_points_host): points (n, 3) world positions.  A POINT_HIT_DTYPE array; node -1
+        for a point outside every leaf or an invalid one (NaN, infinite, beyond 2^21 voxels)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        hits = np.zeros(len(p), POINT_HIT_DTYPE)
+        self._check(self._L.rto_query_points_host(self._h, p.ctypes.data if len(p) else None, len(p), hits.ctypes.data if len(p) else None))
+        return hits
+
+    def query_points_device(self, d_points: int, n: int, d_hits: int, stream: int = 0):
+        """Asynchronous: n points of 3 floats at d_points -> n rto_point_hit records at d_hits (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_points_device(self._h, C.c_void_p(d_points) if d_points else None, int(n),
+                                                    C.c_void_p(d_hits) if d_hits else None, C.c_void_p(stream) if stream else None))
+
+    def query_regions(self, brushes) -> np.ndarray:
+        """How much solid each brush covers (rto_query_regions_host): BRUSH_DTYPE records (make_brushes; the op is ignored).  A
+        REGION_DTYPE array; filled = covered = -1 for an invalid brush.  A CARVE of the brush would change `filled` voxels, a FILL
+        `covered - filled`."""
+        b = np.ascontiguousarray(np.asarray(brushes, BRUSH_DTYPE).reshape(-1))
+        out = np.zeros(len(b), REGION_DTYPE)
+        self._check(self._L.rto_query_regions_host(self._h, b.ctypes.data if len(b) else None, len(b), out.ctypes.data if len(b) else None))
+        return out
+
+    def query_regions_device(self, d_brushes: int, n: int, d_regions: int, stream: int = 0):
+        """Asynchronous: n rto_brush records at d_brushes -> n rto_region records at d_regions (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_regions_device(self._h, C.c_void_p(d_brushes) if d_brushes else None, int(n),
+                                                     C.c_void_p(d_regions) if d_regions else None, C.c_void_p(stream) if stream else None))
+
+    def query_nearest_records(self, points, max_dist=np.inf) -> np.ndarray:
+        """The NEAREST_DTYPE records of rto_query_nearest_host: points (n, 3), max_dist one value or one per point (+inf: no limit)."""
+        p = make_near_points(points, max_dist)
+        out = np.zeros(len(p), NEAREST_DTYPE)
+        self._check(self._L.rto_query_nearest_host(self._h, p.ctypes.data if len(p) else None, len(p), out.ctypes.data if len(p) else None))
+        return out
+
+    def query_nearest(self, points, max_dist=np.inf):
+        """The nearest solid to each point: (records, distance).  records: NEAREST_DTYPE (dist2 -1: none within max_dist, or an
+        invalid record); distance: float64 world units, sqrt(dist2) / 64 * voxelSize computed on the host in double, inf where
+        dist2 is -1."""
+        rec = self.query_nearest_records(points, max_dist)
+        vs = float(self.scene_bounds().voxel_size) if len(rec) else 0.0
+        d2 = rec["dist2"].astype(np.float64)
+        dist = np.where(rec["dist2"] >= 0, np.sqrt(np.maximum(d2, 0.0)) / 64.0 * vs, np.inf)
+        return rec, dist
+
+    def query_nearest_device(self, d_points: int, n: int, d_out: int, stream: int = 0):
+        """Asynchronous: n rto_near_point records at d_points -> n rto_nearest records at d_out (device pointers, 16-byte aligned)."""
+        self._check(self._L.rto_query_nearest_device(self._h, C.c_void_p(d_points) if d_points else None, int(n),
+                                                     C.c_void_p(d_out) if d_out else None, C.c_void_p(stream) if stream else None))
 
     # -- mesh voxelization -----------------------------------------------------
     def voxelize_mesh(self, xyz, tris, voxel_size, grid=None, recenter=0, triangles=False) -> VoxelizeResult:

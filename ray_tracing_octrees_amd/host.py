@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import BRUSH_DTYPE, HIT_DTYPE, NODE_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE, RtoError, _f
+from .hip import (BRUSH_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+                  RtoError, _f)
 
 _lib = None
 _vp = C.c_void_p
@@ -133,6 +134,12 @@ def load():
     L.rtoh_rt_intersect_triangles.restype = None
     L.rtoh_rt_pick_surface.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp]
     L.rtoh_rt_pick_surface.restype = C.c_int
+    L.rtoh_rt_locate.argtypes = [_vp, _vp, C.c_int64, _vp]
+    L.rtoh_rt_locate.restype = C.c_int
+    L.rtoh_rt_census.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
+    L.rtoh_rt_census.restype = C.c_int
+    L.rtoh_rt_nearest_solid.argtypes = [_vp, _vp, C.c_int64, C.c_float, _vp, _vp]
+    L.rtoh_rt_nearest_solid.restype = C.c_int
     L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
     L.rtoh_rt_edit_voxels.restype = C.c_int64
     L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
@@ -528,6 +535,33 @@ class RayTracerBVH:
         shapes = np.ascontiguousarray(b["shape"], dtype=np.int32)
         ops = np.ascontiguousarray(b["op"], dtype=np.int32)
         return int(load().rtoh_rt_edit_voxels(self._h, f.ctypes.data, shapes.ctypes.data, ops.ctypes.data, len(b)))
+
+    def locate(self, points):
+        """Addition: RayTracerBVH::locate -- the leaf that holds each of the (n, 3) points: (code, hip.POINT_HIT_DTYPE records).
+        code is RTO_OK or the refusal's (lastError)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        hits = np.zeros(len(p), POINT_HIT_DTYPE)
+        rc = load().rtoh_rt_locate(self._h, p.ctypes.data, len(p), hits.ctypes.data)
+        return int(rc), hits
+
+    def census(self, brushes):
+        """Addition: RayTracerBVH::census -- what each hip.BRUSH_DTYPE brush covers (the op is ignored): (code, hip.REGION_DTYPE
+        records)."""
+        b = np.asarray(brushes, BRUSH_DTYPE).reshape(-1)
+        f = np.ascontiguousarray(np.concatenate([b["centre"], b["extent"]], 1), dtype=np.float32)
+        shapes = np.ascontiguousarray(b["shape"], dtype=np.int32)
+        out = np.zeros(len(b), REGION_DTYPE)
+        rc = load().rtoh_rt_census(self._h, f.ctypes.data, shapes.ctypes.data, len(b), out.ctypes.data)
+        return int(rc), out
+
+    def nearestSolid(self, points, maxDist: float = float("inf")):
+        """Addition: RayTracerBVH::nearestSolid -- the nearest solid leaf to each of the (n, 3) points within maxDist: (code,
+        hip.NEAREST_DTYPE records, distances in world units as float64, inf where there is none)."""
+        p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+        out = np.zeros(len(p), NEAREST_DTYPE)
+        dist = np.zeros(len(p), np.float64)
+        rc = load().rtoh_rt_nearest_solid(self._h, p.ctypes.data, len(p), _f(maxDist), out.ctypes.data, dist.ctypes.data)
+        return int(rc), out, dist
 
     def loadMesh(self, xyz, tris, voxelSize, recenterPasses=0, triangles=False) -> bool:
         """Addition: RayTracerBVH::loadMesh -- rows (n, 3) and faces (m, 3) of row indices voxelized on every GPU (AUTO grid),

@@ -51,6 +51,10 @@ struct HipApi {
     decltype(&rto_frustum_planes) frustum_planes = nullptr;
     decltype(&rto_extract_mesh) extract_mesh = nullptr;
     decltype(&rto_download_mesh) download_mesh = nullptr;
+    decltype(&rto_query_points_host) query_points_host = nullptr;
+    decltype(&rto_query_regions_host) query_regions_host = nullptr;
+    decltype(&rto_query_nearest_host) query_nearest_host = nullptr;
+    decltype(&rto_scene_bounds_get) scene_bounds_get = nullptr;
     std::string error;
 
     bool load() {
@@ -112,6 +116,10 @@ struct HipApi {
         frustum_planes = reinterpret_cast<decltype(frustum_planes)>(sym("rto_frustum_planes"));
         extract_mesh = reinterpret_cast<decltype(extract_mesh)>(sym("rto_extract_mesh"));
         download_mesh = reinterpret_cast<decltype(download_mesh)>(sym("rto_download_mesh"));
+        query_points_host = reinterpret_cast<decltype(query_points_host)>(sym("rto_query_points_host"));
+        query_regions_host = reinterpret_cast<decltype(query_regions_host)>(sym("rto_query_regions_host"));
+        query_nearest_host = reinterpret_cast<decltype(query_nearest_host)>(sym("rto_query_nearest_host"));
+        scene_bounds_get = reinterpret_cast<decltype(scene_bounds_get)>(sym("rto_scene_bounds_get"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -632,6 +640,81 @@ void RayTracerBVH::renderSceneComputeWithCulling(const Camera& camera, int width
         if (!forEachContext([&](rto_context* c) { return api().update_frustum(c, &view[0][0], fovDeg, aspect, 1); }, "frustum update")) return;
     }
     render(camera, width, height, aspect, fovDeg);
+}
+
+// ---- region queries: the C ABI's records, one per point or brush; a refusal leaves the defaults and returns its code
+int RayTracerBVH::regionFailed(int rc, const char* what) {
+    m_lastError = api().last_error(m_ctx);
+    std::cerr << "[RayTracerBVH] " << what << " failed: " << m_lastError << std::endl;
+    return rc;
+}
+
+int RayTracerBVH::locate(const std::vector<rto_host::vec3>& points, std::vector<PointLocation>& out) {
+    out.assign(points.size(), PointLocation());
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "locate: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (points.empty()) return RTO_OK;
+    std::vector<float> in(3 * points.size());
+    for (size_t i = 0; i < points.size(); i++) { in[3 * i] = points[i].x; in[3 * i + 1] = points[i].y; in[3 * i + 2] = points[i].z; }
+    std::vector<rto_point_hit> hits(points.size());
+    const int rc = api().query_points_host(m_ctx, in.data(), (int64_t)points.size(), hits.data());
+    if (rc != RTO_OK) return regionFailed(rc, "locate");
+    for (size_t i = 0; i < hits.size(); i++) {
+        const rto_point_hit& h = hits[i];
+        PointLocation& o = out[i];
+        o.node = h.node; o.solid = h.solid != 0; o.x = h.x; o.y = h.y; o.z = h.z; o.size = h.size; o.depth = h.depth;
+    }
+    return RTO_OK;
+}
+
+int RayTracerBVH::census(const std::vector<VoxelBrush>& regions, std::vector<RegionCensus>& out) {
+    out.assign(regions.size(), RegionCensus());
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "census: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (regions.empty()) return RTO_OK;
+    std::vector<rto_brush> in(regions.size());
+    for (size_t i = 0; i < regions.size(); i++) {
+        const VoxelBrush& v = regions[i];
+        in[i] = rto_brush{ { v.centre.x, v.centre.y, v.centre.z }, { v.extent.x, v.extent.y, v.extent.z }, v.shape, v.op };
+    }
+    std::vector<rto_region> res(regions.size());
+    const int rc = api().query_regions_host(m_ctx, in.data(), (int64_t)in.size(), res.data());
+    if (rc != RTO_OK) return regionFailed(rc, "census");
+    for (size_t i = 0; i < res.size(); i++) {
+        const rto_region& r = res[i];
+        RegionCensus& o = out[i];
+        o.filled = r.filled; o.covered = r.covered; o.solidLeaves = r.solid_leaves; o.firstNode = r.first_node;
+    }
+    return RTO_OK;
+}
+
+int RayTracerBVH::nearestSolid(const std::vector<rto_host::vec3>& points, std::vector<NearestSolid>& out, float maxDist) {
+    out.assign(points.size(), NearestSolid());
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "nearestSolid: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (points.empty()) return RTO_OK;
+    std::vector<rto_near_point> in(points.size());
+    for (size_t i = 0; i < points.size(); i++) in[i] = rto_near_point{ points[i].x, points[i].y, points[i].z, maxDist };
+    std::vector<rto_nearest> res(points.size());
+    const int rc = api().query_nearest_host(m_ctx, in.data(), (int64_t)in.size(), res.data());
+    if (rc != RTO_OK) return regionFailed(rc, "nearestSolid");
+    rto_scene_bounds sb;
+    const int rcb = api().scene_bounds_get(m_ctx, &sb);
+    if (rcb != RTO_OK) return regionFailed(rcb, "nearestSolid");
+    for (size_t i = 0; i < res.size(); i++) {
+        const rto_nearest& r = res[i];
+        NearestSolid& o = out[i];
+        o.dist2 = r.dist2; o.node = r.node; o.size = r.size;
+        for (int a = 0; a < 3; a++) o.cq[a] = r.cq[a];
+        if (r.dist2 >= 0) o.distance = std::sqrt((double)r.dist2) / 64.0 * (double)sb.voxel_size;
+    }
+    return RTO_OK;
 }
 
 // Carve / fill the resident grid on every GPU (rto_edit_voxels) and rebuild the octree there; triangles that were resident are

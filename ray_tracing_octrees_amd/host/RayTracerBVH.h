@@ -10,6 +10,7 @@
 // last frame is available through framebuffer() (RGBA32F, row-major, row 0 = top).
 #pragma once
 
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -93,6 +94,33 @@ struct VoxelBrush {
     int op;
 };
 
+// What the region queries answer (rto_point_hit, rto_region, rto_nearest, include/rto_hip.h), exact in
+// integers at 1/64 voxel.  PointLocation: the leaf that holds a point (node -1: none, or an invalid point).  RegionCensus: the
+// voxels a VoxelBrush covers (its op is ignored) inside the grid and how many of them are solid (both -1: an invalid brush).
+// NearestSolid: the nearest solid leaf, the closest point of its box in 1/64-voxel units and the distance in world units
+// (dist2 -1 and distance +inf: none within maxDist, or an invalid record).
+struct PointLocation {
+    int node = -1;
+    bool solid = false;
+    int x = 0, y = 0, z = 0, size = 0;
+    int depth = 0;
+    bool found() const { return node >= 0; }
+};
+struct RegionCensus {
+    int64_t filled = -1, covered = -1;
+    int solidLeaves = 0;
+    int firstNode = -1;
+    bool valid() const { return covered >= 0; }
+};
+struct NearestSolid {
+    int64_t dist2 = -1;
+    int node = -1;
+    int size = 0;
+    int cq[3] = { 0, 0, 0 };
+    double distance = std::numeric_limits<double>::infinity();
+    bool found() const { return dist2 >= 0; }
+};
+
 // The lit render's terms (rto_lighting, include/rto_hip.h): the direction the light travels, a shadow ray
 // per lit pixel, aoSamples (0..64) ambient-occlusion rays of length aoRadius (world units) per hit pixel, and the hash seed.
 struct Lighting {
@@ -166,6 +194,16 @@ public:
     // click-to-carve: pickSurface (or pick), then editVoxels({{hit.point, vec3(r), VoxelBrush::Sphere, VoxelBrush::Carve}}).
     void editVoxels(const std::vector<VoxelBrush>& brushes);
     int64_t lastEditChanged() const { return m_lastEditChanged; }   // voxels the last editVoxels changed; -1: it failed
+    // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
+    // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
+    // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same
+    // brushes would change (Carve: filled, Fill: covered - filled) before anything is rebuilt, nearestSolid serves camera collision.
+    // Each returns RTO_OK or the refusal's code with lastError set (RTO_E_NO_OCTREE before any octree is set), the records then
+    // at their defaults.
+    int locate(const std::vector<rto_host::vec3>& points, std::vector<PointLocation>& out);
+    int census(const std::vector<VoxelBrush>& regions, std::vector<RegionCensus>& out);
+    int nearestSolid(const std::vector<rto_host::vec3>& points, std::vector<NearestSolid>& out,
+                     float maxDist = std::numeric_limits<float>::infinity());
     // The current grid: what setOctree / setOctreeFromGrid / loadMesh made, with every edit applied (downloaded when first asked
     // after an edit or a loadMesh).
     const VoxelGrid& grid() const;
@@ -225,6 +263,7 @@ private:
     std::vector<rto_comm*> m_comms;           // setDevices(n > 1): the single-process communicator group
     template <class F> bool forEachContext(F&& call, const char* what);
     bool renderFrame(const rto_frame& f, int mode);
+    int regionFailed(int rc, const char* what);
     mutable std::string m_lastError;
 
     mutable std::vector<float> m_frame;

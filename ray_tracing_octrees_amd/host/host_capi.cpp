@@ -305,6 +305,46 @@ int64_t rtoh_rt_edit_voxels(RayTracerBVH* rt, const float* brushes, const int* s
     rt->editVoxels(b);
     return rt->lastEditChanged();
 }
+// RayTracerBVH::locate / census / nearestSolid: the C ABI's records back out; each returns the class's code (RTO_OK or the refusal's)
+int rtoh_rt_locate(RayTracerBVH* rt, const float* points, int64_t n, rto_point_hit* hits) {
+    std::vector<rto_host::vec3> in((size_t)n);
+    for (int64_t i = 0; i < n; i++) in[(size_t)i] = rto_host::vec3(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+    std::vector<PointLocation> out;
+    const int rc = rt->locate(in, out);
+    for (int64_t i = 0; i < n; i++) {
+        const PointLocation& o = out[(size_t)i];
+        hits[i] = rto_point_hit{ o.node, o.solid ? 1 : 0, o.x, o.y, o.z, o.size, o.depth, 0 };
+    }
+    return rc;
+}
+// brushes: n x (cx, cy, cz, ex, ey, ez) floats, shapes: n ints (as rtoh_rt_edit_voxels; the op is ignored)
+int rtoh_rt_census(RayTracerBVH* rt, const float* brushes, const int* shapes, int64_t n, rto_region* regions) {
+    std::vector<VoxelBrush> b((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const float* f = brushes + 6 * i;
+        b[(size_t)i] = VoxelBrush{ rto_host::vec3(f[0], f[1], f[2]), rto_host::vec3(f[3], f[4], f[5]), shapes[i], VoxelBrush::Carve };
+    }
+    std::vector<RegionCensus> out;
+    const int rc = rt->census(b, out);
+    for (int64_t i = 0; i < n; i++) {
+        const RegionCensus& o = out[(size_t)i];
+        regions[i] = rto_region{ o.filled, o.covered, o.solidLeaves, o.firstNode, { 0, 0 } };
+    }
+    return rc;
+}
+// distances: n doubles, world units (+inf where dist2 is -1)
+int rtoh_rt_nearest_solid(RayTracerBVH* rt, const float* points, int64_t n, float maxDist, rto_nearest* res, double* distances) {
+    std::vector<rto_host::vec3> in((size_t)n);
+    for (int64_t i = 0; i < n; i++) in[(size_t)i] = rto_host::vec3(points[3 * i], points[3 * i + 1], points[3 * i + 2]);
+    std::vector<NearestSolid> out;
+    const int rc = rt->nearestSolid(in, out, maxDist);
+    for (int64_t i = 0; i < n; i++) {
+        const NearestSolid& o = out[(size_t)i];
+        res[i] = rto_nearest{ o.dist2, o.node, o.size, { o.cq[0], o.cq[1], o.cq[2] }, 0 };
+        distances[i] = o.distance;
+    }
+    return rc;
+}
 // the class's current grid (RayTracerBVH::grid()), as rtoh_grid_data: dims only when out is NULL
 void rtoh_rt_grid(const RayTracerBVH* rt, int dims[3], uint8_t* out) {
     const VoxelGrid& g = rt->grid();
