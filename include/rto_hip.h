@@ -33,6 +33,7 @@ extern "C" {
 #define RTO_E_NO_DEVICE  -4   /* no usable gfx950 device / ordinal out of range */
 #define RTO_E_UNSUPPORTED -5  /* e.g. packed kernel requested for a non-canonical array */
 #define RTO_E_TIMEOUT    -6   /* rto_comm_flush_timeout: the collective did not complete; the communicator was aborted and is dead */
+#define RTO_E_INTERNAL   -7   /* a bounded device loop hit its cap (rto_label_components): a defect, never an input error */
 
 /* == struct GPUNodes, S/RayTracerBVH.h:21-26 / GLSL OctreeNodeGPUStruct S/RayTracerBVH.cpp:195-204 */
 typedef struct rto_node {
@@ -812,6 +813,68 @@ int  rto_query_nearest_host(rto_context* ctx, const rto_near_point* points, int6
 /* Pure host function, no device: pq of the rule above for this grid; RTO_E_INVALID for an invalid point, a NULL argument or a
  * voxel_size that is not finite and positive. */
 int  rto_point_quantize(const float p[3], const float grid_min[3], float voxel_size, int64_t pq[3]);
+
+/* ---- connected components -------------------------------------------------
+ * Labels the resident grid (rto_build_octree, rto_voxelize_mesh, after edits) and flips whole components: debris left floating by
+ * a carve, the cavity inside a voxelized shell.  No reference counterpart.  Every result is an integer that a brute-force
+ * flood fill over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel (i, j, k) has linear index v = i + dimX (j + dimY k): rto_download_voxels' layout.
+ *   set       RTO_SET_SOLID: the voxels equal to 1; RTO_SET_EMPTY: the voxels equal to 0.  Voxels outside the grid do not exist:
+ *             they belong to no set and connect nothing.
+ *   joined    RTO_CONN_FACE (6): two voxels of the set that differ by 1 on exactly one axis; RTO_CONN_FULL (26): two that differ by
+ *             at most 1 on every axis and are not equal.  Components are the classes of the transitive closure.
+ *   canonical a component's root is the smallest linear index among its voxels; components are numbered 0 .. count - 1 in
+ *             ascending order of root; the label volume holds that number for voxels of the set and -1 for the others.  Nothing
+ *             depends on scheduling.
+ * rto_label_components keeps the label volume (int32 per voxel) and the table resident; they describe the grid they were made
+ * from, and every call that changes or replaces the grid frees them (rto_build_octree, rto_upload_octree, rto_voxelize_mesh,
+ * rto_edit_voxels / rto_edit_components with changed > 0, rto_destroy): the readers then return RTO_E_INVALID.  An empty set
+ * gives count 0, a volume of -1 and an empty table.  Synchronous on the context's stream.
+ * rto_edit_components labels afresh (the resident labels are not consulted), selects components, and flips every voxel of the
+ * selected ones (SOLID -> 0, EMPTY -> 1).  *changed (may be NULL) = voxels flipped.  When it is > 0 the context is left exactly as
+ * rto_edit_voxels leaves it after a change (rebuild on the build path in force, resident leaf triangles rebuilt, frustum culling
+ * off); changed == 0 touches nothing.
+ *   RTO_SELECT_SMALLER_THAN      voxels < arg
+ *   RTO_SELECT_ALL_BUT_LARGEST   every component except the one with the most voxels; on a tie the smaller root is kept
+ *   RTO_SELECT_ENCLOSED          touches == 0
+ *   RTO_SELECT_CONTAINING        the component that holds linear voxel arg; none if that voxel is not in the set
+ *   RTO_SELECT_NOT_CONTAINING    all but that one; none if that voxel is not in the set
+ * Errors, each leaving the context untouched: RTO_E_INVALID (unknown set, connectivity or selection; arg < 0 for SMALLER_THAN and
+ * the CONTAINING forms; arg at or beyond the voxel count for the CONTAINING forms; too small a capacity; no resident labels);
+ * RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the octree came from rto_upload_octree: no resident grid; or the grid
+ * has more than 2^31 - 2 voxels: labels are 32-bit); RTO_E_INTERNAL (merging did not settle in 32 passes: a defect). */
+#define RTO_SET_SOLID 1
+#define RTO_SET_EMPTY 0
+#define RTO_CONN_FACE 6
+#define RTO_CONN_FULL 26
+#define RTO_SELECT_SMALLER_THAN    0
+#define RTO_SELECT_ALL_BUT_LARGEST 1
+#define RTO_SELECT_ENCLOSED        2
+#define RTO_SELECT_CONTAINING      3
+#define RTO_SELECT_NOT_CONTAINING  4
+typedef struct rto_component {      /* 48 bytes */
+    int64_t root;                   /* smallest linear voxel index of the component */
+    int64_t voxels;                 /* its size */
+    int32_t lo[3], hi[3];           /* inclusive voxel bounding box */
+    int32_t touches;                /* bit a: has a voxel with index 0 on axis a; bit 3 + a: one with index dim[a] - 1 */
+    int32_t reserved;               /* 0 */
+} rto_component;
+
+int  rto_label_components(rto_context* ctx, int set, int connectivity, int64_t* count /* may be NULL */);
+/* out == NULL: the count alone. */
+int  rto_download_components(rto_context* ctx, rto_component* out, int64_t capacity, int64_t* count);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_labels(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident label volume and table (device pointers the context owns, valid until the labels are freed). */
+int  rto_labels_device(rto_context* ctx, int32_t** d_labels, rto_component** d_components, int64_t* count);
+/* Device time in ms of the last rto_label_components: tile-local labelling, merging (all passes, with the host's look at the
+ * flag between them), flatten + ranking + label volume, statistics (-1: not run). */
+int  rto_last_components_ms(const rto_context* ctx, float ms[4]);
+/* Merge launches of the last rto_label_components (2 = one merge and one clean check; the cap is 32). */
+int  rto_debug_components_passes(const rto_context* ctx, int* passes);
+int  rto_edit_components(rto_context* ctx, int set, int connectivity, int select, int64_t arg, int64_t* changed /* may be NULL */);
 
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */

@@ -19,6 +19,7 @@ static int lean_block(int path);
 #include <vector>
 
 using namespace rto;
+namespace rto { struct CcComp; }   // rto_components.inc
 
 struct rto_context {
     int device = -1;
@@ -167,6 +168,13 @@ struct rto_context {
     float meshMs[3] = { -1.f, -1.f, -1.f };
     int meshLevelStart[kMaxDepth + 2] = { 0 };
     int meshLevels = 0;                       // 0: not known for the resident array (made on first use, dropped with the arrays)
+
+    // connected components (rto_components.inc): the last labelling of the resident grid; dropped whenever the grid changes
+    int* d_ccLabels = nullptr;                // nullptr: no labels resident
+    rto::CcComp* d_ccComps = nullptr;
+    int64_t ccCount = 0;
+    int ccPasses = 0;
+    float ccMs[4] = { -1.f, -1.f, -1.f, -1.f };
 };
 
 static thread_local std::string g_createError;
@@ -216,8 +224,16 @@ static void free_cull_buffers(rto_context* c) {
     (void)hipFree(c->d_compact); c->d_compact = nullptr;
 }
 
+// The resident component labels (rto_components.inc): they describe one state of the grid.
+static void free_components(rto_context* c) {
+    (void)hipFree(c->d_ccLabels); c->d_ccLabels = nullptr;
+    (void)hipFree(c->d_ccComps); c->d_ccComps = nullptr;
+    c->ccCount = 0;
+}
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rto_edit_voxels rebuilds from it).
 static void free_octree_arrays(rto_context* c) {
+    free_components(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -2724,3 +2740,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
 #include "rto_region.inc"
+#include "rto_components.inc"

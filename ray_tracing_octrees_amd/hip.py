@@ -14,6 +14,7 @@ from . import _build
 
 RTO_OK = 0
 RTO_E_INVALID, RTO_E_NO_OCTREE, RTO_E_HIP, RTO_E_NO_DEVICE, RTO_E_UNSUPPORTED, RTO_E_TIMEOUT = -1, -2, -3, -4, -5, -6
+RTO_E_INTERNAL = -7
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_PACKED, KERNEL_PACKED_V1, KERNEL_PACKED_PERSISTENT, KERNEL_PACKED_V3 = 0, 1, 2, 3, 4, 5
 
 # struct GPUNodes (453-skeleton/RayTracerBVH.h:21-26)
@@ -45,6 +46,8 @@ SYMBOLS = (
     "rto_frustum_planes", "rto_extract_mesh", "rto_mesh_device", "rto_download_mesh", "rto_last_mesh_ms",
     "rto_query_points_device", "rto_query_points_host", "rto_query_regions_device", "rto_query_regions_host",
     "rto_query_nearest_device", "rto_query_nearest_host", "rto_point_quantize",
+    "rto_label_components", "rto_download_components", "rto_download_labels", "rto_labels_device", "rto_last_components_ms",
+    "rto_debug_components_passes", "rto_edit_components",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -73,6 +76,12 @@ REGION_DTYPE = np.dtype([("filled", "<i8"), ("covered", "<i8"), ("solid_leaves",
                          ("reserved", "<i4", (2,))])
 NEAR_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("max_dist", "<f4")])
 NEAREST_DTYPE = np.dtype([("dist2", "<i8"), ("node", "<i4"), ("size", "<i4"), ("cq", "<i4", (3,)), ("reserved", "<i4")])
+# struct rto_component, 48 bytes: connected components (rto_label_components, rto_edit_components)
+SET_EMPTY, SET_SOLID = 0, 1
+CONN_FACE, CONN_FULL = 6, 26
+SELECT_SMALLER_THAN, SELECT_ALL_BUT_LARGEST, SELECT_ENCLOSED, SELECT_CONTAINING, SELECT_NOT_CONTAINING = 0, 1, 2, 3, 4
+COMPONENT_DTYPE = np.dtype([("root", "<i8"), ("voxels", "<i8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("touches", "<i4"),
+                            ("reserved", "<i4")])
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -405,6 +414,13 @@ def load():
     L.rto_mesh_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.rto_download_mesh.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.rto_last_mesh_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_label_components.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    L.rto_download_components.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_download_labels.argtypes = [vp, vp, C.c_int64]
+    L.rto_labels_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_last_components_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_components_passes.argtypes = [vp, C.POINTER(C.c_int)]
+    L.rto_edit_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -911,6 +927,60 @@ class Context:
         ms = (C.c_float * 3)()
         self._check(self._L.rto_last_edit_ms(self._h, ms))
         return tuple(ms)
+
+    # -- connected components --------------------------------------------------
+    def label_components(self, set: int = SET_SOLID, connectivity: int = CONN_FACE) -> np.ndarray:
+        """rto_label_components: label the resident grid's SET_SOLID or SET_EMPTY voxels under CONN_FACE (6) or CONN_FULL (26); the
+        table as a COMPONENT_DTYPE array in ascending order of root.  Labels and table stay resident until the grid changes."""
+        n = C.c_int64()
+        self._check(self._L.rto_label_components(self._h, int(set), int(connectivity), C.byref(n)))
+        out = np.zeros(n.value, COMPONENT_DTYPE)
+        if n.value:
+            self._check(self._L.rto_download_components(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def components(self) -> np.ndarray:
+        """The resident table (rto_download_components)."""
+        n = C.c_int64()
+        self._check(self._L.rto_download_components(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, COMPONENT_DTYPE)
+        if n.value:
+            self._check(self._L.rto_download_components(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def component_labels(self) -> np.ndarray:
+        """The resident label volume as int32 (dimZ, dimY, dimX): the component's number, -1 outside the set."""
+        self._check(self._L.rto_labels_device(self._h, None, None, None))     # no labels resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_labels(self._h, out.ctypes.data, out.size))
+        return out
+
+    def component_labels_device(self):
+        """(device pointer of the int32 label volume, device pointer of the 48-byte table records, count)."""
+        l, t, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._L.rto_labels_device(self._h, C.byref(l), C.byref(t), C.byref(n)))
+        return l.value or 0, t.value or 0, n.value
+
+    def last_components_ms(self):
+        """Device ms of the last labelling: (tile-local labelling, merging, flatten + ranking, statistics); -1: not run."""
+        ms = (C.c_float * 4)()
+        self._check(self._L.rto_last_components_ms(self._h, ms))
+        return tuple(ms)
+
+    def components_passes(self) -> int:
+        """Merge launches of the last labelling (2: one merge, one clean check)."""
+        n = C.c_int()
+        self._check(self._L.rto_debug_components_passes(self._h, C.byref(n)))
+        return n.value
+
+    def edit_components(self, set: int, connectivity: int, select: int, arg: int = 0) -> int:
+        """rto_edit_components: label afresh, flip every voxel of the selected components (SELECT_*), rebuild as edit_voxels
+        does; the number of voxels flipped."""
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_components(self._h, int(set), int(connectivity), int(select), int(arg), C.byref(changed)))
+        return changed.value
 
     # -- region queries --------------------------------------------------------
     def query_points(self, points) -> np.ndarray:

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   RtoError, _f)
 
 _lib = None
@@ -140,6 +140,22 @@ def load():
     L.rtoh_rt_census.restype = C.c_int
     L.rtoh_rt_nearest_solid.argtypes = [_vp, _vp, C.c_int64, C.c_float, _vp, _vp]
     L.rtoh_rt_nearest_solid.restype = C.c_int
+    L.rtoh_components_cpu.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64]
+    L.rtoh_components_cpu.restype = C.c_int64
+    L.rtoh_components_select_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int64]
+    L.rtoh_components_select_cpu.restype = C.c_int64
+    L.rtoh_rt_label_components.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int64]
+    L.rtoh_rt_label_components.restype = C.c_int64
+    L.rtoh_rt_component_labels.argtypes = [_vp, _vp, C.c_int64]
+    L.rtoh_rt_component_labels.restype = C.c_int
+    L.rtoh_rt_remove_debris.argtypes = [_vp, C.c_int64, C.c_int]
+    L.rtoh_rt_remove_debris.restype = C.c_int64
+    L.rtoh_rt_fill_cavities.argtypes = [_vp]
+    L.rtoh_rt_fill_cavities.restype = C.c_int64
+    L.rtoh_rt_keep_largest.argtypes = [_vp, C.c_int]
+    L.rtoh_rt_keep_largest.restype = C.c_int64
+    L.rtoh_rt_flip_component_at.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.rtoh_rt_flip_component_at.restype = C.c_int64
     L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
     L.rtoh_rt_edit_voxels.restype = C.c_int64
     L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
@@ -213,6 +229,24 @@ class VoxelGrid:
 
     def recenter(self) -> bool:
         return bool(load().rtoh_grid_recenter(self._h))
+
+    def labelComponents(self, set: int = 1, connectivity: int = 6):
+        """Addition: labelComponentsCPU (host/Components.h) -- the rule of rto_label_components as a breadth-first search on the
+        CPU: (labels int32 (dimZ, dimY, dimX), table as hip.COMPONENT_DTYPE)."""
+        dx, dy, dz = self.dims
+        labels = np.empty((dz, dy, dx), np.int32)
+        n = load().rtoh_components_cpu(self._h, int(set), int(connectivity), labels.ctypes.data, None, 0)
+        if n < 0:
+            raise ValueError("labelComponents: unknown set or connectivity, or too large a grid")
+        table = np.zeros(n, COMPONENT_DTYPE)
+        if n:
+            load().rtoh_components_cpu(self._h, int(set), int(connectivity), None, table.ctypes.data, n)
+        return labels, table
+
+    def applyComponentSelection(self, set: int, connectivity: int, select: int, arg: int = 0) -> int:
+        """Addition: applyComponentSelectionCPU -- rto_edit_components' selection and flip on this grid, on the CPU; the number
+        of voxels flipped (-1: refused, the grid untouched)."""
+        return int(load().rtoh_components_select_cpu(self._h, int(set), int(connectivity), int(select), int(arg)))
 
 
 def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
@@ -535,6 +569,41 @@ class RayTracerBVH:
         shapes = np.ascontiguousarray(b["shape"], dtype=np.int32)
         ops = np.ascontiguousarray(b["op"], dtype=np.int32)
         return int(load().rtoh_rt_edit_voxels(self._h, f.ctypes.data, shapes.ctypes.data, ops.ctypes.data, len(b)))
+
+    def labelComponents(self, set: int = 1, connectivity: int = 6):
+        """Addition: RayTracerBVH::labelComponents -- the resident grid's components (hip.SET_*, hip.CONN_*) as a
+        hip.COMPONENT_DTYPE table in ascending order of root; None on an error (lastError)."""
+        n = load().rtoh_rt_label_components(self._h, int(set), int(connectivity), None, 0)
+        if n < 0:
+            return None
+        table = np.zeros(n, COMPONENT_DTYPE)
+        if n and load().rtoh_rt_label_components(self._h, int(set), int(connectivity), table.ctypes.data, n) != n:
+            return None
+        return table
+
+    def componentLabels(self):
+        """Addition: RayTracerBVH::componentLabels -- the last labelling's volume, int32 (dimZ, dimY, dimX); None when no labels
+        are resident (not labelled, or the grid has changed since)."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        return out if load().rtoh_rt_component_labels(self._h, out.ctypes.data, out.size) else None
+
+    def removeDebris(self, minVoxels: int, connectivity: int = 6) -> int:
+        """Addition: RayTracerBVH::removeDebris -- clears the solid components of fewer than minVoxels voxels; voxels flipped."""
+        return int(load().rtoh_rt_remove_debris(self._h, int(minVoxels), int(connectivity)))
+
+    def fillCavities(self) -> int:
+        """Addition: RayTracerBVH::fillCavities -- fills the empty space no 6-connected path joins to a face of the grid."""
+        return int(load().rtoh_rt_fill_cavities(self._h))
+
+    def keepLargest(self, connectivity: int = 6) -> int:
+        """Addition: RayTracerBVH::keepLargest -- clears every solid component but the largest."""
+        return int(load().rtoh_rt_keep_largest(self._h, int(connectivity)))
+
+    def flipComponentAt(self, i: int, j: int, k: int, set: int, connectivity: int = 6) -> int:
+        """Addition: RayTracerBVH::flipComponentAt -- flips the component of `set` that holds voxel (i, j, k)."""
+        return int(load().rtoh_rt_flip_component_at(self._h, int(i), int(j), int(k), int(set), int(connectivity)))
 
     def locate(self, points):
         """Addition: RayTracerBVH::locate -- the leaf that holds each of the (n, 3) points: (code, hip.POINT_HIT_DTYPE records).

@@ -55,6 +55,10 @@ struct HipApi {
     decltype(&rto_query_regions_host) query_regions_host = nullptr;
     decltype(&rto_query_nearest_host) query_nearest_host = nullptr;
     decltype(&rto_scene_bounds_get) scene_bounds_get = nullptr;
+    decltype(&rto_label_components) label_components = nullptr;
+    decltype(&rto_download_components) download_components = nullptr;
+    decltype(&rto_download_labels) download_labels = nullptr;
+    decltype(&rto_edit_components) edit_components = nullptr;
     std::string error;
 
     bool load() {
@@ -120,6 +124,10 @@ struct HipApi {
         query_regions_host = reinterpret_cast<decltype(query_regions_host)>(sym("rto_query_regions_host"));
         query_nearest_host = reinterpret_cast<decltype(query_nearest_host)>(sym("rto_query_nearest_host"));
         scene_bounds_get = reinterpret_cast<decltype(scene_bounds_get)>(sym("rto_scene_bounds_get"));
+        label_components = reinterpret_cast<decltype(label_components)>(sym("rto_label_components"));
+        download_components = reinterpret_cast<decltype(download_components)>(sym("rto_download_components"));
+        download_labels = reinterpret_cast<decltype(download_labels)>(sym("rto_download_labels"));
+        edit_components = reinterpret_cast<decltype(edit_components)>(sym("rto_edit_components"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -754,6 +762,95 @@ void RayTracerBVH::editVoxels(const std::vector<VoxelBrush>& brushes) {
         if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
     }
     if (changed > 0) m_gridStale = true;
+}
+
+// After setOctree() the GPUs hold the caller's node array and no grid: build the octree from m_grid there (the same array, DESIGN.md
+// section 1, N4), keeping leaf triangles resident where they were, as the first editVoxels does.
+bool RayTracerBVH::makeGridResident(const char* what) {
+    if (m_flatNodes.empty()) return true;
+    const float gridMin[3] = { m_grid.minX, m_grid.minY, m_grid.minZ };
+    if (!forEachContext([&](rto_context* c) {
+            int64_t numTris = 0;
+            const bool hadTris = api().download_leaf_triangles(c, nullptr, 0, nullptr, &numTris) == RTO_OK;
+            int rc = api().build_octree(c, reinterpret_cast<const uint8_t*>(m_grid.data.data()), m_grid.dimX, m_grid.dimY, m_grid.dimZ,
+                                        gridMin, m_grid.voxelSize);
+            if (rc == RTO_OK && hadTris) rc = api().build_leaf_triangles(c, nullptr, 0, 0, 0);
+            return rc;
+        }, what))
+        return false;
+    m_flatNodes.clear(); m_octreeRoot = nullptr;      // the caller's pointer tree no longer describes what the GPUs hold
+    rto_octree_info info;
+    if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+    return true;
+}
+
+std::vector<rto_component> RayTracerBVH::labelComponents(int set, int connectivity) {
+    std::vector<rto_component> table;
+    m_lastComponents = -1;
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return table;
+    }
+    if (m_numNodes <= 0 || !makeGridResident("component labelling")) return table;
+    int64_t count = 0;
+    int rc = api().label_components(m_ctx, set, connectivity, &count);
+    if (rc == RTO_OK && count > 0) {
+        table.resize((size_t)count);
+        rc = api().download_components(m_ctx, table.data(), count, &count);
+    }
+    if (rc != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] component labelling failed: " << m_lastError << std::endl;
+        table.clear();
+        return table;
+    }
+    m_lastComponents = count;
+    return table;
+}
+
+std::vector<int32_t> RayTracerBVH::componentLabels() {
+    std::vector<int32_t> labels;
+    if (!m_ctx || m_numNodes <= 0) return labels;
+    labels.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+    if (api().download_labels(m_ctx, labels.data(), (int64_t)labels.size()) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        labels.clear();
+    }
+    return labels;
+}
+
+int64_t RayTracerBVH::editComponents(int set, int connectivity, int select, int64_t arg) {
+    if (!m_computeInited || !m_computeOk) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return -1;
+    }
+    m_lastEditChanged = -1;
+    if (m_numNodes <= 0 || !makeGridResident("component edit")) return -1;
+    int64_t changed = 0;
+    if (!forEachContext([&](rto_context* c) { return api().edit_components(c, set, connectivity, select, arg, c == m_ctx ? &changed : nullptr); },
+                        "component edit"))
+        return -1;
+    m_lastEditChanged = changed;
+    if (changed > 0) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+        m_gridStale = true;
+    }
+    return changed;
+}
+
+int64_t RayTracerBVH::removeDebris(int64_t minVoxels, int connectivity) {
+    return editComponents(RTO_SET_SOLID, connectivity, RTO_SELECT_SMALLER_THAN, minVoxels);
+}
+int64_t RayTracerBVH::fillCavities() { return editComponents(RTO_SET_EMPTY, RTO_CONN_FACE, RTO_SELECT_ENCLOSED, 0); }
+int64_t RayTracerBVH::keepLargest(int connectivity) { return editComponents(RTO_SET_SOLID, connectivity, RTO_SELECT_ALL_BUT_LARGEST, 0); }
+int64_t RayTracerBVH::flipComponentAt(int i, int j, int k, int set, int connectivity) {
+    if (i < 0 || i >= m_grid.dimX || j < 0 || j >= m_grid.dimY || k < 0 || k >= m_grid.dimZ) {
+        m_lastError = "flipComponentAt: the voxel lies outside the grid";
+        m_lastEditChanged = -1;
+        return -1;
+    }
+    return editComponents(set, connectivity, RTO_SELECT_CONTAINING, (int64_t)i + (int64_t)m_grid.dimX * ((int64_t)j + (int64_t)m_grid.dimY * k));
 }
 
 bool RayTracerBVH::loadMesh(const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize, int recenterPasses,

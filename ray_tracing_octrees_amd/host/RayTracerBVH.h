@@ -194,6 +194,22 @@ public:
     // click-to-carve: pickSurface (or pick), then editVoxels({{hit.point, vec3(r), VoxelBrush::Sphere, VoxelBrush::Carve}}).
     void editVoxels(const std::vector<VoxelBrush>& brushes);
     int64_t lastEditChanged() const { return m_lastEditChanged; }   // voxels the last editVoxels changed; -1: it failed
+    // Connected components of the resident grid (rto_label_components / rto_edit_components): set is
+    // RTO_SET_SOLID or RTO_SET_EMPTY, connectivity RTO_CONN_FACE (6) or RTO_CONN_FULL (26).  labelComponents labels the grid of the
+    // first GPU and returns the table in ascending order of root (empty with lastError set on an error); componentLabels() is that
+    // labelling's volume (one int32 per voxel, x fastest, -1 outside the set; empty once the grid has changed).  The edits act on
+    // every GPU and rebuild as editVoxels does; each returns the number of voxels flipped, -1 on an error (lastEditChanged() too):
+    // removeDebris clears the solid components of fewer than minVoxels voxels, fillCavities fills the empty components that touch
+    // no face of the grid (6-connected: what a voxelized closed mesh encloses), keepLargest clears every solid component but the
+    // largest, flipComponentAt flips the component of `set` that holds voxel (i, j, k) (0 when that voxel is not in the set).
+    // After setOctree() the first of these builds the octree from the grid given to it, as the first editVoxels does.
+    std::vector<rto_component> labelComponents(int set = RTO_SET_SOLID, int connectivity = RTO_CONN_FACE);
+    int64_t lastComponentCount() const { return m_lastComponents; }   // components the last labelComponents found; -1: it failed
+    std::vector<int32_t> componentLabels();
+    int64_t removeDebris(int64_t minVoxels, int connectivity = RTO_CONN_FACE);
+    int64_t fillCavities();
+    int64_t keepLargest(int connectivity = RTO_CONN_FACE);
+    int64_t flipComponentAt(int i, int j, int k, int set, int connectivity = RTO_CONN_FACE);
     // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
     // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
     // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same
@@ -250,6 +266,7 @@ private:
     mutable VoxelGrid m_grid;
     mutable bool m_gridStale = false;         // the GPUs hold an edited grid that m_grid does not show yet (grid())
     int64_t m_lastEditChanged = 0;
+    int64_t m_lastComponents = 0;
     std::vector<GPUNodes> m_flatNodes;
     int m_numNodes;
 
@@ -264,6 +281,8 @@ private:
     template <class F> bool forEachContext(F&& call, const char* what);
     bool renderFrame(const rto_frame& f, int mode);
     int regionFailed(int rc, const char* what);
+    bool makeGridResident(const char* what);
+    int64_t editComponents(int set, int connectivity, int select, int64_t arg);
     mutable std::string m_lastError;
 
     mutable std::vector<float> m_frame;

@@ -1,6 +1,7 @@
 // host_capi.cpp -- extern "C" doors onto the C++ host layer so Python (tests, bench.py) can drive the
 // same classes a C++ application would: VoxelGrid / createOctreeFromVoxelGrid / Camera / Frustum /
 // CacheUtils / RayTracerBVH.  Pure plumbing; no algorithm lives here.
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstring>
@@ -9,6 +10,7 @@
 
 #include "BuildingLoader.h"
 #include "CacheUtils.h"
+#include "Components.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -304,6 +306,39 @@ int64_t rtoh_rt_edit_voxels(RayTracerBVH* rt, const float* brushes, const int* s
     }
     rt->editVoxels(b);
     return rt->lastEditChanged();
+}
+// Connected components.  rtoh_components_cpu: the CPU form of the rule (Components.h) on a grid: labels (dims product int32) and
+// table (capacity records) may be NULL; the count, -1 for a refusal.  rtoh_components_select_cpu edits the grid in place.
+int64_t rtoh_components_cpu(const VoxelGrid* g, int set, int connectivity, int32_t* labels, rto_component* table, int64_t capacity) {
+    std::vector<int32_t> l;
+    std::vector<rto_component> t;
+    const int64_t n = labelComponentsCPU(*g, set, connectivity, l, t);
+    if (n < 0) return n;
+    if (labels) std::copy(l.begin(), l.end(), labels);
+    if (table) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>(n, capacity), table);
+    return n;
+}
+int64_t rtoh_components_select_cpu(VoxelGrid* g, int set, int connectivity, int select, int64_t arg) {
+    return applyComponentSelectionCPU(*g, set, connectivity, select, arg);
+}
+// RayTracerBVH::labelComponents: the count (-1: it failed), table filled up to capacity; rtoh_rt_component_labels: 1 when copied
+int64_t rtoh_rt_label_components(RayTracerBVH* rt, int set, int connectivity, rto_component* table, int64_t capacity) {
+    const std::vector<rto_component> t = rt->labelComponents(set, connectivity);
+    if (rt->lastComponentCount() < 0) return -1;
+    if (table) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), table);
+    return (int64_t)t.size();
+}
+int rtoh_rt_component_labels(RayTracerBVH* rt, int32_t* out, int64_t capacity) {
+    const std::vector<int32_t> l = rt->componentLabels();
+    if (l.empty() || (int64_t)l.size() > capacity) return 0;
+    std::copy(l.begin(), l.end(), out);
+    return 1;
+}
+int64_t rtoh_rt_remove_debris(RayTracerBVH* rt, int64_t minVoxels, int connectivity) { return rt->removeDebris(minVoxels, connectivity); }
+int64_t rtoh_rt_fill_cavities(RayTracerBVH* rt) { return rt->fillCavities(); }
+int64_t rtoh_rt_keep_largest(RayTracerBVH* rt, int connectivity) { return rt->keepLargest(connectivity); }
+int64_t rtoh_rt_flip_component_at(RayTracerBVH* rt, int i, int j, int k, int set, int connectivity) {
+    return rt->flipComponentAt(i, j, k, set, connectivity);
 }
 // RayTracerBVH::locate / census / nearestSolid: the C ABI's records back out; each returns the class's code (RTO_OK or the refusal's)
 int rtoh_rt_locate(RayTracerBVH* rt, const float* points, int64_t n, rto_point_hit* hits) {
