@@ -876,6 +876,66 @@ int  rto_last_components_ms(const rto_context* ctx, float ms[4]);
 int  rto_debug_components_passes(const rto_context* ctx, int* passes);
 int  rto_edit_components(rto_context* ctx, int set, int connectivity, int select, int64_t arg, int64_t* changed /* may be NULL */);
 
+/* ---- distance fields and morphology -----------------------------------------
+ * How far every voxel of the resident grid is from a set of its voxels, exactly, and the edits that move the surface by a distance:
+ * thicken a voxelized shell until rto_edit_components can see it as closed, close pinholes, open away attached whiskers, find the
+ * thickest point of a part.  No reference counterpart.  Every result is an integer that a brute-force minimum over
+ * rto_download_voxels reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel (i, j, k) has linear index v = i + dimX (j + dimY k); the sets are rto_label_components': RTO_SET_SOLID the
+ *             voxels equal to 1, RTO_SET_EMPTY the voxels equal to 0.  Voxels outside the grid belong to no set.
+ *   field     d2[v] = min over the voxels u of the set of (i_v - i_u)^2 + (j_v - j_u)^2 + (k_v - k_u)^2, as int32, in voxel-index
+ *             units (multiply by voxelSize^2 for world units): 0 exactly on the set; RTO_DIST_NONE where the set is empty.  No
+ *             nearest-voxel index is returned: ties would need a rule the separable passes do not give for free.
+ *   cap       mq = floor(max_dist / voxelSize * 64 + 0.5) in double from the context's floats, as rto_query_nearest_* quantises
+ *             max_dist; +inf: no cap.  A voxel is in reach when 4096 d2 <= mq^2 (int64); voxels out of reach hold RTO_DIST_NONE,
+ *             so a capped field is the uncapped one, thresholded.
+ *   summary   max_d2 the largest finite value, argmax the smallest linear index that holds it, finite the number of finite
+ *             values; max_d2 = argmax = -1 when finite is 0.
+ * rto_distance_field keeps the volume (int32 per voxel) resident; it describes the grid it was made from, and every call that
+ * changes or replaces the grid frees it (rto_build_octree, rto_upload_octree, rto_voxelize_mesh, rto_edit_voxels /
+ * rto_edit_components / rto_edit_morphology with changed > 0, rto_destroy): the readers then return RTO_E_INVALID.  Synchronous on
+ * the context's stream.
+ * rto_edit_morphology quantises radius to rq as max_dist is quantised to mq and makes its own capped fields (the resident one is
+ * not consulted):
+ *   RTO_MORPH_DILATE   an EMPTY voxel becomes FILLED when its d2 to SOLID is in reach of rq
+ *   RTO_MORPH_ERODE    a FILLED voxel becomes EMPTY when its d2 to EMPTY is in reach
+ *   RTO_MORPH_OPEN     ERODE, then DILATE of the result;   RTO_MORPH_CLOSE   DILATE, then ERODE of the result
+ * The outside of the grid is no set: erosion never eats in from the grid's faces and dilation never grows past them, so on the
+ * subsets of the grid dilate(X) is inside Y exactly when X is inside erode(Y); CLOSE only adds, OPEN only removes, both are
+ * idempotent.  The DILATE by r of a single FILLED voxel is the voxel set of rto_edit_voxels' FILL with a SPHERE brush of radius r
+ * on that voxel's centre.  *changed (may be NULL) = voxels whose final value differs from their value before the call (for OPEN
+ * and CLOSE: from the grid before the first step).  When it is > 0 the context is left exactly as rto_edit_voxels leaves it after a
+ * change (one rebuild on the build path in force, resident leaf triangles rebuilt, frustum culling off, labels and field freed);
+ * changed == 0 (rq == 0 included) touches nothing.
+ * Errors, each leaving the context untouched: RTO_E_INVALID (unknown set or op; max_dist or radius NaN, negative, or beyond 2^28
+ * quanta; too small a capacity; no resident field); RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the octree came from
+ * rto_upload_octree: no resident grid; more than 2^31 - 2 voxels; (dimX-1)^2 + (dimY-1)^2 + (dimZ-1)^2 >= 2^31 - 1: the field is
+ * 32-bit -- 46342 x 1 x 1 is refused, 46341 x 1 x 1 accepted). */
+#define RTO_DIST_NONE 0x7fffffff
+#define RTO_MORPH_DILATE 0
+#define RTO_MORPH_ERODE  1
+#define RTO_MORPH_OPEN   2
+#define RTO_MORPH_CLOSE  3
+typedef struct rto_dist_summary {   /* 32 bytes */
+    int64_t max_d2;                 /* the largest finite value; -1: none */
+    int64_t argmax;                 /* the smallest linear voxel index that holds it; -1: none */
+    int64_t finite;                 /* voxels with a finite value */
+    int64_t reserved;               /* 0 */
+} rto_dist_summary;
+
+int  rto_distance_field(rto_context* ctx, int set, float max_dist, rto_dist_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_distance(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed). */
+int  rto_distance_device(rto_context* ctx, int32_t** d_d2);
+/* Device time in ms of the last rto_distance_field: x pass, y pass, z pass, summary (-1: not run). */
+int  rto_last_distance_ms(const rto_context* ctx, float ms[4]);
+int  rto_edit_morphology(rto_context* ctx, int op, float radius, int64_t* changed /* may be NULL */);
+/* Device time in ms of the last rto_edit_morphology: transforms and flips, octree rebuild, triangle rebuild (-1: not run). */
+int  rto_last_morphology_ms(const rto_context* ctx, float ms[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -175,6 +175,11 @@ struct rto_context {
     int64_t ccCount = 0;
     int ccPasses = 0;
     float ccMs[4] = { -1.f, -1.f, -1.f, -1.f };
+
+    // distance fields (rto_distance.inc): the last field of the resident grid; dropped whenever the grid changes
+    int* d_dist = nullptr;                    // nullptr: no field resident
+    float distMs[4] = { -1.f, -1.f, -1.f, -1.f };
+    float morphMs[3] = { -1.f, -1.f, -1.f };  // the last rto_edit_morphology: transforms and flips, octree rebuild, triangle rebuild
 };
 
 static thread_local std::string g_createError;
@@ -231,9 +236,13 @@ static void free_components(rto_context* c) {
     c->ccCount = 0;
 }
 
+// The resident distance field (rto_distance.inc): it describes one state of the grid.
+static void free_distance(rto_context* c) { (void)hipFree(c->d_dist); c->d_dist = nullptr; }
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rto_edit_voxels rebuilds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
+    free_distance(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -2741,3 +2750,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_mesh.inc"
 #include "rto_region.inc"
 #include "rto_components.inc"
+#include "rto_distance.inc"

@@ -48,6 +48,8 @@ SYMBOLS = (
     "rto_query_nearest_device", "rto_query_nearest_host", "rto_point_quantize",
     "rto_label_components", "rto_download_components", "rto_download_labels", "rto_labels_device", "rto_last_components_ms",
     "rto_debug_components_passes", "rto_edit_components",
+    "rto_distance_field", "rto_download_distance", "rto_distance_device", "rto_last_distance_ms", "rto_edit_morphology",
+    "rto_last_morphology_ms",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -82,6 +84,10 @@ CONN_FACE, CONN_FULL = 6, 26
 SELECT_SMALLER_THAN, SELECT_ALL_BUT_LARGEST, SELECT_ENCLOSED, SELECT_CONTAINING, SELECT_NOT_CONTAINING = 0, 1, 2, 3, 4
 COMPONENT_DTYPE = np.dtype([("root", "<i8"), ("voxels", "<i8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("touches", "<i4"),
                             ("reserved", "<i4")])
+# struct rto_dist_summary, 32 bytes: distance fields and morphology (rto_distance_field, rto_edit_morphology)
+DIST_NONE = 0x7fffffff
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+DIST_SUMMARY_DTYPE = np.dtype([("max_d2", "<i8"), ("argmax", "<i8"), ("finite", "<i8"), ("reserved", "<i8")])
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -421,6 +427,12 @@ def load():
     L.rto_last_components_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_components_passes.argtypes = [vp, C.POINTER(C.c_int)]
     L.rto_edit_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_distance_field.argtypes = [vp, C.c_int, C.c_float, vp]
+    L.rto_download_distance.argtypes = [vp, vp, C.c_int64]
+    L.rto_distance_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_last_distance_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_edit_morphology.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
+    L.rto_last_morphology_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -981,6 +993,49 @@ class Context:
         changed = C.c_int64()
         self._check(self._L.rto_edit_components(self._h, int(set), int(connectivity), int(select), int(arg), C.byref(changed)))
         return changed.value
+
+    # -- distance fields and morphology ------------------------------------------
+    def distance_field(self, set: int = SET_SOLID, max_dist: float = float("inf")):
+        """rto_distance_field: (the int32 (dimZ, dimY, dimX) volume of squared distances, in voxel-index units, to the nearest voxel
+        of SET_SOLID or SET_EMPTY, DIST_NONE beyond max_dist (world units); the summary as a DIST_SUMMARY_DTYPE scalar).  The field
+        stays resident until the grid changes."""
+        summary = np.zeros((), DIST_SUMMARY_DTYPE)
+        self._check(self._L.rto_distance_field(self._h, int(set), float(max_dist), summary.ctypes.data))
+        return self.distance(), summary
+
+    def distance(self) -> np.ndarray:
+        """The resident field (rto_download_distance)."""
+        self._check(self._L.rto_distance_device(self._h, None))             # no field resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_distance(self._h, out.ctypes.data, out.size))
+        return out
+
+    def distance_device(self) -> int:
+        """The device pointer of the resident int32 field."""
+        p = C.c_void_p()
+        self._check(self._L.rto_distance_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def last_distance_ms(self):
+        """Device ms of the last distance_field: (x pass, y pass, z pass, summary); -1: not run."""
+        ms = (C.c_float * 4)()
+        self._check(self._L.rto_last_distance_ms(self._h, ms))
+        return tuple(ms)
+
+    def edit_morphology(self, op: int, radius: float) -> int:
+        """rto_edit_morphology: MORPH_DILATE / MORPH_ERODE / MORPH_OPEN / MORPH_CLOSE by `radius` (world units), rebuilt as
+        edit_voxels does; the number of voxels whose value differs from the one before the call."""
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_morphology(self._h, int(op), float(radius), C.byref(changed)))
+        return changed.value
+
+    def last_morphology_ms(self):
+        """Device ms of the last edit_morphology: (transforms and flips, octree rebuild, triangle rebuild); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_morphology_ms(self._h, ms))
+        return tuple(ms)
 
     # -- region queries --------------------------------------------------------
     def query_points(self, points) -> np.ndarray:

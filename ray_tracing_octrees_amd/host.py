@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   RtoError, _f)
 
 _lib = None
@@ -156,6 +156,18 @@ def load():
     L.rtoh_rt_keep_largest.restype = C.c_int64
     L.rtoh_rt_flip_component_at.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.rtoh_rt_flip_component_at.restype = C.c_int64
+    L.rtoh_distance_quantize.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_int64)]
+    L.rtoh_distance_quantize.restype = C.c_int
+    L.rtoh_distance_cpu.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp]
+    L.rtoh_distance_cpu.restype = C.c_int
+    L.rtoh_morphology_cpu.argtypes = [_vp, C.c_int, C.c_int64]
+    L.rtoh_morphology_cpu.restype = C.c_int64
+    L.rtoh_rt_distance_field.argtypes = [_vp, C.c_int, C.c_float, _vp, C.c_int64, _vp]
+    L.rtoh_rt_distance_field.restype = C.c_int
+    L.rtoh_rt_morphology.argtypes = [_vp, C.c_int, C.c_float]
+    L.rtoh_rt_morphology.restype = C.c_int64
+    L.rtoh_rt_thickest_point.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.rtoh_rt_thickest_point.restype = C.c_int
     L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
     L.rtoh_rt_edit_voxels.restype = C.c_int64
     L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
@@ -247,6 +259,21 @@ class VoxelGrid:
         """Addition: applyComponentSelectionCPU -- rto_edit_components' selection and flip on this grid, on the CPU; the number
         of voxels flipped (-1: refused, the grid untouched)."""
         return int(load().rtoh_components_select_cpu(self._h, int(set), int(connectivity), int(select), int(arg)))
+
+    def distanceField(self, set: int = 1, mq: int = -1):
+        """Addition: distanceFieldCPU (host/Distance.h) -- the rule of rto_distance_field on the CPU for mq quanta (-1: no cap):
+        (d2 int32 (dimZ, dimY, dimX), summary as a hip.DIST_SUMMARY_DTYPE scalar)."""
+        dx, dy, dz = self.dims
+        d2 = np.empty((dz, dy, dx), np.int32)
+        summary = np.zeros((), DIST_SUMMARY_DTYPE)
+        if not load().rtoh_distance_cpu(self._h, int(set), int(mq), d2.ctypes.data, summary.ctypes.data):
+            raise ValueError("distanceField: unknown set, or a grid the 32-bit field cannot serve")
+        return d2, summary
+
+    def applyMorphology(self, op: int, rq: int) -> int:
+        """Addition: applyMorphologyCPU -- rto_edit_morphology's DILATE / ERODE / OPEN / CLOSE on this grid for rq quanta, on the
+        CPU; the number of voxels changed (-1: refused, the grid untouched)."""
+        return int(load().rtoh_morphology_cpu(self._h, int(op), int(rq)))
 
 
 def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
@@ -604,6 +631,43 @@ class RayTracerBVH:
     def flipComponentAt(self, i: int, j: int, k: int, set: int, connectivity: int = 6) -> int:
         """Addition: RayTracerBVH::flipComponentAt -- flips the component of `set` that holds voxel (i, j, k)."""
         return int(load().rtoh_rt_flip_component_at(self._h, int(i), int(j), int(k), int(set), int(connectivity)))
+
+    def distanceField(self, set: int = 1, maxDist: float = float("inf")):
+        """Addition: RayTracerBVH::distanceField -- (code, d2 int32 (dimZ, dimY, dimX), summary as a hip.DIST_SUMMARY_DTYPE scalar);
+        code is RTO_OK or the refusal's (lastError), and d2 is then None."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        d2 = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        summary = np.zeros((), DIST_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_distance_field(self._h, int(set), float(maxDist), d2.ctypes.data, d2.size, summary.ctypes.data))
+        return rc, (d2 if rc == 0 else None), summary
+
+    def dilate(self, radius: float) -> int:
+        """Addition: RayTracerBVH::dilate -- EMPTY voxels within `radius` of a FILLED one become FILLED; voxels changed, or the
+        refusal's code (negative)."""
+        return int(load().rtoh_rt_morphology(self._h, 0, float(radius)))
+
+    def erode(self, radius: float) -> int:
+        """Addition: RayTracerBVH::erode -- FILLED voxels within `radius` of an EMPTY one become EMPTY."""
+        return int(load().rtoh_rt_morphology(self._h, 1, float(radius)))
+
+    def open(self, radius: float) -> int:
+        """Addition: RayTracerBVH::open -- erode, then dilate."""
+        return int(load().rtoh_rt_morphology(self._h, 2, float(radius)))
+
+    def close(self, radius: float) -> int:
+        """Addition: RayTracerBVH::close -- dilate, then erode."""
+        return int(load().rtoh_rt_morphology(self._h, 3, float(radius)))
+
+    def thickestPoint(self):
+        """Addition: RayTracerBVH::thickestPoint -- (code, None or ((i, j, k), d2, distance in world units)) of the FILLED voxel
+        farthest from any EMPTY one."""
+        out = (C.c_int64 * 5)()
+        dist = C.c_double()
+        rc = int(load().rtoh_rt_thickest_point(self._h, out, C.byref(dist)))
+        if rc != 0 or not out[0]:
+            return rc, None
+        return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), float(dist.value))
 
     def locate(self, points):
         """Addition: RayTracerBVH::locate -- the leaf that holds each of the (n, 3) points: (code, hip.POINT_HIT_DTYPE records).

@@ -59,6 +59,9 @@ struct HipApi {
     decltype(&rto_download_components) download_components = nullptr;
     decltype(&rto_download_labels) download_labels = nullptr;
     decltype(&rto_edit_components) edit_components = nullptr;
+    decltype(&rto_distance_field) distance_field = nullptr;
+    decltype(&rto_download_distance) download_distance = nullptr;
+    decltype(&rto_edit_morphology) edit_morphology = nullptr;
     std::string error;
 
     bool load() {
@@ -128,6 +131,9 @@ struct HipApi {
         download_components = reinterpret_cast<decltype(download_components)>(sym("rto_download_components"));
         download_labels = reinterpret_cast<decltype(download_labels)>(sym("rto_download_labels"));
         edit_components = reinterpret_cast<decltype(edit_components)>(sym("rto_edit_components"));
+        distance_field = reinterpret_cast<decltype(distance_field)>(sym("rto_distance_field"));
+        download_distance = reinterpret_cast<decltype(download_distance)>(sym("rto_download_distance"));
+        edit_morphology = reinterpret_cast<decltype(edit_morphology)>(sym("rto_edit_morphology"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -851,6 +857,68 @@ int64_t RayTracerBVH::flipComponentAt(int i, int j, int k, int set, int connecti
         return -1;
     }
     return editComponents(set, connectivity, RTO_SELECT_CONTAINING, (int64_t)i + (int64_t)m_grid.dimX * ((int64_t)j + (int64_t)m_grid.dimY * k));
+}
+
+// The distance field of the first GPU's resident grid (rto_distance_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::distanceField(int set, float maxDist, std::vector<int32_t>* d2, rto_dist_summary* summary) {
+    if (d2) d2->clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "distanceField: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("distance field")) return RTO_E_HIP;
+    int rc = api().distance_field(m_ctx, set, maxDist, summary);
+    if (rc == RTO_OK && d2) {
+        d2->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+        rc = api().download_distance(m_ctx, d2->data(), (int64_t)d2->size());
+        if (rc != RTO_OK) d2->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "distanceField");
+    return RTO_OK;
+}
+
+// rto_edit_morphology on every GPU: the number of voxels changed, or the refusal's code (negative).
+int64_t RayTracerBVH::editMorphology(int op, float radius) {
+    m_lastEditChanged = -1;
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "morphology: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("morphology")) return RTO_E_HIP;
+    int64_t changed = 0;
+    for (rto_context* c : m_ctxs) {
+        const int rc = api().edit_morphology(c, op, radius, c == m_ctx ? &changed : nullptr);
+        if (rc != RTO_OK) {
+            m_lastError = api().last_error(c);
+            std::cerr << "[RayTracerBVH] morphology failed: " << m_lastError << std::endl;
+            return rc;
+        }
+    }
+    m_lastEditChanged = changed;
+    if (changed > 0) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+        m_gridStale = true;
+    }
+    return changed;
+}
+
+int64_t RayTracerBVH::dilate(float radius) { return editMorphology(RTO_MORPH_DILATE, radius); }
+int64_t RayTracerBVH::erode(float radius) { return editMorphology(RTO_MORPH_ERODE, radius); }
+int64_t RayTracerBVH::open(float radius) { return editMorphology(RTO_MORPH_OPEN, radius); }
+int64_t RayTracerBVH::close(float radius) { return editMorphology(RTO_MORPH_CLOSE, radius); }
+
+int RayTracerBVH::thickestPoint(ThickestPoint& out) {
+    out = ThickestPoint();
+    rto_dist_summary s;
+    const int rc = distanceField(RTO_SET_EMPTY, INFINITY, nullptr, &s);
+    if (rc != RTO_OK) return rc;
+    if (s.finite == 0 || s.max_d2 <= 0) return RTO_OK;                 // nothing EMPTY to measure from, or nothing FILLED
+    out.found = true;
+    out.i = (int)(s.argmax % m_grid.dimX); out.j = (int)((s.argmax / m_grid.dimX) % m_grid.dimY); out.k = (int)(s.argmax / ((int64_t)m_grid.dimX * m_grid.dimY));
+    out.d2 = s.max_d2;
+    out.distance = std::sqrt((double)s.max_d2) * (double)m_grid.voxelSize;
+    return RTO_OK;
 }
 
 bool RayTracerBVH::loadMesh(const double* xyz, int64_t nVerts, const int32_t* tris, int64_t nTris, float voxelSize, int recenterPasses,

@@ -210,6 +210,21 @@ public:
     int64_t fillCavities();
     int64_t keepLargest(int connectivity = RTO_CONN_FACE);
     int64_t flipComponentAt(int i, int j, int k, int set, int connectivity = RTO_CONN_FACE);
+    // Distance fields and morphology of the resident grid (rto_distance_field / rto_edit_morphology).
+    // distanceField makes the field of the first GPU's grid: one int32 per voxel, x fastest, the squared distance in voxel-index
+    // units to the nearest voxel of `set`, RTO_DIST_NONE beyond maxDist (world units; INFINITY: no cap); d2 and summary may be null.
+    // It returns RTO_OK or the refusal's code (lastError).  dilate / erode / open / close move the surface by `radius` (world units)
+    // on every GPU and rebuild as editVoxels does; each returns the number of voxels changed (lastEditChanged() too), or the
+    // refusal's code, which is negative.  thickestPoint is the FILLED voxel farthest from any EMPTY one (the smallest index among
+    // equals) with its distance in world units; found stays false in a grid with no EMPTY or no FILLED voxel.
+    // After setOctree() the first of these builds the octree from the grid given to it, as the first editVoxels does.
+    struct ThickestPoint { bool found = false; int i = 0, j = 0, k = 0; int64_t d2 = 0; double distance = 0.0; };
+    int distanceField(int set, float maxDist, std::vector<int32_t>* d2, rto_dist_summary* summary = nullptr);
+    int64_t dilate(float radius);
+    int64_t erode(float radius);
+    int64_t open(float radius);
+    int64_t close(float radius);
+    int thickestPoint(ThickestPoint& out);
     // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
     // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
     // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same
@@ -283,6 +298,7 @@ private:
     int regionFailed(int rc, const char* what);
     bool makeGridResident(const char* what);
     int64_t editComponents(int set, int connectivity, int select, int64_t arg);
+    int64_t editMorphology(int op, float radius);
     mutable std::string m_lastError;
 
     mutable std::vector<float> m_frame;

@@ -11,6 +11,7 @@
 #include "BuildingLoader.h"
 #include "CacheUtils.h"
 #include "Components.h"
+#include "Distance.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -339,6 +340,41 @@ int64_t rtoh_rt_fill_cavities(RayTracerBVH* rt) { return rt->fillCavities(); }
 int64_t rtoh_rt_keep_largest(RayTracerBVH* rt, int connectivity) { return rt->keepLargest(connectivity); }
 int64_t rtoh_rt_flip_component_at(RayTracerBVH* rt, int i, int j, int k, int set, int connectivity) {
     return rt->flipComponentAt(i, j, k, set, connectivity);
+}
+// Distance fields.  rtoh_distance_cpu: the CPU form of the rule (Distance.h) on a grid for mq quanta (-1: no cap): d2 (dims product
+// int32) and summary may be NULL; 1, or 0 for a refusal.  rtoh_morphology_cpu edits the grid in place (-1: refused).
+int rtoh_distance_quantize(float dist, float voxelSize, int64_t* mq) { return quantizeDistanceCPU(dist, voxelSize, *mq) ? 1 : 0; }
+int rtoh_distance_cpu(const VoxelGrid* g, int set, int64_t mq, int32_t* d2, rto_dist_summary* summary) {
+    std::vector<int32_t> f;
+    if (!distanceFieldCPU(*g, set, mq, f, summary)) return 0;
+    if (d2) std::copy(f.begin(), f.end(), d2);
+    return 1;
+}
+int64_t rtoh_morphology_cpu(VoxelGrid* g, int op, int64_t rq) { return applyMorphologyCPU(*g, op, rq); }
+// RayTracerBVH::distanceField: the class's code; d2 (capacity int32) and summary may be NULL.  rtoh_rt_morphology: changed, or the
+// refusal's code.  rtoh_rt_thickest_point: the class's code; out = found, i, j, k, d2 as int64 and the distance.
+int rtoh_rt_distance_field(RayTracerBVH* rt, int set, float maxDist, int32_t* d2, int64_t capacity, rto_dist_summary* summary) {
+    std::vector<int32_t> f;
+    const int rc = rt->distanceField(set, maxDist, d2 ? &f : nullptr, summary);
+    if (rc != RTO_OK) return rc;
+    if (d2) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), d2);
+    return RTO_OK;
+}
+int64_t rtoh_rt_morphology(RayTracerBVH* rt, int op, float radius) {
+    switch (op) {
+        case RTO_MORPH_DILATE: return rt->dilate(radius);
+        case RTO_MORPH_ERODE: return rt->erode(radius);
+        case RTO_MORPH_OPEN: return rt->open(radius);
+        case RTO_MORPH_CLOSE: return rt->close(radius);
+        default: return RTO_E_INVALID;
+    }
+}
+int rtoh_rt_thickest_point(RayTracerBVH* rt, int64_t out[5], double* distance) {
+    RayTracerBVH::ThickestPoint t;
+    const int rc = rt->thickestPoint(t);
+    out[0] = t.found ? 1 : 0; out[1] = t.i; out[2] = t.j; out[3] = t.k; out[4] = t.d2;
+    *distance = t.distance;
+    return rc;
 }
 // RayTracerBVH::locate / census / nearestSolid: the C ABI's records back out; each returns the class's code (RTO_OK or the refusal's)
 int rtoh_rt_locate(RayTracerBVH* rt, const float* points, int64_t n, rto_point_hit* hits) {
