@@ -239,7 +239,7 @@ static void free_components(rto_context* c) {
 // The resident distance field (rto_distance.inc): it describes one state of the grid.
 static void free_distance(rto_context* c) { (void)hipFree(c->d_dist); c->d_dist = nullptr; }
 
-// The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rto_edit_voxels rebuilds from it).
+// The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
     free_distance(c);
@@ -538,7 +538,59 @@ struct BuildScratch {
         return e;
     }
 };
+// The timing events of one call.  Declared BEFORE create(), which makes them one by one: when a create fails, the ones already
+// made go with the scope and nothing leaks.
+template <int N> struct StreamEvents {
+    hipEvent_t ev[N];
+    int made = 0;
+    StreamEvents() = default;
+    StreamEvents(const StreamEvents&) = delete;
+    StreamEvents& operator=(const StreamEvents&) = delete;
+    ~StreamEvents() { for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]); }
+    hipError_t create() {
+        for (; made < N; made++) {
+            const hipError_t e = hipEventCreate(&ev[made]);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    hipError_t record(int i, hipStream_t s) { return hipEventRecord(ev[i], s); }
+    hipError_t elapsed(int i, int j, float* ms) { return hipEventElapsedTime(ms, ev[i], ev[j]); }
+};
+// The changed-voxel count of a grid edit: one 64-bit word of the call's scratch that the edit kernel's blocks add into
+// (block_add_count, rto_device.hip.h).
+struct ChangedCount {
+    unsigned long long* d = nullptr;
+    hipError_t alloc(BuildScratch& scratch) { return scratch.alloc(&d, 1); }
+    hipError_t clear(hipStream_t s) { return hipMemsetAsync(d, 0, sizeof(unsigned long long), s); }
+    // behind the launch: waits for the stream, then *out is what the kernel counted
+    hipError_t read(hipStream_t s, unsigned long long* out) {
+        const hipError_t e = hipMemcpyAsync(out, d, sizeof *out, hipMemcpyDeviceToHost, s);
+        return e != hipSuccess ? e : hipStreamSynchronize(s);
+    }
+};
 }  // namespace
+
+// The root depth of a grid: the smallest R with 2^R >= its largest dimension.
+static int root_depth_of(int dimX, int dimY, int dimZ) {
+    const int maxDim = std::max(dimX, std::max(dimY, dimZ));
+    int R = 0;
+    while ((1 << R) < maxDim) R++;
+    return R;
+}
+
+// Voxels of the resident grid.
+static int64_t grid_voxels(const rto_context* c) { return (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2]; }
+
+// Is a voxel grid resident?  What every entry point that reads or writes c->d_vox asks first.  index32 != nullptr: the caller
+// addresses voxels with 32 bits, so the grid must also hold at most 2^31 - 2 of them; the text ends the message ("" for none).
+static int resident_grid_check(rto_context* c, const char* who, const char* index32 = nullptr) {
+    const std::string w(who);
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, w + ": no octree built");
+    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, w + ": the octree came from rto_upload_octree: no voxel grid is resident");
+    if (index32 && grid_voxels(c) > 0x7ffffffell) return fail(c, RTO_E_UNSUPPORTED, w + ": the grid has more than 2^31 - 2 voxels" + index32);
+    return RTO_OK;
+}
 
 // Per-octree derived data of canonical trees, made once after upload / build on the context's stream (synchronises):
 // descPos (position + size of every internal node: the frustum update and the cells read it) and the coarse cells of the
@@ -618,7 +670,7 @@ static int build_cells_impl(rto_context* c) {
 // The four-launch build (k_mb_*): fills c->d_nodes / d_desc / d_descFirstChild from c->d_vox.  *total / *internal: sizes;
 // solidBox: lo[3], hi[3] of the cells that hold FILLED voxels (level-1 cell precision; lo > hi: nothing solid).
 // Host voxels (if any) are uploaded here (between the events e0 and e1), after the scratch has been allocated and the chunk sums
-// zeroed; voxels == nullptr: c->d_vox already holds the grid (rto_edit_voxels) and e0, e1 bracket nothing.
+// zeroed; voxels == nullptr: c->d_vox already holds the grid (rebuild_from_resident_grid) and e0, e1 bracket nothing.
 static int build_octree_morton(rto_context* c, hipStream_t s, BuildScratch& scratch, int R, int dimX, int dimY, int dimZ,
                                const uint8_t* voxels, hipEvent_t e0, hipEvent_t e1, int64_t* total, int64_t* internal, int solidBox[6]) {
     MbLevels Lv;
@@ -699,10 +751,7 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
     if (!c) return RTO_E_INVALID;
     if (!voxels || !grid_min || dimX <= 0 || dimY <= 0 || dimZ <= 0)
         return fail(c, RTO_E_INVALID, "rto_build_octree: empty voxel grid (createOctreeFromVoxelGrid returns no root for it)");
-    int maxDim = dimX > dimY ? dimX : dimY;
-    if (dimZ > maxDim) maxDim = dimZ;
-    int R = 0;
-    while ((1 << R) < maxDim) R++;
+    const int R = root_depth_of(dimX, dimY, dimZ);
     if (R > kMaxDepth) return fail(c, RTO_E_UNSUPPORTED, "rto_build_octree: grid too large");
     RTO_HIP(c, hipSetDevice(c->device));
     RTO_HIP(c, hipStreamSynchronize(c->stream));
@@ -718,15 +767,14 @@ int rto_build_octree(rto_context* c, const uint8_t* voxels, int dimX, int dimY, 
 }  // extern "C"
 
 // The build proper: the octree of the grid in c->d_vox (dims c->voxDim, root 2^R), into arrays the caller has freed (free_octree /
-// free_octree_arrays).  voxels != nullptr (rto_build_octree): they are first copied into c->d_vox, between the events e0 and e1;
-// nullptr (rto_edit_voxels): c->d_vox already holds them and the upload time reads 0.
+// free_octree_arrays).  voxels != nullptr (rto_build_octree): they are first copied into c->d_vox, between the events 0 and 1;
+// nullptr (rebuild_from_resident_grid): c->d_vox already holds them and the upload time reads 0.
 static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
     const int dimX = c->voxDim[0], dimY = c->voxDim[1], dimZ = c->voxDim[2];
     hipStream_t s = c->stream;
     BuildScratch scratch(c->stream);
-    hipEvent_t e0, e1, e2;
-    RTO_HIP(c, hipEventCreate(&e0)); RTO_HIP(c, hipEventCreate(&e1)); RTO_HIP(c, hipEventCreate(&e2));
-    struct EvGuard { hipEvent_t a, b, d; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); } } evg{ e0, e1, e2 };
+    StreamEvents<3> events;
+    RTO_HIP(c, events.create());
 
     // ---- voxels -> HBM
     const size_t nvox = (size_t)dimX * dimY * dimZ;
@@ -738,13 +786,13 @@ static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
     RTO_HIP(c, scratch.alloc(&d_bbox, 6));
     if (R >= 1 && R <= kMbMaxDepth && c->buildPath == 0) {
         // four launches whatever the depth: every level ranked and emitted at once (Morton order == BFS order within a level)
-        const int rc = build_octree_morton(c, s, scratch, R, dimX, dimY, dimZ, voxels, e0, e1, &total, &internal, box);
+        const int rc = build_octree_morton(c, s, scratch, R, dimX, dimY, dimZ, voxels, events.ev[0], events.ev[1], &total, &internal, box);
         if (rc != RTO_OK) return rc;
         haveBox = true;
     } else {
-        RTO_HIP(c, hipEventRecord(e0, s));
+        RTO_HIP(c, events.record(0, s));
         if (voxels) RTO_HIP(c, hipMemcpyAsync(d_vox, voxels, nvox, hipMemcpyHostToDevice, s));
-        RTO_HIP(c, hipEventRecord(e1, s));
+        RTO_HIP(c, events.record(1, s));
         // level-by-level form (any depth up to kMaxDepth; also the cross-check of the other: rto_debug_set_build_path)
         // ---- occupancy pyramid, bottom-up; every level also leaves its number of mixed cells = internal nodes
         PyramidView V;
@@ -842,22 +890,58 @@ static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
         RTO_HIP(c, hipMemcpyAsync(d_bbox, initBox, sizeof initBox, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_solid_bbox, dim3((unsigned)std::min<int64_t>((total + kBlock - 1) / kBlock, 512)), dim3(kBlock), 0, s, c->d_nodes, total, d_bbox);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipEventRecord(e2, s));
+        RTO_HIP(c, events.record(2, s));
         RTO_HIP(c, hipMemcpyAsync(box, d_bbox, sizeof box, hipMemcpyDeviceToHost, s));
-    } else RTO_HIP(c, hipEventRecord(e2, s));
+    } else RTO_HIP(c, events.record(2, s));
     RTO_HIP(c, hipStreamSynchronize(s));
     for (int a = 0; a < 3; a++) {
         c->solidCentre[a] = box[a] <= box[3 + a] ? 0.5f * (float)(box[a] + box[3 + a]) : 0.5f * (float)(1 << R);
         c->solidLo[a] = box[a] <= box[3 + a] ? box[a] : 1; c->solidHi[a] = box[a] <= box[3 + a] ? box[3 + a] : 0;
     }
-    RTO_HIP(c, hipEventElapsedTime(&c->buildUploadMs, e0, e1));
-    RTO_HIP(c, hipEventElapsedTime(&c->buildMs, e1, e2));
+    RTO_HIP(c, events.elapsed(0, 1, &c->buildUploadMs));
+    RTO_HIP(c, events.elapsed(1, 2, &c->buildMs));
 
     c->numNodes = total; c->visibleNodes = total; c->numInternal = internal;
     c->rootSize = 1 << R; c->depth = R;
     c->canonical = internal > 0;                 // a one-node tree is rendered by the generic kernel
     c->anyOrderStackNeed = 0;
     return build_cells(c);
+}
+
+// The tail of the rto_download_* entries of resident per-grid arrays: `count` elements of `elem` bytes, once the stream has drained.
+static int download_resident(rto_context* c, const char* who, void* out, int64_t capacity, const void* src, int64_t count, size_t elem) {
+    if (!out || capacity < count) return fail(c, RTO_E_INVALID, std::string(who) + ": capacity too small");
+    if (count == 0) return RTO_OK;
+    RTO_HIP(c, hipSetDevice(c->device));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
+    RTO_HIP(c, hipMemcpy(out, src, (size_t)count * elem, hipMemcpyDeviceToHost));
+    return RTO_OK;
+}
+
+// The one way from a changed resident grid back to a renderable context: what rto_build_octree(that grid, same gridMin, same
+// voxelSize) leaves, followed by rto_build_leaf_triangles(NULL) when `triangles` -- the callers pass "were triangles resident?",
+// sampled before the call, or what their parameters ask for.  Every grid edit and the voxelizer's commit end here.
+//   dropped:  the octree's arrays and all that describes the grid or the tree as it was (free_octree_arrays): component labels,
+//             distance field, leaf triangles and their records, cull buffers and the culling switch, occupancy cells, mesh levels;
+//             every stream's tile orders and cost history are invalidated.
+//   survives: d_vox, voxDim, gridMin, voxelSize, buildPath (and everything that is not per octree: kernel mode, frame buffers,
+//             the last extracted mesh).
+//   timing:   each build's buildMs goes to *octree_ms / *tris_ms (either may be nullptr) as soon as that build has succeeded.
+//   failure:  the failing build's code and message are returned.  The octree build fails: numNodes == 0, so the context
+//             answers RTO_E_NO_OCTREE until a build succeeds; the grid stays in d_vox; arrays the build had already allocated are
+//             released by the next free_octree_arrays or by rto_destroy.  The triangle build fails: the new octree is complete
+//             and usable, *octree_ms is written, and the triangle buffers are what rto_build_leaf_triangles leaves on that error.
+static int rebuild_from_resident_grid(rto_context* c, bool triangles, float* octree_ms, float* tris_ms) {
+    const int R = root_depth_of(c->voxDim[0], c->voxDim[1], c->voxDim[2]);
+    free_octree_arrays(c);
+    const int rcBuild = build_octree_resident(c, nullptr, R);
+    if (rcBuild != RTO_OK) return rcBuild;
+    if (octree_ms) *octree_ms = c->buildMs;
+    if (!triangles) return RTO_OK;
+    const int rcTris = rto_build_leaf_triangles(c, nullptr, 0, 0, 0);
+    if (rcTris != RTO_OK) return rcTris;
+    if (tris_ms) *tris_ms = c->buildMs;
+    return RTO_OK;
 }
 
 extern "C" {
@@ -2182,16 +2266,13 @@ int rto_build_leaf_triangles(rto_context* c, const uint8_t* voxels, int dimX, in
     hipStream_t s = c->stream;
     RTO_HIP(c, hipDeviceSynchronize());          // frames in flight on any stream still read the old buffers / descriptors
     BuildScratch scratch(c->stream);
-    hipEvent_t e0, e1, e2;
-    RTO_HIP(c, hipEventCreate(&e0)); RTO_HIP(c, hipEventCreate(&e1)); RTO_HIP(c, hipEventCreate(&e2));
-    struct EvGuard { hipEvent_t a, b, d; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(d); } } evg{ e0, e1, e2 };
+    StreamEvents<3> events;
+    RTO_HIP(c, events.create());
     const uint8_t* d_vox = nullptr;
-    RTO_HIP(c, hipEventRecord(e0, s));
+    RTO_HIP(c, events.record(0, s));
     if (voxels) {
         if (dimX <= 0 || dimY <= 0 || dimZ <= 0) return fail(c, RTO_E_INVALID, "rto_build_leaf_triangles: bad grid dimensions");
-        int maxDim = dimX > dimY ? dimX : dimY;
-        if (dimZ > maxDim) maxDim = dimZ;
-        if (maxDim > c->rootSize) return fail(c, RTO_E_INVALID, "rto_build_leaf_triangles: the grid is larger than the resident octree's root");
+        if (std::max(dimX, std::max(dimY, dimZ)) > c->rootSize) return fail(c, RTO_E_INVALID, "rto_build_leaf_triangles: the grid is larger than the resident octree's root");
         uint8_t* up = nullptr;
         RTO_HIP(c, scratch.alloc(&up, (size_t)dimX * dimY * dimZ));
         RTO_HIP(c, hipMemcpyAsync(up, voxels, (size_t)dimX * dimY * dimZ, hipMemcpyHostToDevice, s));
@@ -2200,7 +2281,7 @@ int rto_build_leaf_triangles(rto_context* c, const uint8_t* voxels, int dimX, in
         if (!c->d_vox) return fail(c, RTO_E_INVALID, "rto_build_leaf_triangles: voxels == NULL needs an octree made by rto_build_octree");
         d_vox = c->d_vox; dimX = c->voxDim[0]; dimY = c->voxDim[1]; dimZ = c->voxDim[2];
     }
-    RTO_HIP(c, hipEventRecord(e1, s));
+    RTO_HIP(c, events.record(1, s));
     if (!c->d_mcCases) {
         unsigned long long packed[256];
         pack_mc_cases(packed);
@@ -2262,10 +2343,10 @@ int rto_build_leaf_triangles(rto_context* c, const uint8_t* voxels, int dimX, in
         const int rcRec = build_triangle_records(c, s);
         if (rcRec != RTO_OK) return rcRec;
     }
-    RTO_HIP(c, hipEventRecord(e2, s));
+    RTO_HIP(c, events.record(2, s));
     RTO_HIP(c, hipStreamSynchronize(s));
-    RTO_HIP(c, hipEventElapsedTime(&c->buildUploadMs, e0, e1));
-    RTO_HIP(c, hipEventElapsedTime(&c->buildMs, e1, e2));
+    RTO_HIP(c, events.elapsed(0, 1, &c->buildUploadMs));
+    RTO_HIP(c, events.elapsed(1, 2, &c->buildMs));
     return RTO_OK;
 }
 

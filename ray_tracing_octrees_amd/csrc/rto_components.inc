@@ -426,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_select(const CcComp* __restrict__
 }
 
 // Every voxel of a selected component takes newValue.  A thread owns 16 consecutive voxels (WIDE: n % 16 == 0, one 16-byte
-// store when anything changed).  The count: a wave reduction, then one 64-bit atomic per block, as k_edit_brushes counts.
+// store when anything changed).  The count: block_add_count.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_cc_flip(uint8_t* __restrict__ vox, const int* __restrict__ labels, const uint8_t* __restrict__ sel,
                                                    unsigned n, unsigned newValue, unsigned long long* __restrict__ changed) {
@@ -460,15 +460,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_flip(uint8_t* __restrict__ vox, c
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    __shared__ int waveSum[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        if (s) atomicAdd(changed, (unsigned long long)s);
-    }
+    block_add_count(count, changed);
 }
 
 }  // namespace rto
@@ -489,24 +481,18 @@ int cc_check_args(rto_context* c, const char* who, int set, int connectivity) {
     const std::string w(who);
     if (set != RTO_SET_SOLID && set != RTO_SET_EMPTY) return fail(c, RTO_E_INVALID, w + ": unknown set");
     if (connectivity != RTO_CONN_FACE && connectivity != RTO_CONN_FULL) return fail(c, RTO_E_INVALID, w + ": connectivity must be 6 or 26");
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, w + ": no octree built");
-    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, w + ": the octree came from rto_upload_octree: no voxel grid is resident");
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
-    if (nvox > 0x7ffffffell) return fail(c, RTO_E_UNSUPPORTED, w + ": the grid has more than 2^31 - 2 voxels: labels are 32-bit");
-    return RTO_OK;
+    return resident_grid_check(c, who, ": labels are 32-bit");
 }
 
 // Labels the resident grid into `out` (arguments already checked).  On any error `out` is released and the context is as it was.
 int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResult& out) {
     using namespace rto;
-    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)((int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2]) };
+    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)grid_voxels(c) };
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
-    hipEvent_t ev[5];
-    int made = 0;
-    struct EvGuard { hipEvent_t* e; int* n; ~EvGuard() { for (int i = 0; i < *n; i++) (void)hipEventDestroy(e[i]); } } evg{ ev, &made };
-    for (; made < 5; made++) RTO_HIP(c, hipEventCreate(&ev[made]));
+    StreamEvents<5> events;
+    RTO_HIP(c, events.create());
     struct OutGuard { CcResult* r; bool keep = false; ~OutGuard() { if (!keep) r->release(); } } og{ &out };
 
     const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
@@ -526,7 +512,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
     RTO_HIP(c, hipMemsetAsync(d_flags, 0, kCcMaxPasses * sizeof(int), s));
 
     // (1) tiles
-    RTO_HIP(c, hipEventRecord(ev[0], s));
+    RTO_HIP(c, events.record(0, s));
     {
         const dim3 g((unsigned)tiles), b(kBlock);
         const bool wide = D.x % kCcVec == 0;
@@ -536,7 +522,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
         else hipLaunchKernelGGL((k_cc_local<false, false>), g, b, 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_parent);
         RTO_HIP(c, hipGetLastError());
     }
-    RTO_HIP(c, hipEventRecord(ev[1], s));
+    RTO_HIP(c, events.record(1, s));
     // (2) merge until a pass is clean: the first two passes go out together (the expected case: one merge, one clean check)
     int passes = 0;
     bool clean = false;
@@ -554,7 +540,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
         clean = flags[passes - 1] == 0;
     }
     if (!clean) return fail(c, RTO_E_INTERNAL, std::string(who) + ": merging did not settle in 32 passes");
-    RTO_HIP(c, hipEventRecord(ev[2], s));
+    RTO_HIP(c, events.record(2, s));
     // (3) flatten, rank, label
     hipLaunchKernelGGL(k_cc_flatten, dim3(chunks), dim3(kBlock), 0, s, d_parent, D.n, d_blockCount);
     RTO_HIP(c, hipGetLastError());
@@ -568,7 +554,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
     RTO_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(k_cc_label, dim3(chunks), dim3(kBlock), 0, s, d_parent, D.n, out.d_labels);
     RTO_HIP(c, hipGetLastError());
-    RTO_HIP(c, hipEventRecord(ev[3], s));
+    RTO_HIP(c, events.record(3, s));
     // (4) statistics
     if (total) {
         const unsigned statBlocks = (D.n + kBlock * kCcStatPerThread - 1) / (kBlock * kCcStatPerThread);
@@ -577,9 +563,9 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
         hipLaunchKernelGGL(k_cc_touches, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, s, out.d_comps, total, D);
         RTO_HIP(c, hipGetLastError());
     }
-    RTO_HIP(c, hipEventRecord(ev[4], s));
+    RTO_HIP(c, events.record(4, s));
     RTO_HIP(c, hipStreamSynchronize(s));
-    for (int i = 0; i < 4; i++) RTO_HIP(c, hipEventElapsedTime(&out.ms[i], ev[i], ev[i + 1]));
+    for (int i = 0; i < 4; i++) RTO_HIP(c, events.elapsed(i, i + 1, &out.ms[i]));
     out.count = (int64_t)total;
     out.passes = passes;
     og.keep = true;
@@ -609,23 +595,13 @@ int rto_download_components(rto_context* c, rto_component* out, int64_t capacity
     if (!c->d_ccLabels) return fail(c, RTO_E_INVALID, "rto_download_components: no labels are resident (not labelled yet, or the grid has changed since)");
     if (count) *count = c->ccCount;
     if (!out) return RTO_OK;
-    if (capacity < c->ccCount) return fail(c, RTO_E_INVALID, "rto_download_components: capacity too small");
-    if (c->ccCount == 0) return RTO_OK;
-    RTO_HIP(c, hipSetDevice(c->device));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    RTO_HIP(c, hipMemcpy(out, c->d_ccComps, (size_t)c->ccCount * sizeof(rto_component), hipMemcpyDeviceToHost));
-    return RTO_OK;
+    return download_resident(c, "rto_download_components", out, capacity, c->d_ccComps, c->ccCount, sizeof(rto_component));
 }
 
 int rto_download_labels(rto_context* c, int32_t* out, int64_t capacity) {
     if (!c) return RTO_E_INVALID;
     if (!c->d_ccLabels) return fail(c, RTO_E_INVALID, "rto_download_labels: no labels are resident (not labelled yet, or the grid has changed since)");
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
-    if (!out || capacity < nvox) return fail(c, RTO_E_INVALID, "rto_download_labels: capacity too small");
-    RTO_HIP(c, hipSetDevice(c->device));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    RTO_HIP(c, hipMemcpy(out, c->d_ccLabels, (size_t)nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RTO_OK;
+    return download_resident(c, "rto_download_labels", out, capacity, c->d_ccLabels, grid_voxels(c), sizeof(int32_t));
 }
 
 int rto_labels_device(rto_context* c, int32_t** d_labels, rto_component** d_components, int64_t* count) {
@@ -656,7 +632,7 @@ int rto_edit_components(rto_context* c, int set, int connectivity, int select, i
     if (select < RTO_SELECT_SMALLER_THAN || select > RTO_SELECT_NOT_CONTAINING) return fail(c, RTO_E_INVALID, "rto_edit_components: unknown selection");
     const int rcArgs = cc_check_args(c, "rto_edit_components", set, connectivity);
     if (rcArgs != RTO_OK) return rcArgs;
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
+    const int64_t nvox = grid_voxels(c);
     const bool byVoxel = select == RTO_SELECT_CONTAINING || select == RTO_SELECT_NOT_CONTAINING;
     if ((byVoxel || select == RTO_SELECT_SMALLER_THAN) && arg < 0) return fail(c, RTO_E_INVALID, "rto_edit_components: arg is negative");
     if (byVoxel && arg >= nvox) return fail(c, RTO_E_INVALID, "rto_edit_components: arg is not a voxel of the grid");
@@ -669,11 +645,12 @@ int rto_edit_components(rto_context* c, int set, int connectivity, int select, i
     unsigned long long count = 0;
     {
         BuildScratch scratch(s);
-        uint8_t* d_sel = nullptr; int* d_keep = nullptr; unsigned long long* d_count = nullptr;
+        uint8_t* d_sel = nullptr; int* d_keep = nullptr;
+        ChangedCount d_count;
         RTO_HIP(c, scratch.alloc(&d_sel, (size_t)r.count));
         RTO_HIP(c, scratch.alloc(&d_keep, 1));
-        RTO_HIP(c, scratch.alloc(&d_count, 1));
-        RTO_HIP(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+        RTO_HIP(c, d_count.alloc(scratch));
+        RTO_HIP(c, d_count.clear(s));
         if (select == RTO_SELECT_ALL_BUT_LARGEST) {
             hipLaunchKernelGGL(k_cc_largest, dim3(1), dim3(kBlock), 0, s, r.d_comps, (unsigned)r.count, d_keep);
             RTO_HIP(c, hipGetLastError());
@@ -684,28 +661,15 @@ int rto_edit_components(rto_context* c, int set, int connectivity, int select, i
         const unsigned n = (unsigned)nvox;
         const unsigned blocks = (unsigned)(((nvox + kCcVec - 1) / kCcVec + kBlock - 1) / kBlock);
         const unsigned newValue = set == RTO_SET_SOLID ? 0u : 1u;
-        if (n % kCcVec == 0) hipLaunchKernelGGL(k_cc_flip<true>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, r.d_labels, d_sel, n, newValue, d_count);
-        else hipLaunchKernelGGL(k_cc_flip<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, r.d_labels, d_sel, n, newValue, d_count);
+        if (n % kCcVec == 0) hipLaunchKernelGGL(k_cc_flip<true>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, r.d_labels, d_sel, n, newValue, d_count.d);
+        else hipLaunchKernelGGL(k_cc_flip<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, r.d_labels, d_sel, n, newValue, d_count.d);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
+        RTO_HIP(c, d_count.read(s, &count));
     }
     if (changed) *changed = (int64_t)count;
     if (count == 0) return RTO_OK;                                  // the octree, the triangles, the labels and the frustum state stay
 
-    // ---- rebuild from the resident grid, as rto_edit_voxels does after a change
-    const bool hadTris = c->d_triOffset != nullptr;
-    const int maxDim = std::max(c->voxDim[0], std::max(c->voxDim[1], c->voxDim[2]));
-    int R = 0;
-    while ((1 << R) < maxDim) R++;
-    free_octree_arrays(c);
-    const int rcBuild = build_octree_resident(c, nullptr, R);
-    if (rcBuild != RTO_OK) return rcBuild;
-    if (hadTris) {
-        const int rcTris = rto_build_leaf_triangles(c, nullptr, 0, 0, 0);
-        if (rcTris != RTO_OK) return rcTris;
-    }
-    return RTO_OK;
+    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -306,6 +306,21 @@ __device__ __forceinline__ void wave_accumulate(Counters* c, int steps, bool hit
     }
 }
 
+// The tail of a kernel (blocks of kBlock threads) that counts: every thread's count is added to *total -- a wave reduction, the
+// waves' sums through LDS, then one 64-bit atomic per block (none for a block that counted nothing).  EVERY thread of the block
+// must reach the call (it holds a barrier): call it outside the kernel's bounds test, with count == 0 for threads that own nothing.
+__device__ __forceinline__ void block_add_count(int count, unsigned long long* total) {
+    for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off);
+    __shared__ int waveSum[kBlock / kWave];
+    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
+        if (s) atomicAdd(total, (unsigned long long)s);
+    }
+}
+
 // ================================================================ generic kernel
 // Direct statement of S/RT:239-327 over the 60-byte array.
 template <int MODE>

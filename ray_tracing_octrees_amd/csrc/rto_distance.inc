@@ -201,8 +201,8 @@ __global__ __launch_bounds__(kBlock) void k_dt_summary(const int* __restrict__ d
 
 // ---- morphology: the threshold.  Every voxel equal to `from` whose field value is finite (in reach of the cap the field was made
 // with) takes `to`.  A thread owns 16 consecutive voxels (WIDE: n % 16 == 0, one 16-byte store when anything changed).  The count
-// is of voxels whose value now differs from `orig` (the grid before the call; nullptr: the grid before this launch): a wave
-// reduction, then one 64-bit atomic per workgroup, as k_cc_flip counts.
+// is of voxels whose value now differs from `orig` (the grid before the call; nullptr: the grid before this launch):
+// block_add_count.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_morph_flip(uint8_t* __restrict__ vox, const int* __restrict__ d2, const uint8_t* __restrict__ orig,
                                                       unsigned n, unsigned from, unsigned to, unsigned long long* __restrict__ changed) {
@@ -247,15 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_morph_flip(uint8_t* __restrict__ vox
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    __shared__ int waveSum[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        if (s) atomicAdd(changed, (unsigned long long)s);
-    }
+    block_add_count(count, changed);
 }
 
 }  // namespace rto
@@ -280,10 +272,8 @@ bool dt_quantize(float dist, float voxelSize, long long& mq, int& cap) {
 
 int dt_check_grid(rto_context* c, const char* who) {
     const std::string w(who);
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, w + ": no octree built");
-    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, w + ": the octree came from rto_upload_octree: no voxel grid is resident");
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
-    if (nvox > 0x7ffffffell) return fail(c, RTO_E_UNSUPPORTED, w + ": the grid has more than 2^31 - 2 voxels");
+    const int rcGrid = resident_grid_check(c, who, "");
+    if (rcGrid != RTO_OK) return rcGrid;
     int64_t diag = 0;
     for (int a = 0; a < 3; a++) diag += (int64_t)(c->voxDim[a] - 1) * (c->voxDim[a] - 1);
     if (diag >= 0x7fffffffll) return fail(c, RTO_E_UNSUPPORTED, w + ": the grid's diagonal squared does not fit the 32-bit field");
@@ -293,18 +283,16 @@ int dt_check_grid(rto_context* c, const char* who) {
 // The three passes into d_out (one int32 per voxel; arguments already checked).  ms: x, y, z pass.  The context is not touched.
 int dt_transform(rto_context* c, int set, int cap, int* d_out, float ms[3]) {
     using namespace rto;
-    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)((int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2]) };
+    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)grid_voxels(c) };
     hipStream_t s = c->stream;
-    hipEvent_t ev[4];
-    int made = 0;
-    struct EvGuard { hipEvent_t* e; int* n; ~EvGuard() { for (int i = 0; i < *n; i++) (void)hipEventDestroy(e[i]); } } evg{ ev, &made };
-    for (; made < 4; made++) RTO_HIP(c, hipEventCreate(&ev[made]));
+    StreamEvents<4> events;
+    RTO_HIP(c, events.create());
     BuildScratch scratch(s);
     unsigned* d_stPos = nullptr; int* d_stVal = nullptr;
     RTO_HIP(c, scratch.alloc(&d_stPos, (size_t)D.n));
     RTO_HIP(c, scratch.alloc(&d_stVal, (size_t)D.n));
     const unsigned setValue = set == RTO_SET_SOLID ? 1u : 0u;
-    RTO_HIP(c, hipEventRecord(ev[0], s));
+    RTO_HIP(c, events.record(0, s));
     {
         const int rowWords = (D.x + 31) / 32;
         const int rowsPerBlock = std::max(1, kDtRowVox / D.x);          // rowsPerBlock * rowWords <= kDtMaskWords (rowWords <= dimX)
@@ -314,18 +302,18 @@ int dt_transform(rto_context* c, int set, int cap, int* d_out, float ms[3]) {
         else hipLaunchKernelGGL(k_dt_x<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, D, rowsPerBlock, rowWords, numRows, setValue, cap, d_out);
         RTO_HIP(c, hipGetLastError());
     }
-    RTO_HIP(c, hipEventRecord(ev[1], s));
+    RTO_HIP(c, events.record(1, s));
     {
         const unsigned colsY = (unsigned)D.x * (unsigned)D.z, colsZ = (unsigned)D.x * (unsigned)D.y;
         hipLaunchKernelGGL(k_dt_axis<1>, dim3((colsY + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d_out, D, colsY, cap, d_stPos, d_stVal);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipEventRecord(ev[2], s));
+        RTO_HIP(c, events.record(2, s));
         hipLaunchKernelGGL(k_dt_axis<2>, dim3((colsZ + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d_out, D, colsZ, cap, d_stPos, d_stVal);
         RTO_HIP(c, hipGetLastError());
     }
-    RTO_HIP(c, hipEventRecord(ev[3], s));
+    RTO_HIP(c, events.record(3, s));
     RTO_HIP(c, hipStreamSynchronize(s));
-    for (int i = 0; i < 3; i++) RTO_HIP(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    for (int i = 0; i < 3; i++) RTO_HIP(c, events.elapsed(i, i + 1, &ms[i]));
     return RTO_OK;
 }
 
@@ -347,7 +335,7 @@ int rto_distance_field(rto_context* c, int set, float max_dist, rto_dist_summary
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned n = (unsigned)((int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2]);
+    const unsigned n = (unsigned)grid_voxels(c);
     int* d_new = nullptr;
     RTO_HIP(c, hipMalloc(&d_new, (size_t)n * sizeof(int)));
     struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
@@ -355,21 +343,20 @@ int rto_distance_field(rto_context* c, int set, float max_dist, rto_dist_summary
     const int rc = dt_transform(c, set, cap, d_new, ms);
     if (rc != RTO_OK) return rc;
     if (summary) {
-        hipEvent_t e0, e1;
-        RTO_HIP(c, hipEventCreate(&e0)); RTO_HIP(c, hipEventCreate(&e1));
-        struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ e0, e1 };
+        StreamEvents<2> events;
+        RTO_HIP(c, events.create());
         BuildScratch scratch(s);
         unsigned long long* d_red = nullptr;
         RTO_HIP(c, scratch.alloc(&d_red, 2));
         RTO_HIP(c, hipMemsetAsync(d_red, 0, 2 * sizeof(unsigned long long), s));
-        RTO_HIP(c, hipEventRecord(e0, s));
+        RTO_HIP(c, events.record(0, s));
         hipLaunchKernelGGL(k_dt_summary, dim3((n + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, s, d_new, n, d_red, d_red + 1);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipEventRecord(e1, s));
+        RTO_HIP(c, events.record(1, s));
         unsigned long long red[2] = { 0ull, 0ull };
         RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
         RTO_HIP(c, hipStreamSynchronize(s));
-        RTO_HIP(c, hipEventElapsedTime(&ms[3], e0, e1));
+        RTO_HIP(c, events.elapsed(0, 1, &ms[3]));
         summary->finite = (int64_t)red[1];
         summary->max_d2 = red[1] ? (int64_t)(red[0] >> 32) : -1;
         summary->argmax = red[1] ? (int64_t)(~(unsigned)(red[0] & 0xffffffffull)) : -1;
@@ -385,12 +372,7 @@ int rto_distance_field(rto_context* c, int set, float max_dist, rto_dist_summary
 int rto_download_distance(rto_context* c, int32_t* out, int64_t capacity) {
     if (!c) return RTO_E_INVALID;
     if (!c->d_dist) return fail(c, RTO_E_INVALID, "rto_download_distance: no distance field is resident (not made yet, or the grid has changed since)");
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
-    if (!out || capacity < nvox) return fail(c, RTO_E_INVALID, "rto_download_distance: capacity too small");
-    RTO_HIP(c, hipSetDevice(c->device));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    RTO_HIP(c, hipMemcpy(out, c->d_dist, (size_t)nvox * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return RTO_OK;
+    return download_resident(c, "rto_download_distance", out, capacity, c->d_dist, grid_voxels(c), sizeof(int32_t));
 }
 
 int rto_distance_device(rto_context* c, int32_t** d_d2) {
@@ -423,20 +405,20 @@ int rto_edit_morphology(rto_context* c, int op, float radius, int64_t* changed) 
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned n = (unsigned)((int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2]);
+    const unsigned n = (unsigned)grid_voxels(c);
     // DILATE grows the SOLID set into the EMPTY voxels in reach; ERODE grows the EMPTY set into the FILLED ones
     const int first = (op == RTO_MORPH_DILATE || op == RTO_MORPH_CLOSE) ? RTO_SET_SOLID : RTO_SET_EMPTY;
     const int steps = (op == RTO_MORPH_OPEN || op == RTO_MORPH_CLOSE) ? 2 : 1;
     unsigned long long count = 0;
     {
-        hipEvent_t e0, e1;
-        RTO_HIP(c, hipEventCreate(&e0)); RTO_HIP(c, hipEventCreate(&e1));
-        struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ e0, e1 };
+        StreamEvents<2> events;
+        RTO_HIP(c, events.create());
         BuildScratch scratch(s);
-        int* d_field = nullptr; uint8_t* d_orig = nullptr; unsigned long long* d_count = nullptr;
+        int* d_field = nullptr; uint8_t* d_orig = nullptr;
+        ChangedCount d_count;
         RTO_HIP(c, scratch.alloc(&d_field, (size_t)n));
-        RTO_HIP(c, scratch.alloc(&d_count, 1));
-        RTO_HIP(c, hipEventRecord(e0, s));
+        RTO_HIP(c, d_count.alloc(scratch));
+        RTO_HIP(c, events.record(0, s));
         RTO_HIP(c, scratch.alloc(&d_orig, (size_t)n));               // the grid before the call: what OPEN and CLOSE count against, and what an error restores
         RTO_HIP(c, hipMemcpyAsync(d_orig, c->d_vox, (size_t)n, hipMemcpyDeviceToDevice, s));
         const unsigned blocks = (unsigned)((((int64_t)n + kCcVec - 1) / kCcVec + kBlock - 1) / kBlock);
@@ -447,14 +429,13 @@ int rto_edit_morphology(rto_context* c, int op, float radius, int64_t* changed) 
             if (rc == RTO_OK) {
                 const unsigned from = set == RTO_SET_SOLID ? 0u : 1u, to = set == RTO_SET_SOLID ? 1u : 0u;
                 const uint8_t* orig = step == 0 ? nullptr : d_orig;
-                hipError_t e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s);
+                hipError_t e = d_count.clear(s);
                 if (e == hipSuccess) {
-                    if (n % kCcVec == 0) hipLaunchKernelGGL(k_morph_flip<true>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, orig, n, from, to, d_count);
-                    else hipLaunchKernelGGL(k_morph_flip<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, orig, n, from, to, d_count);
+                    if (n % kCcVec == 0) hipLaunchKernelGGL(k_morph_flip<true>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, orig, n, from, to, d_count.d);
+                    else hipLaunchKernelGGL(k_morph_flip<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, orig, n, from, to, d_count.d);
                     e = hipGetLastError();
                 }
-                if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipStreamSynchronize(s);
+                if (e == hipSuccess) e = d_count.read(s, &count);
                 if (e != hipSuccess) rc = fail(c, RTO_E_HIP, std::string("rto_edit_morphology: ") + hipGetErrorString(e));
             }
             if (rc != RTO_OK) {                                         // give the grid back as it was before the first step
@@ -463,28 +444,14 @@ int rto_edit_morphology(rto_context* c, int op, float radius, int64_t* changed) 
                 return rc;
             }
         }
-        RTO_HIP(c, hipEventRecord(e1, s));
+        RTO_HIP(c, events.record(1, s));
         RTO_HIP(c, hipStreamSynchronize(s));
-        RTO_HIP(c, hipEventElapsedTime(&c->morphMs[0], e0, e1));
+        RTO_HIP(c, events.elapsed(0, 1, &c->morphMs[0]));
     }
     if (changed) *changed = (int64_t)count;
     if (count == 0) return RTO_OK;           // the grid is byte for byte what it was: octree, triangles, labels, field and frustum state stay
 
-    // ---- rebuild from the resident grid, as rto_edit_voxels and rto_edit_components do after a change
-    const bool hadTris = c->d_triOffset != nullptr;
-    const int maxDim = std::max(c->voxDim[0], std::max(c->voxDim[1], c->voxDim[2]));
-    int R = 0;
-    while ((1 << R) < maxDim) R++;
-    free_octree_arrays(c);
-    const int rcBuild = build_octree_resident(c, nullptr, R);
-    if (rcBuild != RTO_OK) return rcBuild;
-    c->morphMs[1] = c->buildMs;
-    if (hadTris) {
-        const int rcTris = rto_build_leaf_triangles(c, nullptr, 0, 0, 0);
-        if (rcTris != RTO_OK) return rcTris;
-        c->morphMs[2] = c->buildMs;
-    }
-    return RTO_OK;
+    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->morphMs[1], &c->morphMs[2]);
 }
 
 int rto_last_morphology_ms(const rto_context* c, float ms[3]) {

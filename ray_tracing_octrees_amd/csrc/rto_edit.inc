@@ -26,8 +26,8 @@ struct EditBox { int x0, xlo, y0, z0, x1, y1, z1; int runsX, blocksX, blocksY; }
 // One launch over the union box.  Each thread owns one x-aligned run of 16 voxels of one row and scans the brushes from the last
 // back: the first brush that covers a voxel decides it, voxels no brush covers keep their value.  Rows of a grid with dimX % 16 ==
 // 0 are read and written 16 bytes at a time (WIDE: the box rounded out to 16-byte chunks, bytes outside it written back as
-// they were, and only runs with a change are written); other grids read and write only bytes inside the box.  The changed count: a wave
-// reduction, then one atomic per block.
+// they were, and only runs with a change are written); other grids read and write only bytes inside the box.  The changed count:
+// block_add_count.
 template <bool WIDE>
 __global__ __launch_bounds__(kBlock) void k_edit_brushes(uint8_t* __restrict__ vox, int dimX, int dimY, const EditBrush* __restrict__ brushes,
                                                         int n, EditBox box, unsigned long long* __restrict__ changed) {
@@ -93,15 +93,7 @@ __global__ __launch_bounds__(kBlock) void k_edit_brushes(uint8_t* __restrict__ v
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    __shared__ int waveSum[kBlock / kWave];
-    if ((t % kWave) == 0) waveSum[t / kWave] = count;
-    __syncthreads();
-    if (t == 0) {
-        int s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        if (s) atomicAdd(changed, (unsigned long long)s);
-    }
+    block_add_count(count, changed);
 }
 
 }  // namespace rto
@@ -169,8 +161,8 @@ int rto_edit_voxels(rto_context* c, const rto_brush* brushes, int n, int64_t* ch
     if (changed) *changed = 0;
     if (n < 0 || n > RTO_EDIT_MAX_BRUSHES) return fail(c, RTO_E_INVALID, "rto_edit_voxels: n must lie in [0, 65536]");
     if (n > 0 && !brushes) return fail(c, RTO_E_INVALID, "rto_edit_voxels: brushes is NULL");
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_edit_voxels: no octree built");
-    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, "rto_edit_voxels: the octree came from rto_upload_octree: no voxel grid is resident");
+    const int rcGrid = resident_grid_check(c, "rto_edit_voxels");
+    if (rcGrid != RTO_OK) return rcGrid;
     const int dims[3] = { c->voxDim[0], c->voxDim[1], c->voxDim[2] };
     std::vector<rto::EditBrush> host((size_t)n);
     int box[6] = { dims[0], dims[1], dims[2], -1, -1, -1 };        // union, inclusive
@@ -189,18 +181,17 @@ int rto_edit_voxels(rto_context* c, const rto_brush* brushes, int n, int64_t* ch
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
-    hipEvent_t e0, e1;
-    RTO_HIP(c, hipEventCreate(&e0)); RTO_HIP(c, hipEventCreate(&e1));
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ e0, e1 };
+    StreamEvents<2> events;
+    RTO_HIP(c, events.create());
     unsigned long long count = 0;
     {
         BuildScratch scratch(s);
         rto::EditBrush* d_brushes = nullptr;
-        unsigned long long* d_count = nullptr;
+        ChangedCount d_count;
         RTO_HIP(c, scratch.alloc(&d_brushes, (size_t)n));
-        RTO_HIP(c, scratch.alloc(&d_count, 1));
+        RTO_HIP(c, d_count.alloc(scratch));
         RTO_HIP(c, hipMemcpyAsync(d_brushes, host.data(), (size_t)n * sizeof(rto::EditBrush), hipMemcpyHostToDevice, s));
-        RTO_HIP(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+        RTO_HIP(c, d_count.clear(s));
         rto::EditBox eb;
         eb.xlo = box[0]; eb.x0 = box[0] & ~(rto::kEditRun - 1); eb.y0 = box[1]; eb.z0 = box[2];
         eb.x1 = box[3] + 1; eb.y1 = box[4] + 1; eb.z1 = box[5] + 1;
@@ -209,49 +200,29 @@ int rto_edit_voxels(rto_context* c, const rto_brush* brushes, int n, int64_t* ch
         eb.blocksY = (eb.y1 - eb.y0 + rto::kEditRowsY - 1) / rto::kEditRowsY;
         const long long blocks = (long long)eb.blocksX * eb.blocksY * (eb.z1 - eb.z0);
         if (blocks > 0x7fffffffll) return fail(c, RTO_E_UNSUPPORTED, "rto_edit_voxels: the brushes' box is too large for one launch");
-        RTO_HIP(c, hipEventRecord(e0, s));
+        RTO_HIP(c, events.record(0, s));
         if (dims[0] % rto::kEditRun == 0)
-            hipLaunchKernelGGL(rto::k_edit_brushes<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, c->d_vox, dims[0], dims[1], d_brushes, n, eb, d_count);
+            hipLaunchKernelGGL(rto::k_edit_brushes<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, c->d_vox, dims[0], dims[1], d_brushes, n, eb, d_count.d);
         else
-            hipLaunchKernelGGL(rto::k_edit_brushes<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, c->d_vox, dims[0], dims[1], d_brushes, n, eb, d_count);
+            hipLaunchKernelGGL(rto::k_edit_brushes<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, c->d_vox, dims[0], dims[1], d_brushes, n, eb, d_count.d);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipEventRecord(e1, s));
-        RTO_HIP(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
+        RTO_HIP(c, events.record(1, s));
+        RTO_HIP(c, d_count.read(s, &count));
     }
-    RTO_HIP(c, hipEventElapsedTime(&c->editMs[0], e0, e1));
+    RTO_HIP(c, events.elapsed(0, 1, &c->editMs[0]));
     if (changed) *changed = (int64_t)count;
     if (count == 0) return RTO_OK;                                  // the octree, the triangles and the frustum state stay as they were
 
-    // ---- rebuild from the resident grid: what rto_build_octree(edited grid, same gridMin, same voxelSize) leaves
-    const bool hadTris = c->d_triOffset != nullptr;
-    int maxDim = std::max(dims[0], std::max(dims[1], dims[2]));
-    int R = 0;
-    while ((1 << R) < maxDim) R++;
-    free_octree_arrays(c);
-    const int rcBuild = build_octree_resident(c, nullptr, R);
-    if (rcBuild != RTO_OK) return rcBuild;
-    c->editMs[1] = c->buildMs;
-    if (hadTris) {
-        const int rcTris = rto_build_leaf_triangles(c, nullptr, 0, 0, 0);
-        if (rcTris != RTO_OK) return rcTris;
-        c->editMs[2] = c->buildMs;
-    }
-    return RTO_OK;
+    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->editMs[1], &c->editMs[2]);
 }
 
 int rto_download_voxels(rto_context* c, uint8_t* out, int64_t capacity, int dims[3]) {
     if (!c) return RTO_E_INVALID;
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_download_voxels: no octree built");
-    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, "rto_download_voxels: the octree came from rto_upload_octree: no voxel grid is resident");
+    const int rcGrid = resident_grid_check(c, "rto_download_voxels");
+    if (rcGrid != RTO_OK) return rcGrid;
     if (dims) { dims[0] = c->voxDim[0]; dims[1] = c->voxDim[1]; dims[2] = c->voxDim[2]; }
     if (!out) return RTO_OK;
-    const int64_t nvox = (int64_t)c->voxDim[0] * c->voxDim[1] * c->voxDim[2];
-    if (capacity < nvox) return fail(c, RTO_E_INVALID, "rto_download_voxels: capacity too small");
-    RTO_HIP(c, hipSetDevice(c->device));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    RTO_HIP(c, hipMemcpy(out, c->d_vox, (size_t)nvox, hipMemcpyDeviceToHost));
-    return RTO_OK;
+    return download_resident(c, "rto_download_voxels", out, capacity, c->d_vox, grid_voxels(c), 1);
 }
 
 int rto_last_edit_ms(const rto_context* c, float ms[3]) {

@@ -256,13 +256,10 @@ int rto_extract_mesh(rto_context* c, int kind, const rto_mesh_cull* cull, int64_
     P.rootSize = c->rootSize;
     P.dimX = c->voxDim[0]; P.dimY = c->voxDim[1]; P.dimZ = c->voxDim[2];
 
-    // count + cull: ev[0] .. ev[1]; ranking passes: ev[1] .. ev[2]; emit: ev[3] .. ev[4], begun after the count's read-back and
+    // count + cull: events 0 .. 1; ranking passes: events 1 .. 2; emit: events 3 .. 4, begun after the count's read-back and
     // the output buffer's growth, which belong to the call's wall time and to no phase
-    constexpr int kEv = 5;
-    hipEvent_t ev[kEv];
-    for (int i = 0; i < kEv; i++) ev[i] = nullptr;
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < kEv; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ ev };
-    for (int i = 0; i < kEv; i++) RTO_HIP(c, hipEventCreate(&ev[i]));
+    StreamEvents<5> events;
+    RTO_HIP(c, events.create());
 
     BuildScratch scratch(s);
     unsigned *d_cnt = nullptr, *d_off = nullptr;
@@ -273,13 +270,13 @@ int rto_extract_mesh(rto_context* c, int kind, const rto_mesh_cull* cull, int64_
     const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
 
     // ---- count + cull
-    RTO_HIP(c, hipEventRecord(ev[0], s));
+    RTO_HIP(c, events.record(0, s));
     if (kind == RTO_MESH_MC)
         hipLaunchKernelGGL(rto::k_mesh_count<RTO_MESH_MC>, dim3(nb), dim3(kBlock), 0, s, P, c->d_nodes, n, c->d_triOffset, (const uint8_t*)nullptr, d_cnt, d_off, d_mask);
     else
         hipLaunchKernelGGL(rto::k_mesh_count<RTO_MESH_CUBES>, dim3(nb), dim3(kBlock), 0, s, P, c->d_nodes, n, (const int*)nullptr, c->d_vox, d_cnt, d_off, d_mask);
     RTO_HIP(c, hipGetLastError());
-    RTO_HIP(c, hipEventRecord(ev[1], s));
+    RTO_HIP(c, events.record(1, s));
 
     // ---- depth-first ranks: the deepest level holds leaves only
     for (int l = levels - 2; l >= 0; l--) {
@@ -291,7 +288,7 @@ int rto_extract_mesh(rto_context* c, int kind, const rto_mesh_cull* cull, int64_
         hipLaunchKernelGGL(rto::k_mesh_offset_level, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c->d_nodes, first, count, d_cnt, d_off);
     }
     RTO_HIP(c, hipGetLastError());
-    RTO_HIP(c, hipEventRecord(ev[2], s));
+    RTO_HIP(c, events.record(2, s));
     unsigned total = 0;
     RTO_HIP(c, hipMemcpyAsync(&total, d_cnt, sizeof total, hipMemcpyDeviceToHost, s));     // the one read-back: it sizes the output
     RTO_HIP(c, hipStreamSynchronize(s));
@@ -307,7 +304,7 @@ int rto_extract_mesh(rto_context* c, int kind, const rto_mesh_cull* cull, int64_
         (void)hipFree(c->d_mesh); (void)hipFree(c->d_meshNode);
         c->d_mesh = d_new; c->d_meshNode = d_newNode; c->meshCap = (int64_t)cap;
     }
-    RTO_HIP(c, hipEventRecord(ev[3], s));
+    RTO_HIP(c, events.record(3, s));
     if (total > 0) {
         if (kind == RTO_MESH_MC)
             hipLaunchKernelGGL(rto::k_mesh_emit_mc, dim3((unsigned)((c->numTris + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
@@ -316,12 +313,12 @@ int rto_extract_mesh(rto_context* c, int kind, const rto_mesh_cull* cull, int64_
             hipLaunchKernelGGL(rto::k_mesh_emit_cubes, dim3(nb), dim3(kBlock), 0, s, P, c->d_nodes, n, d_mask, d_off, c->d_mesh, c->d_meshNode);
         RTO_HIP(c, hipGetLastError());
     }
-    RTO_HIP(c, hipEventRecord(ev[4], s));
+    RTO_HIP(c, events.record(4, s));
     RTO_HIP(c, hipStreamSynchronize(s));
     c->meshTris = (int64_t)total;
-    RTO_HIP(c, hipEventElapsedTime(&c->meshMs[0], ev[0], ev[1]));
-    RTO_HIP(c, hipEventElapsedTime(&c->meshMs[1], ev[1], ev[2]));
-    RTO_HIP(c, hipEventElapsedTime(&c->meshMs[2], ev[3], ev[4]));
+    RTO_HIP(c, events.elapsed(0, 1, &c->meshMs[0]));
+    RTO_HIP(c, events.elapsed(1, 2, &c->meshMs[1]));
+    RTO_HIP(c, events.elapsed(3, 4, &c->meshMs[2]));
     *num_tris = (int64_t)total;
     return RTO_OK;
 }

@@ -334,18 +334,13 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
             return fail(c, RTO_E_INVALID, tooBig ? "rto_voxelize_mesh: grid above the build's size limit"
                                                  : "rto_voxelize_mesh: empty grid (no face, or no row with finite coordinates)");
     }
-    int maxDim = std::max(g.dims[0], std::max(g.dims[1], g.dims[2]));
-    int R = 0;
-    while ((1 << R) < maxDim) R++;
     const size_t nvox = (size_t)g.dims[0] * g.dims[1] * g.dims[2];
 
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
-    hipEvent_t ev[4];
-    for (auto& e : ev) e = nullptr;
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ ev };
-    for (auto& e : ev) RTO_HIP(c, hipEventCreate(&e));
+    StreamEvents<4> events;
+    RTO_HIP(c, events.create());
     float ms[4] = { -1.f, -1.f, -1.f, -1.f };
     VoxOwned vox;
     RTO_HIP(c, hipMalloc(&vox.p, nvox));
@@ -374,12 +369,12 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
             RTO_HIP(c, hipMemcpyAsync(d_xyz, xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, s));
             RTO_HIP(c, hipMemcpyAsync(d_tris, tris, (size_t)nf * 3 * sizeof(int), hipMemcpyHostToDevice, s));
             RTO_HIP(c, hipMemsetAsync(d_invalid, 0, sizeof(int), s));
-            RTO_HIP(c, hipEventRecord(ev[0], s));
+            RTO_HIP(c, events.record(0, s));
             hipLaunchKernelGGL(rto::k_vox_setup, dim3((unsigned)nb), dim3(kBlock), 0, s, d_xyz, d_tris, nfi, g, d_faces, d_counts, d_sums, d_invalid);
             hipLaunchKernelGGL(rto::k_vox_scan_blocks, dim3(1), dim3(1024), 0, s, d_sums, nb, d_total);
             hipLaunchKernelGGL(rto::k_vox_scan_faces, dim3((unsigned)nb), dim3(kBlock), 0, s, d_counts, nfi, d_sums, d_total, d_off);
             RTO_HIP(c, hipGetLastError());
-            RTO_HIP(c, hipEventRecord(ev[1], s));
+            RTO_HIP(c, events.record(1, s));
             long long total = 0;
             int invalid = 0;
             RTO_HIP(c, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, s));
@@ -394,10 +389,10 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
                 hipLaunchKernelGGL(rto::k_vox_fill, dim3((unsigned)blocks), dim3(kBlock), 0, s, d_faces, d_off, nfi, total, g, vox.p);
             RTO_HIP(c, hipGetLastError());
         } else {
-            RTO_HIP(c, hipEventRecord(ev[0], s));
-            RTO_HIP(c, hipEventRecord(ev[1], s));
+            RTO_HIP(c, events.record(0, s));
+            RTO_HIP(c, events.record(1, s));
         }
-        RTO_HIP(c, hipEventRecord(ev[2], s));
+        RTO_HIP(c, events.record(2, s));
         int* d_box = nullptr;
         unsigned long long* d_filled = nullptr;
         RTO_HIP(c, scratch.alloc(&d_box, 6));
@@ -408,16 +403,16 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
         const unsigned bb = (unsigned)std::max<long long>(1, std::min<long long>((runs + kBlock - 1) / kBlock, (long long)c->numCUs * 8));
         hipLaunchKernelGGL(rto::k_vox_bbox, dim3(bb), dim3(kBlock), 0, s, vox.p, g.dims[0], g.dims[1], (long long)nvox, d_box, d_filled);
         RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, hipEventRecord(ev[3], s));
+        RTO_HIP(c, events.record(3, s));
         RTO_HIP(c, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, s));
         RTO_HIP(c, hipMemcpyAsync(&filled, d_filled, sizeof filled, hipMemcpyDeviceToHost, s));
         RTO_HIP(c, hipStreamSynchronize(s));
     }
     if (nf > 0) {
-        RTO_HIP(c, hipEventElapsedTime(&ms[0], ev[0], ev[1]));
-        RTO_HIP(c, hipEventElapsedTime(&ms[1], ev[1], ev[2]));
+        RTO_HIP(c, events.elapsed(0, 1, &ms[0]));
+        RTO_HIP(c, events.elapsed(1, 2, &ms[1]));
     }
-    RTO_HIP(c, hipEventElapsedTime(&ms[2], ev[2], ev[3]));
+    RTO_HIP(c, events.elapsed(2, 3, &ms[2]));
 
     // recentring (S/main.cpp:376-422): the centres are non-decreasing in the index, so the min / max centre is the centre of the
     // min / max FILLED index, in the reference's float arithmetic
@@ -431,20 +426,15 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
         }
     }
 
-    // ---- commit: what rto_build_octree(grid, gmin, vs) leaves
+    // ---- commit: adopt the new grid, then rebuild_from_resident_grid -- what rto_build_octree(grid, gmin, vs) leaves
     free_octree(c);
     std::memcpy(c->gridMin, gmin, sizeof c->gridMin);
     c->voxelSize = g.vs;
     c->d_vox = vox.p; vox.p = nullptr;
     c->voxDim[0] = g.dims[0]; c->voxDim[1] = g.dims[1]; c->voxDim[2] = g.dims[2];
     for (int i = 0; i < 4; i++) c->voxelizeMs[i] = ms[i];
-    const int rcBuild = build_octree_resident(c, nullptr, R);
+    const int rcBuild = rebuild_from_resident_grid(c, P.triangles != 0, &c->voxelizeMs[3], nullptr);
     if (rcBuild != RTO_OK) return rcBuild;
-    c->voxelizeMs[3] = c->buildMs;
-    if (P.triangles) {
-        const int rcTris = rto_build_leaf_triangles(c, nullptr, 0, 0, 0);
-        if (rcTris != RTO_OK) return rcTris;
-    }
     if (result) {
         std::memset(result, 0, sizeof *result);
         for (int a = 0; a < 3; a++) { result->dims[a] = g.dims[a]; result->grid_min[a] = gmin[a]; }

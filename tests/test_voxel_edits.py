@@ -224,11 +224,10 @@ def path(request, ctx, ctx2):
         c.debug_set_build_path(False)
 
 
-def _odd_grid(orc):
+def _odd_grid(orc, dims=(37, 53, 29), radii=(15.0, 22.0, 12.0)):
     rng = np.random.default_rng(5)
-    dims = (37, 53, 29)
     z, y, x = np.mgrid[0:dims[2], 0:dims[1], 0:dims[0]]
-    blob = ((x - 18) ** 2 / 15.0 ** 2 + (y - 26) ** 2 / 22.0 ** 2 + (z - 14) ** 2 / 12.0 ** 2) <= 1.0
+    blob = ((x - dims[0] // 2) ** 2 / radii[0] ** 2 + (y - dims[1] // 2) ** 2 / radii[1] ** 2 + (z - dims[2] // 2) ** 2 / radii[2] ** 2) <= 1.0
     data = (blob & (rng.random(blob.shape) < 0.97)).astype(np.uint8)
     vox = np.float32(1.0 / 64)
     gmin = (-0.5 * np.asarray(dims, np.float32) * vox).astype(np.float32)
@@ -369,6 +368,71 @@ def test_gpu_ten_edits_equal_one_fresh_build(ctx, ctx2, orc, scenes, camera):
     assert t1.tobytes() == t2.tobytes() and o1.tobytes() == o2.tobytes()
     view, pos = _view(orc, camera, "sphere256")
     _check_renders(ctx, orc, og, nodes, view, pos, "ten edits")
+
+
+def _changing_selection(ctx, cr, g, cur):
+    """(grid, edit_components arguments) that the CPU rule (tests/component_ref.py) says change at least one voxel: debris removal
+    where there is debris; otherwise a slab is carved first, as test_gpu_carved_sphere_falls_in_two_... does, so that the smaller
+    piece is there to drop."""
+    from ray_tracing_octrees_amd import hip
+    debris = (cr.SET_SOLID, cr.CONN_FACE, cr.SELECT_SMALLER_THAN, 50)
+    if cr.apply_selection(cur, *debris)[1] > 0:
+        return cur, debris
+    dims = np.asarray(g.dims, np.float64)
+    centre = _world(g.min, g.voxel_size, dims * (0.5, 0.5, 0.375))
+    half = (np.array([dims[0], dims[1], 1.0]) * float(g.voxel_size)).astype(np.float32)
+    assert ctx.edit_voxels(hip.make_brushes([centre], [half], er.BOX, er.CARVE)) > 0
+    cur = ctx.download_voxels()
+    pieces = (cr.SET_SOLID, cr.CONN_FACE, cr.SELECT_ALL_BUT_LARGEST, 0)
+    assert cr.apply_selection(cur, *pieces)[1] > 0
+    return cur, pieces
+
+
+@gpu
+@pytest.mark.parametrize("name", ["odd37x21", "odd37", "sphere32"])
+def test_gpu_three_edits_share_one_rebuild_and_one_count(ctx, ctx2, orc, scenes, name, path):
+    """rto_edit_voxels, rto_edit_components and rto_edit_morphology on one context, triangles resident: after each, `changed` is
+    the number of bytes of the grid that differ, the nodes, triangles and info are bit for bit those of a fresh build of the
+    downloaded grid with triangles, and the labels and the distance field made before the call are refused.  odd37x21 (37 x 21 x 29
+    = 22,533 voxels) and odd37: dimX % 16 != 0 and n % 16 != 0, the narrow kernel forms, a last block and a last wave that are
+    partly empty; sphere32: the wide forms."""
+    import component_ref as cr
+    from ray_tracing_octrees_amd import hip
+    g = {"odd37x21": lambda: _odd_grid(orc, (37, 21, 29), (15.0, 8.5, 12.0)), "odd37": lambda: _odd_grid(orc),
+         "sphere32": lambda: scenes("sphere32").grid}[name]()
+    assert (g.dims[0] % 16 == 0) == (name == "sphere32") and (int(np.prod(g.dims)) % 16 == 0) == (name == "sphere32")
+    ctx.set_kernel(hip.KERNEL_AUTO)
+    ctx.build_octree(g.data, g.min, g.voxel_size)
+    ctx.build_leaf_triangles(None)
+    cur = np.ascontiguousarray(g.data, np.uint8)
+    brushes = _seeded_brushes(np.random.default_rng(37), 6, g.min, g.voxel_size, g.dims)
+    for step in ("edit_voxels", "edit_components", "edit_morphology"):
+        what = f"{name} {path} {step}"
+        if step == "edit_components":
+            cur, selection = _changing_selection(ctx, cr, g, cur)
+        ctx.label_components(cr.SET_SOLID, cr.CONN_FACE)
+        ctx.distance_field(hip.SET_SOLID)
+        ctx.component_labels(), ctx.distance()                              # both resident now
+        if step == "edit_voxels":
+            changed = ctx.edit_voxels(brushes)
+        elif step == "edit_components":
+            changed = ctx.edit_components(*selection)
+        else:
+            changed = ctx.edit_morphology(hip.MORPH_DILATE, 1.5 * float(g.voxel_size))
+        after = ctx.download_voxels()
+        print(f"{what}: changed {changed}, bytes that differ {int((after != cur).sum())}")
+        assert changed == int((after != cur).sum()) > 0, what
+        ctx2.build_octree(after, g.min, g.voxel_size)
+        ctx2.build_leaf_triangles(None)
+        assert ctx.download_nodes().tobytes() == ctx2.download_nodes().tobytes(), f"{what}: nodes"
+        (t1, o1), (t2, o2) = ctx.download_leaf_triangles(), ctx2.download_leaf_triangles()
+        assert t1.tobytes() == t2.tobytes() and o1.tobytes() == o2.tobytes(), f"{what}: triangles"
+        assert _same_struct(ctx.info(), ctx2.info()), f"{what}: info"
+        for read in (ctx.component_labels, ctx.distance):
+            with pytest.raises(hip.RtoError) as e:
+                read()
+            assert e.value.code == hip.RTO_E_INVALID and "the grid has changed since" in str(e.value), what
+        cur = after
 
 
 @gpu
