@@ -936,6 +936,79 @@ int  rto_edit_morphology(rto_context* ctx, int op, float radius, int64_t* change
 /* Device time in ms of the last rto_edit_morphology: transforms and flips, octree rebuild, triangle rebuild (-1: not run). */
 int  rto_last_morphology_ms(const rto_context* ctx, float ms[3]);
 
+/* ---- geodesic distance fields, paths and flood edits ----------------------------
+ * How far every voxel of the resident grid is from a set of seed voxels along the way one can actually go: through free space
+ * round the walls, or inside the material.  Which voxels a spill, a crowd or a tool reaches within a number of steps, how thick
+ * the material is between two points measured inside it, by which route a target is reached.  No reference counterpart.  Every
+ * result is an integer that a Dijkstra search over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel (i, j, k) has linear index v = i + dimX (j + dimY k); the sets are rto_label_components': RTO_SET_SOLID the
+ *             voxels equal to 1, RTO_SET_EMPTY the voxels equal to 0.  Voxels outside the grid do not exist.
+ *   medium    the set the path stays in: RTO_SET_EMPTY free space, RTO_SET_SOLID through the material.
+ *   moves     RTO_CONN_FACE: the 6 face neighbours, weight 1 (the value is a number of steps).  RTO_CONN_FULL: the 26
+ *             neighbours, weight 3, 4, 5 for a move that changes 1, 2, 3 coordinates (the 3-4-5 chamfer: divide by 3 for voxel
+ *             units).  A move needs both ends in the medium and nothing else: a diagonal move between two medium voxels is
+ *             allowed whatever the voxels beside it hold, exactly as rto_label_components joins them, so the voxels in reach are
+ *             the components of the medium, under the same connectivity, that hold a seed.
+ *   seeds     n >= 1 linear indices, on the host.  A seed outside [0, voxels) is RTO_E_INVALID; a seed that is not in the
+ *             medium is ignored; duplicates are allowed.
+ *   field     g[v] = the smallest total weight of a path of moves from any seed to v, as int32: 0 on the seeds that lie in the
+ *             medium; RTO_DIST_NONE outside the medium, where no seed reaches, and beyond the limit.
+ *   limit     in the metric's own units; limit >= 0x7fffffff: none.  A voxel with g > limit holds RTO_DIST_NONE, so a limited
+ *             field is the unlimited one, thresholded.
+ *   summary   max_g the largest finite value, argmax the smallest linear index that holds it, reached the number of finite
+ *             values; max_g = argmax = -1 when reached is 0.
+ *   paths     on the resident field, under the connectivity it was made with.  From a target t with finite g[t] the path is
+ *             t = p0, p1, ..., pm with g[pm] = 0, where p(k+1) is the smallest linear index among the neighbours u of pk with
+ *             g[u] finite and g[u] + w(u, pk) == g[pk] (one always exists, in a limited field too); len = m + 1.  A target whose
+ *             g is RTO_DIST_NONE has len = -1.  Row i of out_voxels (max_len entries) takes the first min(len, max_len) voxels
+ *             of target i's path, -1 behind them; out_len[i] is always the full len, so max_len = 0 with out_voxels = NULL asks
+ *             for lengths alone.
+ *   flood     rto_edit_geodesic makes its own field (the resident one is not consulted) and flips every voxel with finite g:
+ *             medium EMPTY becomes FILLED, medium SOLID becomes EMPTY.  *changed (may be NULL) = voxels flipped.  When it is > 0
+ *             the context is left exactly as rto_edit_voxels leaves it after a change (one rebuild on the build path in force,
+ *             resident leaf triangles rebuilt, frustum culling off, labels and both fields freed); changed == 0 (no seed in the
+ *             medium, for example) touches nothing.  With no limit and one seed it is
+ *             rto_edit_components(medium, connectivity, RTO_SELECT_CONTAINING, seed).
+ * rto_geodesic_field keeps the volume (int32 per voxel) resident, beside the Euclidean field of rto_distance_field (both may be
+ * resident); it describes the grid it was made from, and every call that changes or replaces the grid frees it, as it frees the
+ * labels and the Euclidean field: the readers and rto_geodesic_paths then return RTO_E_INVALID.  Synchronous on the context's
+ * stream.
+ * Errors, each leaving the context untouched: RTO_E_INVALID (unknown medium or connectivity; n < 1; NULL seeds or targets; a seed
+ * or target out of range; limit < 0; max_len < 0; too small a capacity; no resident geodesic field, for the readers and for
+ * paths); RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the octree came from rto_upload_octree: no resident grid; more
+ * than 2^31 - 2 voxels; w_max (voxels - 1) >= 2^31 - 1 with w_max 1 or 5: the field is 32-bit); RTO_E_INTERNAL (the relaxation
+ * did not settle within voxels + 2 passes: a shortest path crosses tile boundaries fewer times than it has voxels). */
+typedef struct rto_geo_summary {    /* 32 bytes */
+    int64_t max_g;                  /* the largest finite value; -1: none */
+    int64_t argmax;                 /* the smallest linear voxel index that holds it; -1: none */
+    int64_t reached;                /* voxels with a finite value */
+    int64_t reserved;               /* 0 */
+} rto_geo_summary;
+
+int  rto_geodesic_field(rto_context* ctx, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit,
+                        rto_geo_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_geodesic(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed). */
+int  rto_geodesic_device(rto_context* ctx, int32_t** d_g);
+/* out_voxels: n rows of max_len int64 (may be NULL when max_len is 0); out_len: n int64.  Both on the host. */
+int  rto_geodesic_paths(rto_context* ctx, const int64_t* targets, int64_t n, int64_t max_len, int64_t* out_voxels, int64_t* out_len);
+int  rto_edit_geodesic(rto_context* ctx, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit,
+                       int64_t* changed /* may be NULL */);
+/* Device time in ms of the last rto_geodesic_field: init, relaxation (all passes, with the host's looks at the device), summary
+ * (-1: not run). */
+int  rto_last_geodesic_ms(const rto_context* ctx, float ms[3]);
+/* Device time in ms of the last rto_edit_geodesic: field and flip, octree rebuild, triangle rebuild (-1: not run). */
+int  rto_last_geodesic_edit_ms(const rto_context* ctx, float ms[3]);
+/* The last rto_geodesic_field: relaxation launches up to and including the first that found no tile to run (at least 2: the tiles
+ * that hold a seed always run once), and the tiles run summed over them (may be NULL). */
+int  rto_debug_geodesic_passes(const rto_context* ctx, int64_t* passes, int64_t* tiles_run);
+/* How many relaxation launches go out between two looks of the host at the device (1 .. 64, 8 by default).  A tuning choice: no
+ * value of any field, path or edit depends on it. */
+int  rto_debug_set_geodesic_look(rto_context* ctx, int passes_per_look);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -180,6 +180,15 @@ struct rto_context {
     int* d_dist = nullptr;                    // nullptr: no field resident
     float distMs[4] = { -1.f, -1.f, -1.f, -1.f };
     float morphMs[3] = { -1.f, -1.f, -1.f };  // the last rto_edit_morphology: transforms and flips, octree rebuild, triangle rebuild
+
+    // geodesic fields (rto_geodesic.inc): the last field of the resident grid, with the medium and connectivity it was made for
+    // (rto_geodesic_paths walks it under them); dropped whenever the grid changes
+    int* d_geo = nullptr;                     // nullptr: no field resident
+    int geoMedium = 0, geoConn = 0;
+    int64_t geoPasses = 0, geoTilesRun = 0;
+    int geoLook = 8;                          // relaxation launches per look at the device (rto_debug_set_geodesic_look): changes no value
+    float geoMs[3] = { -1.f, -1.f, -1.f };    // the last rto_geodesic_field: init, relaxation, summary
+    float geoEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_geodesic: field and flip, octree rebuild, triangle rebuild
 };
 
 static thread_local std::string g_createError;
@@ -239,10 +248,14 @@ static void free_components(rto_context* c) {
 // The resident distance field (rto_distance.inc): it describes one state of the grid.
 static void free_distance(rto_context* c) { (void)hipFree(c->d_dist); c->d_dist = nullptr; }
 
+// The resident geodesic field (rto_geodesic.inc): it describes one state of the grid.
+static void free_geodesic(rto_context* c) { (void)hipFree(c->d_geo); c->d_geo = nullptr; }
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
     free_distance(c);
+    free_geodesic(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -2832,3 +2845,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_region.inc"
 #include "rto_components.inc"
 #include "rto_distance.inc"
+#include "rto_geodesic.inc"

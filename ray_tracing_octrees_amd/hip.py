@@ -50,6 +50,8 @@ SYMBOLS = (
     "rto_debug_components_passes", "rto_edit_components",
     "rto_distance_field", "rto_download_distance", "rto_distance_device", "rto_last_distance_ms", "rto_edit_morphology",
     "rto_last_morphology_ms",
+    "rto_geodesic_field", "rto_download_geodesic", "rto_geodesic_device", "rto_geodesic_paths", "rto_edit_geodesic",
+    "rto_last_geodesic_ms", "rto_last_geodesic_edit_ms", "rto_debug_geodesic_passes", "rto_debug_set_geodesic_look",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -88,6 +90,9 @@ COMPONENT_DTYPE = np.dtype([("root", "<i8"), ("voxels", "<i8"), ("lo", "<i4", (3
 DIST_NONE = 0x7fffffff
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 DIST_SUMMARY_DTYPE = np.dtype([("max_d2", "<i8"), ("argmax", "<i8"), ("finite", "<i8"), ("reserved", "<i8")])
+# struct rto_geo_summary, 32 bytes: geodesic fields (rto_geodesic_field)
+GEO_SUMMARY_DTYPE = np.dtype([("max_g", "<i8"), ("argmax", "<i8"), ("reached", "<i8"), ("reserved", "<i8")])
+GEO_NO_LIMIT = 0x7fffffff
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -433,6 +438,15 @@ def load():
     L.rto_last_distance_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_edit_morphology.argtypes = [vp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
     L.rto_last_morphology_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_geodesic_field.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp]
+    L.rto_download_geodesic.argtypes = [vp, vp, C.c_int64]
+    L.rto_geodesic_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_geodesic_paths.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
+    L.rto_edit_geodesic.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_last_geodesic_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_last_geodesic_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_geodesic_passes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rto_debug_set_geodesic_look.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -1036,6 +1050,87 @@ class Context:
         ms = (C.c_float * 3)()
         self._check(self._L.rto_last_morphology_ms(self._h, ms))
         return tuple(ms)
+
+    # -- geodesic fields, paths and flood edits ---------------------------------------
+    def _voxel_indices(self, voxels) -> np.ndarray:
+        """Linear indices as contiguous int64: `voxels` is a sequence of them, or an (n, 3) array of (i, j, k) in the resident
+        grid's dims."""
+        a = np.asarray(voxels)
+        if a.ndim == 2 and a.shape[1] == 3:
+            dims = (C.c_int * 3)()
+            self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+            a = a.astype(np.int64)
+            a = a[:, 0] + dims[0] * (a[:, 1] + dims[1] * a[:, 2])
+        return np.ascontiguousarray(a.reshape(-1), np.int64)
+
+    def geodesic_field(self, seeds, medium: int = SET_EMPTY, connectivity: int = CONN_FACE, limit=None):
+        """rto_geodesic_field: (the int32 (dimZ, dimY, dimX) volume of shortest-path lengths inside `medium` from `seeds` (linear
+        indices, or an (n, 3) array of (i, j, k)): steps under CONN_FACE, 3 / 4 / 5 per move under CONN_FULL; DIST_NONE outside the
+        medium, out of reach or above `limit` (None: no limit); the summary as a GEO_SUMMARY_DTYPE scalar).  The field stays
+        resident until the grid changes."""
+        s = self._voxel_indices(seeds)
+        summary = np.zeros((), GEO_SUMMARY_DTYPE)
+        self._check(self._L.rto_geodesic_field(self._h, int(medium), int(connectivity), s.ctypes.data, s.size,
+                                               GEO_NO_LIMIT if limit is None else int(limit), summary.ctypes.data))
+        return self.geodesic(), summary
+
+    def geodesic(self) -> np.ndarray:
+        """The resident geodesic field (rto_download_geodesic)."""
+        self._check(self._L.rto_geodesic_device(self._h, None))             # no field resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_geodesic(self._h, out.ctypes.data, out.size))
+        return out
+
+    def geodesic_device(self) -> int:
+        """The device pointer of the resident int32 geodesic field."""
+        p = C.c_void_p()
+        self._check(self._L.rto_geodesic_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def geodesic_paths(self, targets, max_len: int):
+        """rto_geodesic_paths on the resident field: (rows, lengths) -- rows (n, max_len) int64, each the first voxels of the path
+        from its target down to a seed and -1 behind them; lengths (n,) int64, the full length of each path, -1 for a target the
+        field does not reach."""
+        t = self._voxel_indices(targets)
+        rows = np.empty((t.size, int(max_len)), np.int64) if int(max_len) >= 0 else np.empty((t.size, 0), np.int64)
+        lengths = np.empty(t.size, np.int64)
+        self._check(self._L.rto_geodesic_paths(self._h, t.ctypes.data, t.size, int(max_len), rows.ctypes.data if rows.size else None,
+                                               lengths.ctypes.data))
+        return rows, lengths
+
+    def edit_geodesic(self, seeds, medium: int = SET_EMPTY, connectivity: int = CONN_FACE, limit=None) -> int:
+        """rto_edit_geodesic: flips every voxel of `medium` within `limit` of the seeds along paths inside the medium, rebuilt as
+        edit_voxels does; the number of voxels flipped."""
+        s = self._voxel_indices(seeds)
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_geodesic(self._h, int(medium), int(connectivity), s.ctypes.data, s.size,
+                                              GEO_NO_LIMIT if limit is None else int(limit), C.byref(changed)))
+        return changed.value
+
+    def last_geodesic_ms(self):
+        """Device ms of the last geodesic_field: (init, relaxation, summary); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_geodesic_ms(self._h, ms))
+        return tuple(ms)
+
+    def last_geodesic_edit_ms(self):
+        """Device ms of the last edit_geodesic: (field and flip, octree rebuild, triangle rebuild); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_geodesic_edit_ms(self._h, ms))
+        return tuple(ms)
+
+    def geodesic_passes(self, tiles: bool = False):
+        """Relaxation launches of the last geodesic_field, the closing one that found no tile included; with tiles=True the pair
+        (launches, tiles run summed over them)."""
+        p, t = C.c_int64(), C.c_int64()
+        self._check(self._L.rto_debug_geodesic_passes(self._h, C.byref(p), C.byref(t)))
+        return (p.value, t.value) if tiles else p.value
+
+    def debug_set_geodesic_look(self, passes_per_look: int) -> None:
+        """How many relaxation launches go out between two looks at the device (1 .. 64): changes no value."""
+        self._check(self._L.rto_debug_set_geodesic_look(self._h, int(passes_per_look)))
 
     # -- region queries --------------------------------------------------------
     def query_points(self, points) -> np.ndarray:

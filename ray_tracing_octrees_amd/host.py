@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   RtoError, _f)
 
 _lib = None
@@ -168,6 +168,20 @@ def load():
     L.rtoh_rt_morphology.restype = C.c_int64
     L.rtoh_rt_thickest_point.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.rtoh_rt_thickest_point.restype = C.c_int
+    L.rtoh_geodesic_cpu.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp]
+    L.rtoh_geodesic_cpu.restype = C.c_int
+    L.rtoh_geodesic_paths_cpu.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp]
+    L.rtoh_geodesic_paths_cpu.restype = C.c_int
+    L.rtoh_geodesic_flood_cpu.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64]
+    L.rtoh_geodesic_flood_cpu.restype = C.c_int64
+    L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
+    L.rtoh_rt_geodesic_field.restype = C.c_int
+    L.rtoh_rt_paths_to.argtypes = [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]
+    L.rtoh_rt_paths_to.restype = C.c_int
+    L.rtoh_rt_flood_from.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]
+    L.rtoh_rt_flood_from.restype = C.c_int64
+    L.rtoh_rt_farthest_point.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    L.rtoh_rt_farthest_point.restype = C.c_int
     L.rtoh_rt_edit_voxels.argtypes = [_vp, _vp, _vp, _vp, C.c_int]
     L.rtoh_rt_edit_voxels.restype = C.c_int64
     L.rtoh_rt_grid.argtypes = [_vp, C.POINTER(C.c_int), _vp]
@@ -274,6 +288,33 @@ class VoxelGrid:
         """Addition: applyMorphologyCPU -- rto_edit_morphology's DILATE / ERODE / OPEN / CLOSE on this grid for rq quanta, on the
         CPU; the number of voxels changed (-1: refused, the grid untouched)."""
         return int(load().rtoh_morphology_cpu(self._h, int(op), int(rq)))
+
+    def geodesicField(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff):
+        """Addition: geodesicFieldCPU (host/Geodesic.h) -- the rule of rto_geodesic_field on the CPU (a bucket queue): (code, g int32
+        (dimZ, dimY, dimX) or None when refused, summary as a hip.GEO_SUMMARY_DTYPE scalar)."""
+        dx, dy, dz = self.dims
+        s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
+        g = np.empty((dz, dy, dx), np.int32)
+        summary = np.zeros((), GEO_SUMMARY_DTYPE)
+        rc = int(load().rtoh_geodesic_cpu(self._h, int(medium), int(connectivity), s.ctypes.data if s.size else None, s.size, int(limit),
+                                          g.ctypes.data, summary.ctypes.data))
+        return rc, (g if rc == 0 else None), summary
+
+    def geodesicPaths(self, g, targets, maxLen: int, connectivity: int = 6):
+        """Addition: geodesicPathsCPU -- rto_geodesic_paths on a field `g` of this grid: (code, rows (n, maxLen) int64, lengths)."""
+        f = np.ascontiguousarray(g, np.int32)
+        t = np.ascontiguousarray(np.asarray(targets).reshape(-1), np.int64)
+        rows = np.empty((t.size, max(int(maxLen), 0)), np.int64)
+        lengths = np.empty(t.size, np.int64)
+        rc = int(load().rtoh_geodesic_paths_cpu(self._h, int(connectivity), f.ctypes.data, t.ctypes.data if t.size else None, t.size,
+                                                int(maxLen), rows.ctypes.data if rows.size else None, lengths.ctypes.data))
+        return rc, rows, lengths
+
+    def floodGeodesic(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff) -> int:
+        """Addition: floodGeodesicCPU -- rto_edit_geodesic on this grid, on the CPU; the number of voxels flipped, or the refusal's
+        code (negative, the grid untouched)."""
+        s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
+        return int(load().rtoh_geodesic_flood_cpu(self._h, int(medium), int(connectivity), s.ctypes.data if s.size else None, s.size, int(limit)))
 
 
 def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
@@ -668,6 +709,44 @@ class RayTracerBVH:
         if rc != 0 or not out[0]:
             return rc, None
         return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), float(dist.value))
+
+    def geodesicField(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff):
+        """Addition: RayTracerBVH::geodesicField -- (code, g int32 (dimZ, dimY, dimX), summary as a hip.GEO_SUMMARY_DTYPE scalar);
+        code is RTO_OK or the refusal's (lastError), and g is then None."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
+        g = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        summary = np.zeros((), GEO_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_geodesic_field(self._h, s.ctypes.data if s.size else None, s.size, int(medium), int(connectivity), int(limit),
+                                               g.ctypes.data, g.size, summary.ctypes.data))
+        return rc, (g if rc == 0 else None), summary
+
+    def pathsTo(self, targets, maxLen: int):
+        """Addition: RayTracerBVH::pathsTo -- the routes of the last geodesicField: (code, rows (n, maxLen) int64 with -1 behind each
+        path, lengths (n,) int64 with -1 for a target not reached)."""
+        t = np.ascontiguousarray(np.asarray(targets).reshape(-1), np.int64)
+        rows = np.empty((t.size, max(int(maxLen), 0)), np.int64)
+        lengths = np.empty(t.size, np.int64)
+        rc = int(load().rtoh_rt_paths_to(self._h, t.ctypes.data if t.size else None, t.size, int(maxLen), rows.ctypes.data if rows.size else None,
+                                         lengths.ctypes.data))
+        return rc, rows, lengths
+
+    def floodFrom(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff) -> int:
+        """Addition: RayTracerBVH::floodFrom -- flips every voxel of `medium` within `limit` of the seeds along paths inside the
+        medium; voxels flipped, or the refusal's code (negative)."""
+        s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
+        return int(load().rtoh_rt_flood_from(self._h, s.ctypes.data if s.size else None, s.size, int(medium), int(connectivity), int(limit)))
+
+    def farthestPoint(self, seeds, medium: int = 0, connectivity: int = 6):
+        """Addition: RayTracerBVH::farthestPoint -- (code, None or ((i, j, k), voxel, g, reached)) of the reached voxel farthest
+        from the seeds along paths inside the medium."""
+        s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
+        out = (C.c_int64 * 7)()
+        rc = int(load().rtoh_rt_farthest_point(self._h, s.ctypes.data if s.size else None, s.size, int(medium), int(connectivity), out))
+        if rc != 0 or not out[0]:
+            return rc, None
+        return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), int(out[5]), int(out[6]))
 
     def locate(self, points):
         """Addition: RayTracerBVH::locate -- the leaf that holds each of the (n, 3) points: (code, hip.POINT_HIT_DTYPE records).

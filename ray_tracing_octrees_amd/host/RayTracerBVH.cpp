@@ -62,6 +62,10 @@ struct HipApi {
     decltype(&rto_distance_field) distance_field = nullptr;
     decltype(&rto_download_distance) download_distance = nullptr;
     decltype(&rto_edit_morphology) edit_morphology = nullptr;
+    decltype(&rto_geodesic_field) geodesic_field = nullptr;
+    decltype(&rto_download_geodesic) download_geodesic = nullptr;
+    decltype(&rto_geodesic_paths) geodesic_paths = nullptr;
+    decltype(&rto_edit_geodesic) edit_geodesic = nullptr;
     std::string error;
 
     bool load() {
@@ -134,6 +138,10 @@ struct HipApi {
         distance_field = reinterpret_cast<decltype(distance_field)>(sym("rto_distance_field"));
         download_distance = reinterpret_cast<decltype(download_distance)>(sym("rto_download_distance"));
         edit_morphology = reinterpret_cast<decltype(edit_morphology)>(sym("rto_edit_morphology"));
+        geodesic_field = reinterpret_cast<decltype(geodesic_field)>(sym("rto_geodesic_field"));
+        download_geodesic = reinterpret_cast<decltype(download_geodesic)>(sym("rto_download_geodesic"));
+        geodesic_paths = reinterpret_cast<decltype(geodesic_paths)>(sym("rto_geodesic_paths"));
+        edit_geodesic = reinterpret_cast<decltype(edit_geodesic)>(sym("rto_edit_geodesic"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -918,6 +926,81 @@ int RayTracerBVH::thickestPoint(ThickestPoint& out) {
     out.i = (int)(s.argmax % m_grid.dimX); out.j = (int)((s.argmax / m_grid.dimX) % m_grid.dimY); out.k = (int)(s.argmax / ((int64_t)m_grid.dimX * m_grid.dimY));
     out.d2 = s.max_d2;
     out.distance = std::sqrt((double)s.max_d2) * (double)m_grid.voxelSize;
+    return RTO_OK;
+}
+
+// The geodesic field of the first GPU's resident grid (rto_geodesic_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::geodesicField(const std::vector<int64_t>& seeds, int medium, int connectivity, int64_t limit, std::vector<int32_t>* g,
+                                rto_geo_summary* summary) {
+    if (g) g->clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "geodesicField: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("geodesic field")) return RTO_E_HIP;
+    int rc = api().geodesic_field(m_ctx, medium, connectivity, seeds.data(), (int64_t)seeds.size(), limit, summary);
+    if (rc == RTO_OK && g) {
+        g->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+        rc = api().download_geodesic(m_ctx, g->data(), (int64_t)g->size());
+        if (rc != RTO_OK) g->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "geodesicField");
+    return RTO_OK;
+}
+
+// The paths of the last geodesicField to `targets` (rto_geodesic_paths): rows of maxLen voxels, -1 behind each path; the full lengths.
+int RayTracerBVH::pathsTo(const std::vector<int64_t>& targets, int64_t maxLen, std::vector<int64_t>& voxels, std::vector<int64_t>& lengths) {
+    voxels.clear();
+    lengths.clear();
+    if (maxLen < 0 || targets.empty()) { m_lastError = "pathsTo: no targets, or a negative maxLen"; return RTO_E_INVALID; }
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "pathsTo: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    voxels.assign(targets.size() * (size_t)maxLen, -1);
+    lengths.assign(targets.size(), -1);
+    const int rc = api().geodesic_paths(m_ctx, targets.data(), (int64_t)targets.size(), maxLen, maxLen > 0 ? voxels.data() : nullptr, lengths.data());
+    if (rc != RTO_OK) { voxels.clear(); lengths.clear(); regionFailed(rc, "pathsTo"); }
+    return rc;
+}
+
+// rto_edit_geodesic on every GPU: the number of voxels flipped, or the refusal's code (negative).
+int64_t RayTracerBVH::floodFrom(const std::vector<int64_t>& seeds, int medium, int connectivity, int64_t limit) {
+    m_lastEditChanged = -1;
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "floodFrom: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("flood")) return RTO_E_HIP;
+    int64_t changed = 0;
+    for (rto_context* c : m_ctxs) {
+        const int rc = api().edit_geodesic(c, medium, connectivity, seeds.data(), (int64_t)seeds.size(), limit, c == m_ctx ? &changed : nullptr);
+        if (rc != RTO_OK) {
+            m_lastError = api().last_error(c);
+            std::cerr << "[RayTracerBVH] flood failed: " << m_lastError << std::endl;
+            return rc;
+        }
+    }
+    m_lastEditChanged = changed;
+    if (changed > 0) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+        m_gridStale = true;
+    }
+    return changed;
+}
+
+int RayTracerBVH::farthestPoint(const std::vector<int64_t>& seeds, int medium, int connectivity, FarthestPoint& out) {
+    out = FarthestPoint();
+    rto_geo_summary s;
+    const int rc = geodesicField(seeds, medium, connectivity, 0x7fffffffll, nullptr, &s);
+    if (rc != RTO_OK) return rc;
+    if (s.reached == 0) return RTO_OK;                                  // no seed lies in the medium
+    out.found = true;
+    out.i = (int)(s.argmax % m_grid.dimX); out.j = (int)((s.argmax / m_grid.dimX) % m_grid.dimY); out.k = (int)(s.argmax / ((int64_t)m_grid.dimX * m_grid.dimY));
+    out.voxel = s.argmax;
+    out.g = s.max_g;
+    out.reached = s.reached;
     return RTO_OK;
 }
 

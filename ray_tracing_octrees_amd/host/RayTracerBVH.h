@@ -225,6 +225,21 @@ public:
     int64_t open(float radius);
     int64_t close(float radius);
     int thickestPoint(ThickestPoint& out);
+    // Geodesic fields, paths and flood edits of the resident grid (rto_geodesic_field / rto_geodesic_paths / rto_edit_geodesic;
+    // DESIGN.md section 20).  geodesicField makes the field of the first GPU's grid: one int32 per voxel, x fastest, the length of
+    // the shortest path inside `medium` from any of `seeds` (linear voxel indices), weight 1 per face move under RTO_CONN_FACE and
+    // 3 / 4 / 5 per move under RTO_CONN_FULL, RTO_DIST_NONE outside the medium, out of reach or above `limit` (>= 0x7fffffff: none);
+    // g and summary may be null.  pathsTo reads the routes back out of that field: maxLen voxels per target from the target down to a
+    // seed, -1 behind the path, and every path's full length (-1: not reached).  floodFrom flips every voxel its own field reaches,
+    // on every GPU, and rebuilds as editVoxels does: the number flipped (lastEditChanged() too).  farthestPoint is the reached voxel
+    // farthest from the seeds (the smallest index among equals).  Each returns RTO_OK or the refusal's code, which is negative.
+    // The CPU form of the same rule for a VoxelGrid is host/Geodesic.h.
+    struct FarthestPoint { bool found = false; int i = 0, j = 0, k = 0; int64_t voxel = -1, g = -1, reached = 0; };
+    int geodesicField(const std::vector<int64_t>& seeds, int medium, int connectivity, int64_t limit, std::vector<int32_t>* g,
+                      rto_geo_summary* summary = nullptr);
+    int pathsTo(const std::vector<int64_t>& targets, int64_t maxLen, std::vector<int64_t>& voxels, std::vector<int64_t>& lengths);
+    int64_t floodFrom(const std::vector<int64_t>& seeds, int medium, int connectivity = RTO_CONN_FACE, int64_t limit = 0x7fffffffll);
+    int farthestPoint(const std::vector<int64_t>& seeds, int medium, int connectivity, FarthestPoint& out);
     // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
     // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
     // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same

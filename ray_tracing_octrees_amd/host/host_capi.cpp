@@ -12,6 +12,7 @@
 #include "CacheUtils.h"
 #include "Components.h"
 #include "Distance.h"
+#include "Geodesic.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -374,6 +375,52 @@ int rtoh_rt_thickest_point(RayTracerBVH* rt, int64_t out[5], double* distance) {
     const int rc = rt->thickestPoint(t);
     out[0] = t.found ? 1 : 0; out[1] = t.i; out[2] = t.j; out[3] = t.k; out[4] = t.d2;
     *distance = t.distance;
+    return rc;
+}
+// Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
+// NULL; the code of rto_geodesic_field.  rtoh_geodesic_paths_cpu walks a field of that grid; rtoh_geodesic_flood_cpu edits the grid
+// in place (the number flipped, or the refusal's code).
+int rtoh_geodesic_cpu(const VoxelGrid* g, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit, int32_t* out,
+                      rto_geo_summary* summary) {
+    std::vector<int32_t> f;
+    const int rc = geodesicFieldCPU(*g, medium, connectivity, seeds, n, limit, f, summary);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(f.begin(), f.end(), out);
+    return RTO_OK;
+}
+int rtoh_geodesic_paths_cpu(const VoxelGrid* g, int connectivity, const int32_t* field, const int64_t* targets, int64_t n, int64_t maxLen,
+                            int64_t* outVoxels, int64_t* outLen) {
+    if (!field) return RTO_E_INVALID;
+    const std::vector<int32_t> f(field, field + (size_t)g->dimX * g->dimY * g->dimZ);
+    return geodesicPathsCPU(*g, connectivity, f, targets, n, maxLen, outVoxels, outLen);
+}
+int64_t rtoh_geodesic_flood_cpu(VoxelGrid* g, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit) {
+    return floodGeodesicCPU(*g, medium, connectivity, seeds, n, limit);
+}
+// RayTracerBVH::geodesicField / pathsTo / floodFrom / farthestPoint: the class's codes; out = found, i, j, k, voxel, g, reached.
+int rtoh_rt_geodesic_field(RayTracerBVH* rt, const int64_t* seeds, int64_t n, int medium, int connectivity, int64_t limit, int32_t* g,
+                           int64_t capacity, rto_geo_summary* summary) {
+    std::vector<int32_t> f;
+    const int rc = rt->geodesicField(std::vector<int64_t>(seeds, seeds + (n > 0 ? n : 0)), medium, connectivity, limit, g ? &f : nullptr, summary);
+    if (rc != RTO_OK) return rc;
+    if (g) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), g);
+    return RTO_OK;
+}
+int rtoh_rt_paths_to(RayTracerBVH* rt, const int64_t* targets, int64_t n, int64_t maxLen, int64_t* outVoxels, int64_t* outLen) {
+    std::vector<int64_t> voxels, lengths;
+    const int rc = rt->pathsTo(std::vector<int64_t>(targets, targets + (n > 0 ? n : 0)), maxLen, voxels, lengths);
+    if (rc != RTO_OK) return rc;
+    if (outVoxels) std::copy(voxels.begin(), voxels.end(), outVoxels);
+    std::copy(lengths.begin(), lengths.end(), outLen);
+    return RTO_OK;
+}
+int64_t rtoh_rt_flood_from(RayTracerBVH* rt, const int64_t* seeds, int64_t n, int medium, int connectivity, int64_t limit) {
+    return rt->floodFrom(std::vector<int64_t>(seeds, seeds + (n > 0 ? n : 0)), medium, connectivity, limit);
+}
+int rtoh_rt_farthest_point(RayTracerBVH* rt, const int64_t* seeds, int64_t n, int medium, int connectivity, int64_t out[7]) {
+    RayTracerBVH::FarthestPoint t;
+    const int rc = rt->farthestPoint(std::vector<int64_t>(seeds, seeds + (n > 0 ? n : 0)), medium, connectivity, t);
+    out[0] = t.found ? 1 : 0; out[1] = t.i; out[2] = t.j; out[3] = t.k; out[4] = t.voxel; out[5] = t.g; out[6] = t.reached;
     return rc;
 }
 // RayTracerBVH::locate / census / nearestSolid: the C ABI's records back out; each returns the class's code (RTO_OK or the refusal's)
