@@ -1009,6 +1009,63 @@ int  rto_debug_geodesic_passes(const rto_context* ctx, int64_t* passes, int64_t*
  * value of any field, path or edit depends on it. */
 int  rto_debug_set_geodesic_look(rto_context* ctx, int passes_per_look);
 
+/* ---- local thickness fields ---------------------------------------------------
+ * How thick the material, or how wide the free space, is at every voxel of the resident grid: the largest ball that fits inside
+ * the medium and contains the voxel (Hildebrand and Ruegsegger's local thickness), for balls up to a caller's radius of at most 8
+ * voxels.  Which walls of a voxelized mesh are thinner than three voxels, where the narrowest gap between two buildings is, what the
+ * pore-size distribution of the free space is.  rto_distance_field does not say: a voxel beside the surface of a thick part has
+ * d2 = 1 exactly like a voxel of a one-voxel wall.  No reference counterpart.  Every result is an integer that a brute-force loop
+ * over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel (i, j, k) has linear index v = i + dimX (j + dimY k); the sets are rto_label_components': RTO_SET_SOLID the
+ *             voxels equal to 1, RTO_SET_EMPTY the voxels equal to 0.  Voxels outside the grid do not exist.
+ *   medium    RTO_SET_SOLID measures the material (wall thickness), RTO_SET_EMPTY the free space (pore width, clearance).
+ *   cap       mq = floor(max_radius / voxelSize * 64 + 0.5) as rto_distance_field quantises max_dist; c = floor(mq^2 / 4096).
+ *             c = 0 is RTO_E_INVALID (a radius under one voxel measures nothing); c > 64, +inf included, is RTO_E_UNSUPPORTED
+ *             (more than 8 voxels).  The cap is part of the rule, not an approximation of another rule.
+ *   radius    for a voxel q of the medium D[q] = min(d2 from q to the nearest voxel of the other set, c), d2 by
+ *             rto_distance_field's rule with set = the complement of the medium; RTO_DIST_NONE (the other set is empty) clips
+ *             to c.  D = 0 for a voxel outside the medium.
+ *   field     for a voxel p of the medium t2[p] = max{ D[q] : q in the grid, (p - q)^2 < D[q] }, as int32; 0 for every other
+ *             voxel.  The ball is open and q = p always qualifies, so a medium voxel holds at least 1 and at least its own D.
+ *             A value below c is an exact width: a wall w voxels wide holds min(((w + 1) div 2)^2, c) throughout.  The value c
+ *             reads "a ball of squared radius c fits here, or something larger".  The capped field is NOT min(uncapped field, c):
+ *             a voxel covered only by a far larger ball whose centre is more than sqrt(c) away can come out lower (never higher).
+ *   histogram bins[t], t = 0 .. c, int64: the number of medium voxels with t2 = t; bins[0] = 0; the sum is the number of medium
+ *             voxels.  Made by every call and kept on the host in the context.
+ *   summary   min_t2 the smallest value over the medium, argmin the smallest linear index that holds it, thin the number of
+ *             medium voxels with t2 < c, medium the number of medium voxels; -1, -1, 0, 0 with no medium voxel.
+ * rto_thickness_field keeps the volume (int32 per voxel) resident beside the labels, the Euclidean field and the geodesic field,
+ * with its medium and its c; every call that changes or replaces the grid frees it as it frees them, and the readers then return
+ * RTO_E_INVALID.  The call makes a private capped transform and frees it: a resident Euclidean field is neither read nor
+ * replaced.  Synchronous on the context's stream.
+ * Errors, in rto_distance_field's order, each leaving the context untouched: RTO_E_INVALID (unknown medium; max_radius NaN,
+ * negative, beyond 2^28 quanta, or under one voxel; too small a capacity; no resident thickness field, for the readers);
+ * RTO_E_UNSUPPORTED (max_radius above 8 voxels; no resident grid; a grid rto_distance_field refuses); RTO_E_NO_OCTREE. */
+#define RTO_THICK_MAX_C 64          /* the largest c: balls of up to 8 voxels */
+typedef struct rto_thick_summary {  /* 32 bytes */
+    int64_t min_t2;                 /* the smallest value over the medium; -1: no medium voxel */
+    int64_t argmin;                 /* the smallest linear voxel index that holds it; -1: none */
+    int64_t thin;                   /* medium voxels with t2 < c */
+    int64_t medium;                 /* medium voxels */
+} rto_thick_summary;
+
+int  rto_thickness_field(rto_context* ctx, int medium, float max_radius, rto_thick_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_thickness(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed). */
+int  rto_thickness_device(rto_context* ctx, int32_t** d_t2);
+/* The resident field's histogram: out takes c + 1 values (capacity >= c + 1; NULL: ask for *bins alone), *bins = c + 1 (may be
+ * NULL).  Both on the host. */
+int  rto_thickness_histogram(rto_context* ctx, int64_t* out, int64_t capacity, int64_t* bins);
+/* Device time in ms of the last rto_thickness_field: transform (its three passes), gather, summary (-1: not run). */
+int  rto_last_thickness_ms(const rto_context* ctx, float ms[3]);
+/* The gather's offset table depends on c alone; the context keeps the one of the last c from call to call, across grids, and
+ * builds another only when c changes.  *table_c = the c it was made for (0: none yet), *built = tables built so far (both may be
+ * NULL).  No value of any field depends on it. */
+int  rto_debug_thickness_table(const rto_context* ctx, int* table_c, int64_t* built);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -189,6 +189,17 @@ struct rto_context {
     int geoLook = 8;                          // relaxation launches per look at the device (rto_debug_set_geodesic_look): changes no value
     float geoMs[3] = { -1.f, -1.f, -1.f };    // the last rto_geodesic_field: init, relaxation, summary
     float geoEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_geodesic: field and flip, octree rebuild, triangle rebuild
+
+    // local thickness fields (rto_thickness.inc): the last field of the resident grid, with the medium and the cap c it was made
+    // for and its histogram (c + 1 bins, on the host); dropped whenever the grid changes
+    int* d_thick = nullptr;                   // nullptr: no field resident
+    int thickMedium = 0, thickCap = 0;
+    int* d_thickTab = nullptr;                // k_thick_gather's offset table for thickTabCap (0: none yet): it depends on c alone, so it
+                                              // outlives fields and grids and is freed by rto_destroy
+    int thickTabCap = 0;
+    int64_t thickTabBuilds = 0;               // tables this context has built (rto_debug_thickness_table)
+    int64_t thickBins[65] = { 0 };
+    float thickMs[3] = { -1.f, -1.f, -1.f };  // the last rto_thickness_field: transform, gather, summary
 };
 
 static thread_local std::string g_createError;
@@ -251,11 +262,15 @@ static void free_distance(rto_context* c) { (void)hipFree(c->d_dist); c->d_dist 
 // The resident geodesic field (rto_geodesic.inc): it describes one state of the grid.
 static void free_geodesic(rto_context* c) { (void)hipFree(c->d_geo); c->d_geo = nullptr; }
 
+// The resident local thickness field (rto_thickness.inc): it describes one state of the grid.
+static void free_thickness(rto_context* c) { (void)hipFree(c->d_thick); c->d_thick = nullptr; }
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
     free_distance(c);
     free_geodesic(c);
+    free_thickness(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -337,6 +352,7 @@ void rto_destroy(rto_context* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_octree(c);
+    (void)hipFree(c->d_thickTab);
     (void)hipFree(c->d_frame);
     (void)hipFree(c->d_rayX);
     (void)hipFree(c->d_rayY);
@@ -2846,3 +2862,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_components.inc"
 #include "rto_distance.inc"
 #include "rto_geodesic.inc"
+#include "rto_thickness.inc"

@@ -52,6 +52,8 @@ SYMBOLS = (
     "rto_last_morphology_ms",
     "rto_geodesic_field", "rto_download_geodesic", "rto_geodesic_device", "rto_geodesic_paths", "rto_edit_geodesic",
     "rto_last_geodesic_ms", "rto_last_geodesic_edit_ms", "rto_debug_geodesic_passes", "rto_debug_set_geodesic_look",
+    "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
+    "rto_debug_thickness_table",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -93,6 +95,9 @@ DIST_SUMMARY_DTYPE = np.dtype([("max_d2", "<i8"), ("argmax", "<i8"), ("finite", 
 # struct rto_geo_summary, 32 bytes: geodesic fields (rto_geodesic_field)
 GEO_SUMMARY_DTYPE = np.dtype([("max_g", "<i8"), ("argmax", "<i8"), ("reached", "<i8"), ("reserved", "<i8")])
 GEO_NO_LIMIT = 0x7fffffff
+# struct rto_thick_summary, 32 bytes: local thickness fields (rto_thickness_field)
+THICK_SUMMARY_DTYPE = np.dtype([("min_t2", "<i8"), ("argmin", "<i8"), ("thin", "<i8"), ("medium", "<i8")])
+THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -447,6 +452,12 @@ def load():
     L.rto_last_geodesic_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_geodesic_passes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rto_debug_set_geodesic_look.argtypes = [vp, C.c_int]
+    L.rto_thickness_field.argtypes = [vp, C.c_int, C.c_float, vp]
+    L.rto_download_thickness.argtypes = [vp, vp, C.c_int64]
+    L.rto_thickness_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_thickness_histogram.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_last_thickness_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_thickness_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1131,6 +1142,53 @@ class Context:
     def debug_set_geodesic_look(self, passes_per_look: int) -> None:
         """How many relaxation launches go out between two looks at the device (1 .. 64): changes no value."""
         self._check(self._L.rto_debug_set_geodesic_look(self._h, int(passes_per_look)))
+
+    # -- local thickness fields ----------------------------------------------------------
+    def thickness_field(self, medium: int = SET_SOLID, max_radius: float | None = None):
+        """rto_thickness_field: (the int32 (dimZ, dimY, dimX) volume of the squared radius, in voxel-index units, of the largest ball
+        inside `medium` (SET_SOLID: the material, SET_EMPTY: the free space) that contains each of its voxels, for balls up to
+        max_radius (world units, at least 1 and at most 8 voxels), 0 outside the medium; the summary as a THICK_SUMMARY_DTYPE
+        scalar).  The field stays resident until the grid changes."""
+        if max_radius is None:
+            raise ValueError("thickness_field: max_radius (world units, 1 to 8 voxels) has no default")
+        summary = np.zeros((), THICK_SUMMARY_DTYPE)
+        self._check(self._L.rto_thickness_field(self._h, int(medium), float(max_radius), summary.ctypes.data))
+        return self.thickness(), summary
+
+    def thickness(self) -> np.ndarray:
+        """The resident thickness field (rto_download_thickness)."""
+        self._check(self._L.rto_thickness_device(self._h, None))            # no field resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_thickness(self._h, out.ctypes.data, out.size))
+        return out
+
+    def thickness_device(self) -> int:
+        """The device pointer of the resident int32 thickness field."""
+        p = C.c_void_p()
+        self._check(self._L.rto_thickness_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def thickness_histogram(self) -> np.ndarray:
+        """rto_thickness_histogram: int64 bins[t], t = 0 .. c: the medium voxels of the resident field with t2 = t."""
+        bins = C.c_int64()
+        self._check(self._L.rto_thickness_histogram(self._h, None, 0, C.byref(bins)))
+        out = np.zeros(bins.value, np.int64)
+        self._check(self._L.rto_thickness_histogram(self._h, out.ctypes.data, out.size, None))
+        return out
+
+    def last_thickness_ms(self):
+        """Device ms of the last thickness_field: (transform, gather, summary); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_thickness_ms(self._h, ms))
+        return tuple(ms)
+
+    def thickness_table(self):
+        """rto_debug_thickness_table: (the c the gather's kept offset table was made for, 0: none yet; tables built so far)."""
+        c, built = C.c_int(), C.c_int64()
+        self._check(self._L.rto_debug_thickness_table(self._h, C.byref(c), C.byref(built)))
+        return c.value, built.value
 
     # -- region queries --------------------------------------------------------
     def query_points(self, points) -> np.ndarray:

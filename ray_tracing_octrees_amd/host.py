@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _build
 from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
-                  RtoError, _f)
+                  THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
 _vp = C.c_void_p
@@ -176,6 +176,14 @@ def load():
     L.rtoh_geodesic_flood_cpu.restype = C.c_int64
     L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
     L.rtoh_rt_geodesic_field.restype = C.c_int
+    L.rtoh_thickness_cpu.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]
+    L.rtoh_thickness_cpu.restype = C.c_int
+    L.rtoh_rt_thickness_field.argtypes = [_vp, C.c_int, C.c_float, _vp, C.c_int64, _vp]
+    L.rtoh_rt_thickness_field.restype = C.c_int
+    L.rtoh_rt_thinnest_point.argtypes = [_vp, C.c_int, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.rtoh_rt_thinnest_point.restype = C.c_int
+    L.rtoh_rt_thickness_histogram.argtypes = [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rtoh_rt_thickness_histogram.restype = C.c_int
     L.rtoh_rt_paths_to.argtypes = [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]
     L.rtoh_rt_paths_to.restype = C.c_int
     L.rtoh_rt_flood_from.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]
@@ -288,6 +296,21 @@ class VoxelGrid:
         """Addition: applyMorphologyCPU -- rto_edit_morphology's DILATE / ERODE / OPEN / CLOSE on this grid for rq quanta, on the
         CPU; the number of voxels changed (-1: refused, the grid untouched)."""
         return int(load().rtoh_morphology_cpu(self._h, int(op), int(rq)))
+
+    def thicknessField(self, medium: int = 1, mq: int = 64):
+        """Addition: thicknessFieldCPU (host/Thickness.h) -- the rule of rto_thickness_field on the CPU for a radius of mq quanta:
+        (code, t2 int32 (dimZ, dimY, dimX), bins int64 (c + 1), summary as a hip.THICK_SUMMARY_DTYPE scalar); t2 and bins are None
+        when refused."""
+        dx, dy, dz = self.dims
+        t2 = np.empty((dz, dy, dx), np.int32)
+        bins = np.zeros(THICK_MAX_C + 1, np.int64)
+        count = C.c_int64()
+        summary = np.zeros((), THICK_SUMMARY_DTYPE)
+        rc = int(load().rtoh_thickness_cpu(self._h, int(medium), int(mq), t2.ctypes.data, bins.ctypes.data, bins.size, C.byref(count),
+                                           summary.ctypes.data))
+        if rc != 0:
+            return rc, None, None, summary
+        return rc, t2, bins[:count.value].copy(), summary
 
     def geodesicField(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff):
         """Addition: geodesicFieldCPU (host/Geodesic.h) -- the rule of rto_geodesic_field on the CPU (a bucket queue): (code, g int32
@@ -709,6 +732,33 @@ class RayTracerBVH:
         if rc != 0 or not out[0]:
             return rc, None
         return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), float(dist.value))
+
+    def thicknessField(self, medium: int = 1, maxRadius: float = 0.0):
+        """Addition: RayTracerBVH::thicknessField -- (code, t2 int32 (dimZ, dimY, dimX), summary as a hip.THICK_SUMMARY_DTYPE
+        scalar); code is RTO_OK or the refusal's (lastError), and t2 is then None."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        t2 = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        summary = np.zeros((), THICK_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_thickness_field(self._h, int(medium), float(maxRadius), t2.ctypes.data, t2.size, summary.ctypes.data))
+        return rc, (t2 if rc == 0 else None), summary
+
+    def thinnestPoint(self, medium: int = 1, maxRadius: float = 0.0):
+        """Addition: RayTracerBVH::thinnestPoint -- (code, None or ((i, j, k), t2, thin, width in world units)) of the medium voxel
+        with the smallest local thickness."""
+        out = (C.c_int64 * 6)()
+        width = C.c_double()
+        rc = int(load().rtoh_rt_thinnest_point(self._h, int(medium), float(maxRadius), out, C.byref(width)))
+        if rc != 0 or not out[0]:
+            return rc, None
+        return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), int(out[5]), float(width.value))
+
+    def thicknessHistogram(self):
+        """Addition: RayTracerBVH::thicknessHistogram -- (code, int64 bins of the last thicknessField, or None)."""
+        bins = np.zeros(THICK_MAX_C + 1, np.int64)
+        count = C.c_int64()
+        rc = int(load().rtoh_rt_thickness_histogram(self._h, bins.ctypes.data, bins.size, C.byref(count)))
+        return rc, (bins[:count.value].copy() if rc == 0 else None)
 
     def geodesicField(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff):
         """Addition: RayTracerBVH::geodesicField -- (code, g int32 (dimZ, dimY, dimX), summary as a hip.GEO_SUMMARY_DTYPE scalar);

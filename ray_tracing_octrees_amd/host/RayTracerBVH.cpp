@@ -66,6 +66,9 @@ struct HipApi {
     decltype(&rto_download_geodesic) download_geodesic = nullptr;
     decltype(&rto_geodesic_paths) geodesic_paths = nullptr;
     decltype(&rto_edit_geodesic) edit_geodesic = nullptr;
+    decltype(&rto_thickness_field) thickness_field = nullptr;
+    decltype(&rto_download_thickness) download_thickness = nullptr;
+    decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
     std::string error;
 
     bool load() {
@@ -142,6 +145,9 @@ struct HipApi {
         download_geodesic = reinterpret_cast<decltype(download_geodesic)>(sym("rto_download_geodesic"));
         geodesic_paths = reinterpret_cast<decltype(geodesic_paths)>(sym("rto_geodesic_paths"));
         edit_geodesic = reinterpret_cast<decltype(edit_geodesic)>(sym("rto_edit_geodesic"));
+        thickness_field = reinterpret_cast<decltype(thickness_field)>(sym("rto_thickness_field"));
+        download_thickness = reinterpret_cast<decltype(download_thickness)>(sym("rto_download_thickness"));
+        thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -1001,6 +1007,55 @@ int RayTracerBVH::farthestPoint(const std::vector<int64_t>& seeds, int medium, i
     out.voxel = s.argmax;
     out.g = s.max_g;
     out.reached = s.reached;
+    return RTO_OK;
+}
+
+// The local thickness field of the first GPU's resident grid (rto_thickness_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::thicknessField(int medium, float maxRadius, std::vector<int32_t>* t2, rto_thick_summary* summary) {
+    if (t2) t2->clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "thicknessField: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("thickness field")) return RTO_E_HIP;
+    int rc = api().thickness_field(m_ctx, medium, maxRadius, summary);
+    if (rc == RTO_OK && t2) {
+        t2->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+        rc = api().download_thickness(m_ctx, t2->data(), (int64_t)t2->size());
+        if (rc != RTO_OK) t2->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "thicknessField");
+    return RTO_OK;
+}
+
+int RayTracerBVH::thinnestPoint(int medium, float maxRadius, ThinnestPoint& out) {
+    out = ThinnestPoint();
+    rto_thick_summary s;
+    const int rc = thicknessField(medium, maxRadius, nullptr, &s);
+    if (rc != RTO_OK) return rc;
+    if (s.medium == 0) return RTO_OK;                                   // no voxel of the medium to measure
+    out.found = true;
+    out.i = (int)(s.argmin % m_grid.dimX); out.j = (int)((s.argmin / m_grid.dimX) % m_grid.dimY); out.k = (int)(s.argmin / ((int64_t)m_grid.dimX * m_grid.dimY));
+    out.t2 = s.min_t2;
+    out.thin = s.thin;
+    out.width = 2.0 * std::sqrt((double)s.min_t2) * (double)m_grid.voxelSize;
+    return RTO_OK;
+}
+
+// The histogram of the last thicknessField (rto_thickness_histogram): c + 1 bins; empty with the refusal's code when none is resident.
+int RayTracerBVH::thicknessHistogram(std::vector<int64_t>& bins) {
+    bins.clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "thicknessHistogram: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    int64_t count = 0;
+    int rc = api().thickness_histogram(m_ctx, nullptr, 0, &count);
+    if (rc == RTO_OK) {
+        bins.assign((size_t)count, 0);
+        rc = api().thickness_histogram(m_ctx, bins.data(), count, nullptr);
+    }
+    if (rc != RTO_OK) { bins.clear(); return regionFailed(rc, "thicknessHistogram"); }
     return RTO_OK;
 }
 

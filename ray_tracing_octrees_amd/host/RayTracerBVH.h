@@ -240,6 +240,18 @@ public:
     int pathsTo(const std::vector<int64_t>& targets, int64_t maxLen, std::vector<int64_t>& voxels, std::vector<int64_t>& lengths);
     int64_t floodFrom(const std::vector<int64_t>& seeds, int medium, int connectivity = RTO_CONN_FACE, int64_t limit = 0x7fffffffll);
     int farthestPoint(const std::vector<int64_t>& seeds, int medium, int connectivity, FarthestPoint& out);
+    // Local thickness fields of the resident grid (rto_thickness_field).  thicknessField makes the field of the
+    // first GPU's grid: one int32 per voxel, x fastest, the squared radius in voxel-index units of the largest ball inside `medium`
+    // (RTO_SET_SOLID: the material, RTO_SET_EMPTY: the free space) that contains the voxel, for balls up to maxRadius (world units,
+    // 1 to 8 voxels), 0 outside the medium; t2 and summary may be null.  thinnestPoint is the medium voxel with the smallest value
+    // (the smallest index among equals), the number of voxels thinner than the cap, and the width 2 sqrt(t2) in world units; found
+    // stays false in a grid with no voxel of the medium.  thicknessHistogram gives the last field's c + 1 bins.  Each returns
+    // RTO_OK or the refusal's code, which is negative (lastError).  Arranged as section 19's methods are: they need the compute
+    // pipeline, and the CPU form of the same rule for a VoxelGrid is host/Thickness.h.
+    struct ThinnestPoint { bool found = false; int i = 0, j = 0, k = 0; int64_t t2 = 0, thin = 0; double width = 0.0; };
+    int thicknessField(int medium, float maxRadius, std::vector<int32_t>* t2, rto_thick_summary* summary = nullptr);
+    int thinnestPoint(int medium, float maxRadius, ThinnestPoint& out);
+    int thicknessHistogram(std::vector<int64_t>& bins);
     // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
     // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
     // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same

@@ -13,6 +13,7 @@
 #include "Components.h"
 #include "Distance.h"
 #include "Geodesic.h"
+#include "Thickness.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -376,6 +377,43 @@ int rtoh_rt_thickest_point(RayTracerBVH* rt, int64_t out[5], double* distance) {
     out[0] = t.found ? 1 : 0; out[1] = t.i; out[2] = t.j; out[3] = t.k; out[4] = t.d2;
     *distance = t.distance;
     return rc;
+}
+// Local thickness fields.  rtoh_thickness_cpu: the CPU form of the rule (Thickness.h) on a grid for mq quanta: t2 (dims product
+// int32), bins (capacity int64, *count = c + 1) and summary may be NULL; the code of rto_thickness_field.
+int rtoh_thickness_cpu(const VoxelGrid* g, int medium, int64_t mq, int32_t* t2, int64_t* bins, int64_t capacity, int64_t* count,
+                       rto_thick_summary* summary) {
+    std::vector<int32_t> f;
+    std::vector<int64_t> b;
+    const int rc = thicknessFieldCPU(*g, medium, mq, f, b, summary);
+    if (rc != RTO_OK) return rc;
+    if (t2) std::copy(f.begin(), f.end(), t2);
+    if (bins) std::copy(b.begin(), b.begin() + (size_t)std::min<int64_t>((int64_t)b.size(), capacity), bins);
+    if (count) *count = (int64_t)b.size();
+    return RTO_OK;
+}
+// RayTracerBVH::thicknessField / thinnestPoint / thicknessHistogram: the class's codes; out = found, i, j, k, t2, thin as int64 and
+// the width; bins: capacity int64, *count = the bins there are.
+int rtoh_rt_thickness_field(RayTracerBVH* rt, int medium, float maxRadius, int32_t* t2, int64_t capacity, rto_thick_summary* summary) {
+    std::vector<int32_t> f;
+    const int rc = rt->thicknessField(medium, maxRadius, t2 ? &f : nullptr, summary);
+    if (rc != RTO_OK) return rc;
+    if (t2) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), t2);
+    return RTO_OK;
+}
+int rtoh_rt_thinnest_point(RayTracerBVH* rt, int medium, float maxRadius, int64_t out[6], double* width) {
+    RayTracerBVH::ThinnestPoint t;
+    const int rc = rt->thinnestPoint(medium, maxRadius, t);
+    out[0] = t.found ? 1 : 0; out[1] = t.i; out[2] = t.j; out[3] = t.k; out[4] = t.t2; out[5] = t.thin;
+    *width = t.width;
+    return rc;
+}
+int rtoh_rt_thickness_histogram(RayTracerBVH* rt, int64_t* bins, int64_t capacity, int64_t* count) {
+    std::vector<int64_t> b;
+    const int rc = rt->thicknessHistogram(b);
+    if (rc != RTO_OK) return rc;
+    if (bins) std::copy(b.begin(), b.begin() + (size_t)std::min<int64_t>((int64_t)b.size(), capacity), bins);
+    if (count) *count = (int64_t)b.size();
+    return RTO_OK;
 }
 // Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
 // NULL; the code of rto_geodesic_field.  rtoh_geodesic_paths_cpu walks a field of that grid; rtoh_geodesic_flood_cpu edits the grid
