@@ -1066,6 +1066,57 @@ int  rto_last_thickness_ms(const rto_context* ctx, float ms[3]);
  * NULL).  No value of any field depends on it. */
 int  rto_debug_thickness_table(const rto_context* ctx, int* table_c, int64_t* built);
 
+/* ---- component measures -------------------------------------------------------
+ * What every piece of the resident labelling measures: its surface by direction, its first and second moments (centre of mass,
+ * principal axes) and its Euler number (blob, ring or shell: pieces - tunnels + cavities).  How much surface a piece that a carve
+ * cut loose has, whether a voxelized part has a through-hole.  No reference counterpart.  Every number is an integer sum over a
+ * voxel and its 3 x 3 x 3 neighbours that a brute-force loop over rto_download_labels reproduces bit for bit.
+ *
+ * Rule.  Measures describe the RESIDENT LABELLING: the set (RTO_SET_SOLID / RTO_SET_EMPTY) and the
+ * connectivity (RTO_CONN_FACE / RTO_CONN_FULL) of the last rto_label_components.  "In the set" means label >= 0; voxels outside
+ * the grid are not in the set; voxel (i, j, k) has linear index v = i + dimX (j + dimY k).  One record per component, in the
+ * table's order, and one for the whole set (the total row):
+ *   voxels    the component's size (== rto_component.voxels).
+ *   faces[d]  the voxels of the component whose neighbour in direction d (-x, +x, -y, +y, -z, +z) is not in the set; a neighbour
+ *             beyond the grid is not in the set.  Both connectivities join face neighbours, so a face neighbour that is in the
+ *             set is in the same component.
+ *   cells     under RTO_CONN_FULL the component is read as a union of closed unit cubes: n0, n1, n2 are the numbers of distinct
+ *             lattice vertices, edges and faces incident to at least one of its voxels.  Two voxels that share a vertex are
+ *             26-adjacent, so every such cell belongs to exactly one component; it is counted at the incident set voxel with
+ *             the smallest linear index.
+ *             Under RTO_CONN_FACE: P the face-adjacent pairs with both voxels in the set, Q the axis-aligned 2 x 2 squares with
+ *             all four in the set, O the 2 x 2 x 2 blocks with all eight in the set, each counted at its lowest corner.  A fully
+ *             set pair, square or block is face-connected, so it lies in one component.
+ *   euler     FULL: n0 - n1 + n2 - voxels.  FACE: voxels - P + Q - O.  The component's Euler number under its connectivity:
+ *             pieces (1) - tunnels + cavities.
+ *   sum       of i, of j, of k over the component's voxels;  sum2 of ii, jj, kk, ij, ik, jk.
+ *   total     the sum of the records field by field; cells are disjoint between components, so its euler is the Euler number
+ *             of the whole set.  All zero for an empty set.
+ * Range: a grid with a dimension above 32768 is RTO_E_UNSUPPORTED; below that every sum stays under 2^61 (voxels <= 2^31, an
+ * index is below 2^15).
+ * rto_measure_components keeps the table resident beside the labels; it is freed wherever the labels are freed (every call that
+ * changes or replaces the grid, a fresh rto_label_components, rto_destroy) and the readers then return RTO_E_INVALID.  The total
+ * is made on the device: no download of the table.  Synchronous on the context's stream.
+ * Errors, each leaving the context untouched: RTO_E_INVALID (no resident labels; too small a capacity; no resident measures, for
+ * the readers); RTO_E_UNSUPPORTED (a dimension above 32768). */
+#define RTO_MEASURE_MAX_DIM 32768
+typedef struct rto_measure {      /* 160 bytes */
+    int64_t voxels;               /* == rto_component.voxels */
+    int64_t faces[6];             /* exposed faces by direction: -x, +x, -y, +y, -z, +z */
+    int64_t cells[3];             /* FULL: n0, n1, n2   FACE: P, Q, O */
+    int64_t euler;                /* FULL: n0 - n1 + n2 - voxels   FACE: voxels - P + Q - O */
+    int64_t sum[3];               /* sum of i, of j, of k */
+    int64_t sum2[6];              /* sum of ii, jj, kk, ij, ik, jk */
+} rto_measure;
+
+int  rto_measure_components(rto_context* ctx, rto_measure* total /* may be NULL */);
+/* The resident table: *count records (may be NULL); out == NULL: the count alone. */
+int  rto_download_measures(rto_context* ctx, rto_measure* out, int64_t capacity, int64_t* count);
+/* The resident table (a device pointer the context owns, valid until the measures are freed). */
+int  rto_measures_device(rto_context* ctx, rto_measure** d_measures, int64_t* count);
+/* Device time in ms of the last rto_measure_components: the measuring kernels (with the memset in front), the total (-1: not run). */
+int  rto_last_measure_ms(const rto_context* ctx, float ms[2]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -175,6 +175,11 @@ struct rto_context {
     int64_t ccCount = 0;
     int ccPasses = 0;
     float ccMs[4] = { -1.f, -1.f, -1.f, -1.f };
+    int ccSet = 0, ccConn = 0;                // what the resident labelling labels (rto_measure.inc reads the connectivity)
+
+    // component measures (rto_measure.inc): one record per component of the resident labelling and the total row; freed with the labels
+    rto_measure* d_ccMeasures = nullptr;      // nullptr: no measures resident; count records, then the total
+    float measureMs[2] = { -1.f, -1.f };      // the last rto_measure_components: the measuring kernels, the total
 
     // distance fields (rto_distance.inc): the last field of the resident grid; dropped whenever the grid changes
     int* d_dist = nullptr;                    // nullptr: no field resident
@@ -253,6 +258,7 @@ static void free_cull_buffers(rto_context* c) {
 static void free_components(rto_context* c) {
     (void)hipFree(c->d_ccLabels); c->d_ccLabels = nullptr;
     (void)hipFree(c->d_ccComps); c->d_ccComps = nullptr;
+    (void)hipFree(c->d_ccMeasures); c->d_ccMeasures = nullptr;
     c->ccCount = 0;
 }
 
@@ -2863,3 +2869,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_distance.inc"
 #include "rto_geodesic.inc"
 #include "rto_thickness.inc"
+#include "rto_measure.inc"

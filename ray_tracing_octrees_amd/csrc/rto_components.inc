@@ -585,6 +585,7 @@ int rto_label_components(rto_context* c, int set, int connectivity, int64_t* cou
     if (rc != RTO_OK) return rc;
     free_components(c);
     c->d_ccLabels = r.d_labels; c->d_ccComps = r.d_comps; c->ccCount = r.count; c->ccPasses = r.passes;
+    c->ccSet = set; c->ccConn = connectivity;
     for (int i = 0; i < 4; i++) c->ccMs[i] = r.ms[i];
     if (count) *count = r.count;
     return RTO_OK;

@@ -54,6 +54,7 @@ SYMBOLS = (
     "rto_last_geodesic_ms", "rto_last_geodesic_edit_ms", "rto_debug_geodesic_passes", "rto_debug_set_geodesic_look",
     "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
     "rto_debug_thickness_table",
+    "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -98,9 +99,36 @@ GEO_NO_LIMIT = 0x7fffffff
 # struct rto_thick_summary, 32 bytes: local thickness fields (rto_thickness_field)
 THICK_SUMMARY_DTYPE = np.dtype([("min_t2", "<i8"), ("argmin", "<i8"), ("thin", "<i8"), ("medium", "<i8")])
 THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
+# struct rto_measure, 160 bytes: component measures (rto_measure_components)
+MEASURE_DTYPE = np.dtype([("voxels", "<i8"), ("faces", "<i8", (6,)), ("cells", "<i8", (3,)), ("euler", "<i8"), ("sum", "<i8", (3,)),
+                          ("sum2", "<i8", (6,))])
+MEASURE_MAX_DIM = 32768  # RTO_MEASURE_MAX_DIM: the largest dimension rto_measure_components takes
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
+
+
+def measure_physical(m, grid_min, voxel_size):
+    """World-space quantities of MEASURE_DTYPE records (an array or one record), in float64: a dict of volume (voxels vs^3), area
+    (all exposed faces, vs^2 each), centroid (grid_min + (sum / voxels + 0.5) vs: a voxel spans [grid_min + i vs, grid_min +
+    (i + 1) vs]), covariance (3 x 3, of the voxel centres, world units squared), and its principal axes by numpy.linalg.eigh:
+    axes_variance ascending and axes with the unit axis k in column k.  Records with no voxel give NaN."""
+    m = np.asarray(m)
+    gm = np.asarray(grid_min, np.float64).reshape(3)
+    vs = float(voxel_size)
+    n = m["voxels"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = m["sum"].astype(np.float64) / n[..., None]
+        s2 = m["sum2"].astype(np.float64) / n[..., None]
+    cov = np.empty(m.shape + (3, 3), np.float64)
+    for k, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+        cov[..., a, b] = cov[..., b, a] = (s2[..., k] - mean[..., a] * mean[..., b]) * vs * vs
+    ok = np.isfinite(cov).all(axis=(-1, -2))
+    var, axes = np.linalg.eigh(np.where(ok[..., None, None], cov, np.eye(3)))
+    var = np.where(ok[..., None], var, np.nan)
+    axes = np.where(ok[..., None, None], axes, np.nan)
+    return {"volume": n * vs ** 3, "area": m["faces"].sum(axis=-1).astype(np.float64) * vs * vs, "centroid": gm + (mean + 0.5) * vs,
+            "covariance": cov, "axes_variance": var, "axes": axes}
 
 
 class RtoError(RuntimeError):
@@ -458,6 +486,10 @@ def load():
     L.rto_thickness_histogram.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.rto_last_thickness_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_thickness_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.rto_measure_components.argtypes = [vp, vp]
+    L.rto_download_measures.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_measures_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_last_measure_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1018,6 +1050,51 @@ class Context:
         changed = C.c_int64()
         self._check(self._L.rto_edit_components(self._h, int(set), int(connectivity), int(select), int(arg), C.byref(changed)))
         return changed.value
+
+    # -- component measures -------------------------------------------------------
+    def measure_components(self):
+        """rto_measure_components: measure every component of the resident labelling (the set and connectivity of the last
+        label_components): (the table as a MEASURE_DTYPE array in the component table's order, the total row as a MEASURE_DTYPE
+        scalar).  The table stays resident beside the labels and goes when they go."""
+        total = np.zeros((), MEASURE_DTYPE)
+        self._check(self._L.rto_measure_components(self._h, total.ctypes.data))
+        return self.component_measures(), total
+
+    def component_measures(self) -> np.ndarray:
+        """The resident measures (rto_download_measures)."""
+        n = C.c_int64()
+        self._check(self._L.rto_download_measures(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, MEASURE_DTYPE)
+        if n.value:
+            self._check(self._L.rto_download_measures(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def component_measures_device(self):
+        """(device pointer of the 160-byte measure records, count)."""
+        p, n = C.c_void_p(), C.c_int64()
+        self._check(self._L.rto_measures_device(self._h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def last_measure_ms(self):
+        """Device ms of the last measure_components: (the measuring kernels, the total); -1: not run."""
+        ms = (C.c_float * 2)()
+        self._check(self._L.rto_last_measure_ms(self._h, ms))
+        return tuple(ms)
+
+    def topology(self, set: int = SET_SOLID, connectivity: int = CONN_FACE):
+        """(pieces, tunnels, cavities) of the set under `connectivity`.  Three steps: label the complement under the dual
+        connectivity (6 <-> 26) and count its components that touch no grid face, the cavities; label the set and count the
+        pieces; measure, and take tunnels = pieces + cavities - total euler.  The SET's labels and measures are what is resident
+        afterwards (the complement's labelling is replaced by step two)."""
+        other = SET_EMPTY if int(set) == SET_SOLID else SET_SOLID
+        dual = CONN_FULL if int(connectivity) == CONN_FACE else CONN_FACE
+        if int(connectivity) not in (CONN_FACE, CONN_FULL):
+            dual = int(connectivity)                                          # refused below, by the library, with its message
+        outside = self.label_components(other, dual)
+        cavities = int((outside["touches"] == 0).sum())
+        pieces = len(self.label_components(set, connectivity))
+        _, total = self.measure_components()
+        return pieces, pieces + cavities - int(total["euler"]), cavities
 
     # -- distance fields and morphology ------------------------------------------
     def distance_field(self, set: int = SET_SOLID, max_dist: float = float("inf")):

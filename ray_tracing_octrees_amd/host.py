@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
@@ -184,6 +184,16 @@ def load():
     L.rtoh_rt_thinnest_point.restype = C.c_int
     L.rtoh_rt_thickness_histogram.argtypes = [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
     L.rtoh_rt_thickness_histogram.restype = C.c_int
+    L.rtoh_measure_cpu.argtypes = [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, _vp]
+    L.rtoh_measure_cpu.restype = C.c_int
+    L.rtoh_rt_measure_components.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]
+    L.rtoh_rt_measure_components.restype = C.c_int
+    L.rtoh_rt_surface_area.argtypes = [_vp, C.c_int, C.POINTER(C.c_double)]
+    L.rtoh_rt_surface_area.restype = C.c_int
+    L.rtoh_rt_centroid.argtypes = [_vp, C.c_int, C.POINTER(C.c_double)]
+    L.rtoh_rt_centroid.restype = C.c_int
+    L.rtoh_rt_topology.argtypes = [_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    L.rtoh_rt_topology.restype = C.c_int
     L.rtoh_rt_paths_to.argtypes = [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]
     L.rtoh_rt_paths_to.restype = C.c_int
     L.rtoh_rt_flood_from.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64]
@@ -210,6 +220,18 @@ def load():
     L.rtoh_tris_take.restype = None
     _lib = L
     return L
+
+
+def measureComponentsCPU(labels, count: int, connectivity: int = 6):
+    """Addition: measureComponentsCPU (host/Measure.h) -- the rule of rto_measure_components as plain loops over an int32 label volume
+    (dimZ, dimY, dimX) with labels in [0, count), -1 outside the set: (code, table as a hip.MEASURE_DTYPE array or None when refused,
+    total as a hip.MEASURE_DTYPE scalar)."""
+    l = np.ascontiguousarray(labels, np.int32)
+    dims = (C.c_int * 3)(l.shape[2], l.shape[1], l.shape[0])
+    table = np.zeros(max(int(count), 0), MEASURE_DTYPE)
+    total = np.zeros((), MEASURE_DTYPE)
+    rc = int(load().rtoh_measure_cpu(dims, l.ctypes.data, int(count), int(connectivity), table.ctypes.data, len(table), total.ctypes.data))
+    return rc, (table if rc == 0 else None), total
 
 
 class VoxelGrid:
@@ -759,6 +781,39 @@ class RayTracerBVH:
         count = C.c_int64()
         rc = int(load().rtoh_rt_thickness_histogram(self._h, bins.ctypes.data, bins.size, C.byref(count)))
         return rc, (bins[:count.value].copy() if rc == 0 else None)
+
+    def measureComponents(self, set: int = 1, connectivity: int = 6):
+        """Addition: RayTracerBVH::measureComponents -- labels `set` under `connectivity` and measures every component: (code, table
+        as a hip.MEASURE_DTYPE array or None when refused, total as a hip.MEASURE_DTYPE scalar)."""
+        total = np.zeros((), MEASURE_DTYPE)
+        n = C.c_int64()
+        rc = int(load().rtoh_rt_measure_components(self._h, int(set), int(connectivity), None, 0, C.byref(n), total.ctypes.data))
+        if rc != 0:
+            return rc, None, total
+        table = np.zeros(n.value, MEASURE_DTYPE)
+        if n.value:
+            rc = int(load().rtoh_rt_measure_components(self._h, int(set), int(connectivity), table.ctypes.data, n.value, C.byref(n), total.ctypes.data))
+        return rc, (table if rc == 0 else None), total
+
+    def surfaceArea(self, set: int = 1):
+        """Addition: RayTracerBVH::surfaceArea -- (code, the exposed faces of the set times voxelSize^2)."""
+        area = C.c_double()
+        rc = int(load().rtoh_rt_surface_area(self._h, int(set), C.byref(area)))
+        return rc, float(area.value)
+
+    def centroid(self, set: int = 1):
+        """Addition: RayTracerBVH::centroid -- (code, None or the set's centre of mass (x, y, z) in world units)."""
+        out = (C.c_double * 4)()
+        rc = int(load().rtoh_rt_centroid(self._h, int(set), out))
+        if rc != 0 or not out[0]:
+            return rc, None
+        return rc, (float(out[1]), float(out[2]), float(out[3]))
+
+    def topology(self, set: int = 1, connectivity: int = 6):
+        """Addition: RayTracerBVH::topology -- (code, (pieces, tunnels, cavities))."""
+        out = (C.c_int64 * 3)()
+        rc = int(load().rtoh_rt_topology(self._h, int(set), int(connectivity), out))
+        return rc, (int(out[0]), int(out[1]), int(out[2]))
 
     def geodesicField(self, seeds, medium: int = 0, connectivity: int = 6, limit: int = 0x7fffffff):
         """Addition: RayTracerBVH::geodesicField -- (code, g int32 (dimZ, dimY, dimX), summary as a hip.GEO_SUMMARY_DTYPE scalar);

@@ -69,6 +69,8 @@ struct HipApi {
     decltype(&rto_thickness_field) thickness_field = nullptr;
     decltype(&rto_download_thickness) download_thickness = nullptr;
     decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
+    decltype(&rto_measure_components) measure_components = nullptr;
+    decltype(&rto_download_measures) download_measures = nullptr;
     std::string error;
 
     bool load() {
@@ -148,6 +150,8 @@ struct HipApi {
         thickness_field = reinterpret_cast<decltype(thickness_field)>(sym("rto_thickness_field"));
         download_thickness = reinterpret_cast<decltype(download_thickness)>(sym("rto_download_thickness"));
         thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
+        measure_components = reinterpret_cast<decltype(measure_components)>(sym("rto_measure_components"));
+        download_measures = reinterpret_cast<decltype(download_measures)>(sym("rto_download_measures"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -1056,6 +1060,83 @@ int RayTracerBVH::thicknessHistogram(std::vector<int64_t>& bins) {
         rc = api().thickness_histogram(m_ctx, bins.data(), count, nullptr);
     }
     if (rc != RTO_OK) { bins.clear(); return regionFailed(rc, "thicknessHistogram"); }
+    return RTO_OK;
+}
+
+// The measures of the first GPU's resident grid (rto_measure_components): labels `set` under `connectivity` afresh, then measures
+// that labelling; the code is RTO_OK or the refusal's.
+int RayTracerBVH::measureComponents(int set, int connectivity, std::vector<rto_measure>* table, rto_measure* total) {
+    if (table) table->clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "measureComponents: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("component measures")) return RTO_E_HIP;
+    int64_t count = 0;
+    int rc = api().label_components(m_ctx, set, connectivity, &count);
+    if (rc == RTO_OK) rc = api().measure_components(m_ctx, total);
+    if (rc == RTO_OK && table && count > 0) {
+        table->resize((size_t)count);
+        rc = api().download_measures(m_ctx, table->data(), count, nullptr);
+        if (rc != RTO_OK) table->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "measureComponents");
+    return RTO_OK;
+}
+
+int RayTracerBVH::surfaceArea(int set, double& area) {
+    area = 0.0;
+    rto_measure t;
+    const int rc = measureComponents(set, RTO_CONN_FACE, nullptr, &t);
+    if (rc != RTO_OK) return rc;
+    int64_t faces = 0;
+    for (int d = 0; d < 6; d++) faces += t.faces[d];
+    area = (double)faces * (double)m_grid.voxelSize * (double)m_grid.voxelSize;
+    return RTO_OK;
+}
+
+int RayTracerBVH::centroid(int set, Centroid& out) {
+    out = Centroid();
+    rto_measure t;
+    const int rc = measureComponents(set, RTO_CONN_FACE, nullptr, &t);
+    if (rc != RTO_OK) return rc;
+    if (t.voxels == 0) return RTO_OK;                                   // no voxel of the set to weigh
+    const double mins[3] = { (double)m_grid.minX, (double)m_grid.minY, (double)m_grid.minZ };
+    out.found = true;
+    out.voxels = t.voxels;
+    for (int a = 0; a < 3; a++) out.p[a] = mins[a] + ((double)t.sum[a] / (double)t.voxels + 0.5) * (double)m_grid.voxelSize;
+    return RTO_OK;
+}
+
+// Cavities first (the complement's components under the dual connectivity that touch no grid face), then the set's pieces, then
+// tunnels = pieces + cavities - euler.  The set's labels and measures stay resident.
+int RayTracerBVH::topology(int set, int connectivity, Topology& out) {
+    out = Topology();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "topology: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("topology")) return RTO_E_HIP;
+    // an unknown set or connectivity goes through as it is: the library refuses it with its message
+    const int other = set == RTO_SET_SOLID ? RTO_SET_EMPTY : (set == RTO_SET_EMPTY ? RTO_SET_SOLID : set);
+    const int dual = connectivity == RTO_CONN_FACE ? RTO_CONN_FULL : (connectivity == RTO_CONN_FULL ? RTO_CONN_FACE : connectivity);
+    int64_t count = 0;
+    std::vector<rto_component> outside;
+    int rc = api().label_components(m_ctx, other, dual, &count);
+    if (rc == RTO_OK && count > 0) {
+        outside.resize((size_t)count);
+        rc = api().download_components(m_ctx, outside.data(), count, &count);
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "topology");
+    int64_t cavities = 0;
+    for (const rto_component& c : outside) cavities += c.touches == 0 ? 1 : 0;
+    rto_measure t;
+    rc = api().label_components(m_ctx, set, connectivity, &count);
+    if (rc == RTO_OK) rc = api().measure_components(m_ctx, &t);
+    if (rc != RTO_OK) return regionFailed(rc, "topology");
+    out.pieces = count;
+    out.cavities = cavities;
+    out.tunnels = count + cavities - t.euler;
     return RTO_OK;
 }
 

@@ -252,6 +252,19 @@ public:
     int thicknessField(int medium, float maxRadius, std::vector<int32_t>* t2, rto_thick_summary* summary = nullptr);
     int thinnestPoint(int medium, float maxRadius, ThinnestPoint& out);
     int thicknessHistogram(std::vector<int64_t>& bins);
+    // Component measures of the resident grid (rto_measure_components).  measureComponents labels `set` under
+    // `connectivity` on the first GPU and measures every component: one rto_measure per component in the table's order (exposed
+    // faces by direction, cell counts, Euler number, first and second moments of the voxel indices) and their sum; table and total
+    // may be null.  surfaceArea is the total's exposed faces times voxelSize^2; centroid the centre of mass of the set in world
+    // units (found stays false for an empty set); topology the number of pieces, of tunnels through them and of cavities inside
+    // them under `connectivity` (the complement under the dual one).  Each returns RTO_OK or the refusal's code, which is negative
+    // (lastError), and leaves the set's labels and measures resident.  The CPU form of the same rule is host/Measure.h.
+    struct Centroid { bool found = false; double p[3] = { 0.0, 0.0, 0.0 }; int64_t voxels = 0; };
+    struct Topology { int64_t pieces = 0, tunnels = 0, cavities = 0; };
+    int measureComponents(int set, int connectivity, std::vector<rto_measure>* table, rto_measure* total = nullptr);
+    int surfaceArea(int set, double& area);
+    int centroid(int set, Centroid& out);
+    int topology(int set, int connectivity, Topology& out);
     // Region queries over the whole resident octree on the first GPU (rto_query_points_host, rto_query_regions_host,
     // rto_query_nearest_host): one record per point or brush.  The reference's click handler finds the voxel
     // under the cursor by a CPU march over the dense grid; locate is its GPU counterpart, census says what an editVoxels of the same

@@ -14,6 +14,7 @@
 #include "Distance.h"
 #include "Geodesic.h"
 #include "Thickness.h"
+#include "Measure.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -414,6 +415,40 @@ int rtoh_rt_thickness_histogram(RayTracerBVH* rt, int64_t* bins, int64_t capacit
     if (bins) std::copy(b.begin(), b.begin() + (size_t)std::min<int64_t>((int64_t)b.size(), capacity), bins);
     if (count) *count = (int64_t)b.size();
     return RTO_OK;
+}
+// Component measures.  rtoh_measure_cpu: the CPU form of the rule (Measure.h) on a label volume of dims[3]: out (capacity records)
+// and total may be NULL; the code of rto_measure_components.
+int rtoh_measure_cpu(const int* dims, const int32_t* labels, int64_t count, int connectivity, rto_measure* out, int64_t capacity,
+                     rto_measure* total) {
+    std::vector<rto_measure> t;
+    const int rc = measureComponentsCPU(dims[0], dims[1], dims[2], labels, count, connectivity, t, total);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), out);
+    return RTO_OK;
+}
+// RayTracerBVH::measureComponents / surfaceArea / centroid / topology: the class's codes; *count = the records there are, out
+// filled up to capacity; centroid: out = found, x, y, z as doubles; topology: out = pieces, tunnels, cavities.
+int rtoh_rt_measure_components(RayTracerBVH* rt, int set, int connectivity, rto_measure* out, int64_t capacity, int64_t* count,
+                               rto_measure* total) {
+    std::vector<rto_measure> t;
+    const int rc = rt->measureComponents(set, connectivity, &t, total);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), out);
+    if (count) *count = (int64_t)t.size();
+    return RTO_OK;
+}
+int rtoh_rt_surface_area(RayTracerBVH* rt, int set, double* area) { return rt->surfaceArea(set, *area); }
+int rtoh_rt_centroid(RayTracerBVH* rt, int set, double out[4]) {
+    RayTracerBVH::Centroid c;
+    const int rc = rt->centroid(set, c);
+    out[0] = c.found ? 1.0 : 0.0; out[1] = c.p[0]; out[2] = c.p[1]; out[3] = c.p[2];
+    return rc;
+}
+int rtoh_rt_topology(RayTracerBVH* rt, int set, int connectivity, int64_t out[3]) {
+    RayTracerBVH::Topology t;
+    const int rc = rt->topology(set, connectivity, t);
+    out[0] = t.pieces; out[1] = t.tunnels; out[2] = t.cavities;
+    return rc;
 }
 // Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
 // NULL; the code of rto_geodesic_field.  rtoh_geodesic_paths_cpu walks a field of that grid; rtoh_geodesic_flood_cpu edits the grid
