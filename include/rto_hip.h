@@ -1117,6 +1117,84 @@ int  rto_measures_device(rto_context* ctx, rto_measure** d_measures, int64_t* co
 /* Device time in ms of the last rto_measure_components: the measuring kernels (with the memset in front), the total (-1: not run). */
 int  rto_last_measure_ms(const rto_context* ctx, float ms[2]);
 
+/* ---- skeletons: topology-preserving thinning -----------------------------------
+ * The centreline of a shape of the resident grid: the one-voxel-wide curve down the middle of a corridor, a duct or a pore, the
+ * ring that is left of a part with a through-hole, the centred curve between two doors.  The set is peeled layer by layer, and a
+ * voxel leaves only when its going changes neither the pieces nor the tunnels nor the cavities of the set.  No reference
+ * counterpart.  Every result is an integer that a plain loop over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel (i, j, k) has linear index v = i + dimX (j + dimY k); the sets are rto_label_components': RTO_SET_SOLID the
+ *             voxels equal to 1, RTO_SET_EMPTY the voxels equal to 0.  A voxel outside the grid is NOT IN THE SET: this is the
+ *             convention of the component measures (section 22), under which their Euler number is the invariant here, and not
+ *             that of the distance fields (section 19), where the outside is no set at all.  So a set that touches a face of the
+ *             grid is peeled from that face too.
+ *   conn      X is the current set.  RTO_CONN_FULL joins X by 26 and its complement by 6; RTO_CONN_FACE joins X by 6 and its
+ *             complement by 26.
+ *   simple    N26*(p): the 26 neighbours of p; N18*(p): those that differ from p on at most two axes; N6*(p): the face
+ *             neighbours.  Under FULL p is simple when X n N26*(p) is non-empty and 26-connected within itself and, with
+ *             B = N18*(p) \ X, the set B n N6*(p) is non-empty and lies in one 6-connected component of B.  Under FACE the same
+ *             with the roles exchanged: X n N6*(p) is non-empty and lies in one 6-component of X n N18*(p), and N26*(p) \ X is
+ *             non-empty and 26-connected; that is simple_FULL of the complemented neighbourhood.
+ *   pass      p = 1, 2, ...  Mark: M = the voxels of X with a neighbour not in X (the 6 face neighbours under FULL, the 26 under
+ *             FACE), fixed for the whole pass: a pass peels at most one layer.  Then sub-steps s = 0 .. 7 in this order:
+ *             subfield s is the voxels with (i & 1) + 2 (j & 1) + 4 (k & 1) == s, and every voxel of subfield s that is in M, is
+ *             no anchor, is not kept by the mode and is simple, each read from the current X, leaves X, all of them at once.
+ *             Two voxels of one subfield are never 26-adjacent, so removing them together is removing them one after the other
+ *             in any order, each a simple point: pieces, tunnels and cavities of X are preserved, and nothing depends on
+ *             scheduling.  The first pass that removes nothing ends the thinning; so does max_passes.
+ *   modes     RTO_SKEL_TOPOLOGY keeps nothing extra: a blob becomes one voxel, a ring a closed curve, a shell a closed surface.
+ *             RTO_SKEL_CURVE keeps a voxel that has exactly one neighbour in X among its 26 (a curve's end); it needs
+ *             RTO_CONN_FULL.
+ *   anchors   n >= 0 linear indices, on the host, duplicates allowed.  An index outside [0, voxels) is RTO_E_INVALID; an anchor
+ *             that is not in the set is ignored; an anchor is never removed.  Two anchors in a simply connected space under
+ *             TOPOLOGY leave a centred curve between them.
+ *   field     k[v] as int32: -1 for a voxel not in the set, 0 for a voxel that stays (the skeleton), p >= 1 for the pass that
+ *             removed it.  A run with max_passes = m leaves exactly {k == 0 or k > m} of the unlimited run.
+ *   limit     max_passes below 1 is RTO_E_INVALID; RTO_SKEL_NO_LIMIT or more: none.
+ *   summary   kept the voxels with k == 0, removed those with k > 0, passes the largest k (the passes that removed something).
+ *   edit      rto_edit_skeleton makes its own field (the resident one is not consulted) and flips every voxel with k > 0: set
+ *             SOLID becomes EMPTY (0), set EMPTY becomes FILLED (1).  *changed (may be NULL) = voxels flipped.  When it is > 0
+ *             the context is left exactly as rto_edit_voxels leaves it after a change (labels, measures and the distance,
+ *             geodesic, thickness and skeleton fields freed); changed == 0 touches nothing.  Idempotent: a second call changes 0.
+ * rto_skeleton_field keeps the volume (int32 per voxel) resident beside the other fields, with its set, connectivity and mode;
+ * every call that changes or replaces the grid frees it as it frees them, and the readers then return RTO_E_INVALID.
+ * Synchronous on the context's stream.
+ * Errors, in rto_geodesic_field's order, each leaving the context untouched: RTO_E_INVALID (unknown set, connectivity or mode;
+ * CURVE with FACE; n < 0, or NULL anchors with n > 0; max_passes below 1; an anchor out of range; too small a capacity; no resident
+ * skeleton field, for the readers); RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the octree came from rto_upload_octree:
+ * no resident grid; more than 2^31 - 2 voxels); RTO_E_INTERNAL (more than voxels + 1 passes: every pass but the last removes a
+ * voxel). */
+#define RTO_SKEL_TOPOLOGY 0
+#define RTO_SKEL_CURVE    1
+#define RTO_SKEL_NO_LIMIT 0x7fffffff
+typedef struct rto_skel_summary {   /* 32 bytes */
+    int64_t kept;                   /* voxels with k == 0: the skeleton */
+    int64_t removed;                /* voxels with k > 0 */
+    int64_t passes;                 /* the largest k: the passes that removed something */
+    int64_t reserved;               /* 0 */
+} rto_skel_summary;
+
+int  rto_skeleton_field(rto_context* ctx, int set, int connectivity, int mode, const int64_t* anchors /* may be NULL when n is 0 */,
+                        int64_t n, int64_t max_passes, rto_skel_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_skeleton(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed). */
+int  rto_skeleton_device(rto_context* ctx, int32_t** d_k);
+int  rto_edit_skeleton(rto_context* ctx, int set, int connectivity, int mode, const int64_t* anchors, int64_t n, int64_t max_passes,
+                       int64_t* changed /* may be NULL */);
+/* Device time in ms of the last rto_skeleton_field: init, thinning (all passes, with the host's looks at the device), summary
+ * (-1: not run). */
+int  rto_last_skeleton_ms(const rto_context* ctx, float ms[3]);
+/* Device time in ms of the last rto_edit_skeleton: field and flip, octree rebuild, triangle rebuild (-1: not run). */
+int  rto_last_skeleton_edit_ms(const rto_context* ctx, float ms[3]);
+/* The last rto_skeleton_field: kernel launches of the thinning (one mark and eight sub-steps per pass sent out, the passes behind
+ * the fixed point included) and the tiles run summed over the sub-steps (may be NULL). */
+int  rto_debug_skeleton_passes(const rto_context* ctx, int64_t* launches, int64_t* tiles_run);
+/* How many passes go out between two looks of the host at the device (1 .. 64, 8 by default).  A tuning choice: passes behind the
+ * fixed point remove nothing, so no value of any field or edit depends on it. */
+int  rto_debug_set_skeleton_look(rto_context* ctx, int passes_per_look);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -205,6 +205,15 @@ struct rto_context {
     int64_t thickTabBuilds = 0;               // tables this context has built (rto_debug_thickness_table)
     int64_t thickBins[65] = { 0 };
     float thickMs[3] = { -1.f, -1.f, -1.f };  // the last rto_thickness_field: transform, gather, summary
+
+    // skeleton fields (rto_skeleton.inc): the last field of the resident grid, with the set, connectivity and mode it was made
+    // for; dropped whenever the grid changes
+    int* d_skel = nullptr;                    // nullptr: no field resident
+    int skelSet = 0, skelConn = 0, skelMode = 0;
+    int64_t skelLaunches = 0, skelTilesRun = 0;
+    int skelLook = 8;                         // passes per look at the device (rto_debug_set_skeleton_look): changes no value
+    float skelMs[3] = { -1.f, -1.f, -1.f };   // the last rto_skeleton_field: init, thinning, summary
+    float skelEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_skeleton: field and flip, octree rebuild, triangle rebuild
 };
 
 static thread_local std::string g_createError;
@@ -271,12 +280,16 @@ static void free_geodesic(rto_context* c) { (void)hipFree(c->d_geo); c->d_geo = 
 // The resident local thickness field (rto_thickness.inc): it describes one state of the grid.
 static void free_thickness(rto_context* c) { (void)hipFree(c->d_thick); c->d_thick = nullptr; }
 
+// The resident skeleton field (rto_skeleton.inc): it describes one state of the grid.
+static void free_skeleton(rto_context* c) { (void)hipFree(c->d_skel); c->d_skel = nullptr; }
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
     free_distance(c);
     free_geodesic(c);
     free_thickness(c);
+    free_skeleton(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -2870,3 +2883,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_geodesic.inc"
 #include "rto_thickness.inc"
 #include "rto_measure.inc"
+#include "rto_skeleton.inc"

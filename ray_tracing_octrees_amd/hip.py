@@ -52,6 +52,8 @@ SYMBOLS = (
     "rto_last_morphology_ms",
     "rto_geodesic_field", "rto_download_geodesic", "rto_geodesic_device", "rto_geodesic_paths", "rto_edit_geodesic",
     "rto_last_geodesic_ms", "rto_last_geodesic_edit_ms", "rto_debug_geodesic_passes", "rto_debug_set_geodesic_look",
+    "rto_skeleton_field", "rto_download_skeleton", "rto_skeleton_device", "rto_edit_skeleton", "rto_last_skeleton_ms",
+    "rto_last_skeleton_edit_ms", "rto_debug_skeleton_passes", "rto_debug_set_skeleton_look",
     "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
     "rto_debug_thickness_table",
     "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
@@ -96,6 +98,10 @@ DIST_SUMMARY_DTYPE = np.dtype([("max_d2", "<i8"), ("argmax", "<i8"), ("finite", 
 # struct rto_geo_summary, 32 bytes: geodesic fields (rto_geodesic_field)
 GEO_SUMMARY_DTYPE = np.dtype([("max_g", "<i8"), ("argmax", "<i8"), ("reached", "<i8"), ("reserved", "<i8")])
 GEO_NO_LIMIT = 0x7fffffff
+# struct rto_skel_summary, 32 bytes: skeleton fields (rto_skeleton_field)
+SKEL_SUMMARY_DTYPE = np.dtype([("kept", "<i8"), ("removed", "<i8"), ("passes", "<i8"), ("reserved", "<i8")])
+SKEL_TOPOLOGY, SKEL_CURVE = 0, 1
+SKEL_NO_LIMIT = 0x7fffffff
 # struct rto_thick_summary, 32 bytes: local thickness fields (rto_thickness_field)
 THICK_SUMMARY_DTYPE = np.dtype([("min_t2", "<i8"), ("argmin", "<i8"), ("thin", "<i8"), ("medium", "<i8")])
 THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
@@ -480,6 +486,14 @@ def load():
     L.rto_last_geodesic_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_geodesic_passes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rto_debug_set_geodesic_look.argtypes = [vp, C.c_int]
+    L.rto_skeleton_field.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp]
+    L.rto_download_skeleton.argtypes = [vp, vp, C.c_int64]
+    L.rto_skeleton_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_edit_skeleton.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_last_skeleton_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_last_skeleton_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_skeleton_passes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.rto_debug_set_skeleton_look.argtypes = [vp, C.c_int]
     L.rto_thickness_field.argtypes = [vp, C.c_int, C.c_float, vp]
     L.rto_download_thickness.argtypes = [vp, vp, C.c_int64]
     L.rto_thickness_device.argtypes = [vp, C.POINTER(vp)]
@@ -1219,6 +1233,64 @@ class Context:
     def debug_set_geodesic_look(self, passes_per_look: int) -> None:
         """How many relaxation launches go out between two looks at the device (1 .. 64): changes no value."""
         self._check(self._L.rto_debug_set_geodesic_look(self._h, int(passes_per_look)))
+
+    # -- skeletons: topology-preserving thinning ------------------------------------------
+    def skeleton_field(self, set: int = SET_SOLID, connectivity: int = CONN_FULL, mode: int = SKEL_TOPOLOGY, anchors=(), max_passes=None):
+        """rto_skeleton_field: (the int32 (dimZ, dimY, dimX) volume k of the thinning of `set`: -1 outside the set, 0 for the voxels
+        that stay (the skeleton), p >= 1 for the pass that removed the voxel; the summary as a SKEL_SUMMARY_DTYPE scalar).
+        `anchors` (linear indices, or an (n, 3) array of (i, j, k)) are never removed; max_passes None: no limit.  The field stays
+        resident until the grid changes."""
+        a = self._voxel_indices(anchors) if len(anchors) else np.empty(0, np.int64)
+        summary = np.zeros((), SKEL_SUMMARY_DTYPE)
+        self._check(self._L.rto_skeleton_field(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
+                                               SKEL_NO_LIMIT if max_passes is None else int(max_passes), summary.ctypes.data))
+        return self.skeleton(), summary
+
+    def skeleton(self) -> np.ndarray:
+        """The resident skeleton field (rto_download_skeleton)."""
+        self._check(self._L.rto_skeleton_device(self._h, None))             # no field resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_skeleton(self._h, out.ctypes.data, out.size))
+        return out
+
+    def skeleton_device(self) -> int:
+        """The device pointer of the resident int32 skeleton field."""
+        p = C.c_void_p()
+        self._check(self._L.rto_skeleton_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def edit_skeleton(self, set: int = SET_SOLID, connectivity: int = CONN_FULL, mode: int = SKEL_TOPOLOGY, anchors=(), max_passes=None) -> int:
+        """rto_edit_skeleton: replaces `set` by its skeleton (every voxel the thinning removes is flipped), rebuilt as edit_voxels
+        does; the number of voxels flipped."""
+        a = self._voxel_indices(anchors) if len(anchors) else np.empty(0, np.int64)
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_skeleton(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
+                                              SKEL_NO_LIMIT if max_passes is None else int(max_passes), C.byref(changed)))
+        return changed.value
+
+    def last_skeleton_ms(self):
+        """Device ms of the last skeleton_field: (init, thinning, summary); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_skeleton_ms(self._h, ms))
+        return tuple(ms)
+
+    def last_skeleton_edit_ms(self):
+        """Device ms of the last edit_skeleton: (field and flip, octree rebuild, triangle rebuild); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_skeleton_edit_ms(self._h, ms))
+        return tuple(ms)
+
+    def skeleton_passes(self):
+        """(kernel launches, tiles run summed over the sub-steps) of the last skeleton_field's thinning."""
+        p, t = C.c_int64(), C.c_int64()
+        self._check(self._L.rto_debug_skeleton_passes(self._h, C.byref(p), C.byref(t)))
+        return p.value, t.value
+
+    def debug_set_skeleton_look(self, passes_per_look: int) -> None:
+        """How many passes go out between two looks at the device (1 .. 64): changes no value."""
+        self._check(self._L.rto_debug_set_skeleton_look(self._h, int(passes_per_look)))
 
     # -- local thickness fields ----------------------------------------------------------
     def thickness_field(self, medium: int = SET_SOLID, max_radius: float | None = None):

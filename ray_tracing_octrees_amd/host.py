@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
@@ -174,6 +174,18 @@ def load():
     L.rtoh_geodesic_paths_cpu.restype = C.c_int
     L.rtoh_geodesic_flood_cpu.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64]
     L.rtoh_geodesic_flood_cpu.restype = C.c_int64
+    L.rtoh_skeleton_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, _vp]
+    L.rtoh_skeleton_cpu.restype = C.c_int
+    L.rtoh_skeleton_thin_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64]
+    L.rtoh_skeleton_thin_cpu.restype = C.c_int64
+    L.rtoh_skeleton_simple.argtypes = [C.c_uint32, C.c_int]
+    L.rtoh_skeleton_simple.restype = C.c_int
+    L.rtoh_rt_skeleton_field.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp]
+    L.rtoh_rt_skeleton_field.restype = C.c_int
+    L.rtoh_rt_thin.argtypes = [_vp, C.c_int, C.c_int64]
+    L.rtoh_rt_thin.restype = C.c_int64
+    L.rtoh_rt_centreline.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rtoh_rt_centreline.restype = C.c_int
     L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
     L.rtoh_rt_geodesic_field.restype = C.c_int
     L.rtoh_thickness_cpu.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]
@@ -360,6 +372,24 @@ class VoxelGrid:
         code (negative, the grid untouched)."""
         s = np.ascontiguousarray(np.asarray(seeds).reshape(-1), np.int64)
         return int(load().rtoh_geodesic_flood_cpu(self._h, int(medium), int(connectivity), s.ctypes.data if s.size else None, s.size, int(limit)))
+
+    def skeletonField(self, set: int = 1, connectivity: int = 26, mode: int = 0, anchors=(), maxPasses: int = 0x7fffffff):
+        """Addition: skeletonFieldCPU (host/Skeleton.h) -- the rule of rto_skeleton_field on the CPU: (code, k int32 (dimZ, dimY, dimX)
+        or None when refused, summary as a hip.SKEL_SUMMARY_DTYPE scalar)."""
+        dx, dy, dz = self.dims
+        a = np.ascontiguousarray(np.asarray(anchors).reshape(-1), np.int64)
+        k = np.empty((dz, dy, dx), np.int32)
+        summary = np.zeros((), SKEL_SUMMARY_DTYPE)
+        rc = int(load().rtoh_skeleton_cpu(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
+                                          int(maxPasses), k.ctypes.data, summary.ctypes.data))
+        return rc, (k if rc == 0 else None), summary
+
+    def thin(self, set: int = 1, connectivity: int = 26, mode: int = 0, anchors=(), maxPasses: int = 0x7fffffff) -> int:
+        """Addition: thinCPU -- rto_edit_skeleton on this grid, on the CPU; the number of voxels flipped, or the refusal's code
+        (negative, the grid untouched)."""
+        a = np.ascontiguousarray(np.asarray(anchors).reshape(-1), np.int64)
+        return int(load().rtoh_skeleton_thin_cpu(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
+                                                 int(maxPasses)))
 
 
 def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
@@ -826,6 +856,31 @@ class RayTracerBVH:
         rc = int(load().rtoh_rt_geodesic_field(self._h, s.ctypes.data if s.size else None, s.size, int(medium), int(connectivity), int(limit),
                                                g.ctypes.data, g.size, summary.ctypes.data))
         return rc, (g if rc == 0 else None), summary
+
+    def skeletonField(self, set: int = 1, connectivity: int = 26, mode: int = 0, anchors=(), maxPasses: int = 0x7fffffff):
+        """Addition: RayTracerBVH::skeletonField -- (code, k int32 (dimZ, dimY, dimX), summary as a hip.SKEL_SUMMARY_DTYPE scalar);
+        code is RTO_OK or the refusal's (lastError), and k is then None."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        a = np.ascontiguousarray(np.asarray(anchors).reshape(-1), np.int64)
+        k = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        summary = np.zeros((), SKEL_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_skeleton_field(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
+                                               int(maxPasses), k.ctypes.data, k.size, summary.ctypes.data))
+        return rc, (k if rc == 0 else None), summary
+
+    def thin(self, mode: int = 1, maxPasses: int = 0x7fffffff) -> int:
+        """Addition: RayTracerBVH::thin -- replaces the solid by its skeleton; voxels removed, or the refusal's code (negative)."""
+        return int(load().rtoh_rt_thin(self._h, int(mode), int(maxPasses)))
+
+    def centreline(self, anchorA: int, anchorB: int):
+        """Addition: RayTracerBVH::centreline -- (code, the int64 linear indices left of the free space with both anchors held)."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        out = np.empty(max(dims[0] * dims[1] * dims[2], 1), np.int64)
+        count = C.c_int64()
+        rc = int(load().rtoh_rt_centreline(self._h, int(anchorA), int(anchorB), out.ctypes.data, out.size, C.byref(count)))
+        return rc, (out[:count.value].copy() if rc == 0 else None)
 
     def pathsTo(self, targets, maxLen: int):
         """Addition: RayTracerBVH::pathsTo -- the routes of the last geodesicField: (code, rows (n, maxLen) int64 with -1 behind each

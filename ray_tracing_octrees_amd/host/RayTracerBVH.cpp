@@ -66,6 +66,9 @@ struct HipApi {
     decltype(&rto_download_geodesic) download_geodesic = nullptr;
     decltype(&rto_geodesic_paths) geodesic_paths = nullptr;
     decltype(&rto_edit_geodesic) edit_geodesic = nullptr;
+    decltype(&rto_skeleton_field) skeleton_field = nullptr;
+    decltype(&rto_download_skeleton) download_skeleton = nullptr;
+    decltype(&rto_edit_skeleton) edit_skeleton = nullptr;
     decltype(&rto_thickness_field) thickness_field = nullptr;
     decltype(&rto_download_thickness) download_thickness = nullptr;
     decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
@@ -147,6 +150,9 @@ struct HipApi {
         download_geodesic = reinterpret_cast<decltype(download_geodesic)>(sym("rto_download_geodesic"));
         geodesic_paths = reinterpret_cast<decltype(geodesic_paths)>(sym("rto_geodesic_paths"));
         edit_geodesic = reinterpret_cast<decltype(edit_geodesic)>(sym("rto_edit_geodesic"));
+        skeleton_field = reinterpret_cast<decltype(skeleton_field)>(sym("rto_skeleton_field"));
+        download_skeleton = reinterpret_cast<decltype(download_skeleton)>(sym("rto_download_skeleton"));
+        edit_skeleton = reinterpret_cast<decltype(edit_skeleton)>(sym("rto_edit_skeleton"));
         thickness_field = reinterpret_cast<decltype(thickness_field)>(sym("rto_thickness_field"));
         download_thickness = reinterpret_cast<decltype(download_thickness)>(sym("rto_download_thickness"));
         thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
@@ -1011,6 +1017,62 @@ int RayTracerBVH::farthestPoint(const std::vector<int64_t>& seeds, int medium, i
     out.voxel = s.argmax;
     out.g = s.max_g;
     out.reached = s.reached;
+    return RTO_OK;
+}
+
+// The skeleton field of the first GPU's resident grid (rto_skeleton_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::skeletonField(int set, int connectivity, int mode, const std::vector<int64_t>& anchors, int64_t maxPasses, std::vector<int32_t>* k,
+                                rto_skel_summary* summary) {
+    if (k) k->clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "skeletonField: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("skeleton field")) return RTO_E_HIP;
+    int rc = api().skeleton_field(m_ctx, set, connectivity, mode, anchors.empty() ? nullptr : anchors.data(), (int64_t)anchors.size(), maxPasses, summary);
+    if (rc == RTO_OK && k) {
+        k->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+        rc = api().download_skeleton(m_ctx, k->data(), (int64_t)k->size());
+        if (rc != RTO_OK) k->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, "skeletonField");
+    return RTO_OK;
+}
+
+// rto_edit_skeleton of the solid under RTO_CONN_FULL on every GPU: the number of voxels removed, or the refusal's code (negative).
+int64_t RayTracerBVH::thin(int mode, int64_t maxPasses) {
+    m_lastEditChanged = -1;
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "thin: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("thin")) return RTO_E_HIP;
+    int64_t changed = 0;
+    for (rto_context* c : m_ctxs) {
+        const int rc = api().edit_skeleton(c, RTO_SET_SOLID, RTO_CONN_FULL, mode, nullptr, 0, maxPasses, c == m_ctx ? &changed : nullptr);
+        if (rc != RTO_OK) {
+            m_lastError = api().last_error(c);
+            std::cerr << "[RayTracerBVH] thin failed: " << m_lastError << std::endl;
+            return rc;
+        }
+    }
+    m_lastEditChanged = changed;
+    if (changed > 0) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+        m_gridStale = true;
+    }
+    return changed;
+}
+
+// What the thinning of the free space leaves when the two anchors are held (the grid stays as it is).
+int RayTracerBVH::centreline(int64_t anchorA, int64_t anchorB, std::vector<int64_t>& voxels) {
+    voxels.clear();
+    std::vector<int32_t> k;
+    const int rc = skeletonField(RTO_SET_EMPTY, RTO_CONN_FULL, RTO_SKEL_TOPOLOGY, { anchorA, anchorB }, RTO_SKEL_NO_LIMIT, &k);
+    if (rc != RTO_OK) return rc;
+    for (size_t v = 0; v < k.size(); v++)
+        if (k[v] == 0) voxels.push_back((int64_t)v);
     return RTO_OK;
 }
 

@@ -252,6 +252,19 @@ public:
     int thicknessField(int medium, float maxRadius, std::vector<int32_t>* t2, rto_thick_summary* summary = nullptr);
     int thinnestPoint(int medium, float maxRadius, ThinnestPoint& out);
     int thicknessHistogram(std::vector<int64_t>& bins);
+    // Skeletons of the resident grid (rto_skeleton_field / rto_edit_skeleton).  skeletonField thins `set` on the
+    // first GPU under `connectivity` and `mode` (RTO_SKEL_TOPOLOGY / RTO_SKEL_CURVE): one int32 per voxel, x fastest, -1 outside
+    // the set, 0 for the skeleton, p >= 1 for the pass that removed the voxel; `anchors` (linear voxel indices) are never removed;
+    // k and summary may be null.  thin replaces the solid by its skeleton under RTO_CONN_FULL on every GPU and rebuilds as
+    // editVoxels does: the number of voxels removed (lastEditChanged() too).  centreline gives the voxels, in ascending index order,
+    // that are left of the free space under RTO_CONN_FULL and RTO_SKEL_TOPOLOGY with the two anchors held: in a simply connected
+    // space the centred curve from one to the other (a space with tunnels keeps its loops as well); the grid is not edited.
+    // Each returns RTO_OK or the refusal's code, which is negative (lastError).  They need the compute pipeline; the CPU form of the
+    // same rule for a VoxelGrid is host/Skeleton.h.
+    int skeletonField(int set, int connectivity, int mode, const std::vector<int64_t>& anchors, int64_t maxPasses, std::vector<int32_t>* k,
+                      rto_skel_summary* summary = nullptr);
+    int64_t thin(int mode = RTO_SKEL_CURVE, int64_t maxPasses = RTO_SKEL_NO_LIMIT);
+    int centreline(int64_t anchorA, int64_t anchorB, std::vector<int64_t>& voxels);
     // Component measures of the resident grid (rto_measure_components).  measureComponents labels `set` under
     // `connectivity` on the first GPU and measures every component: one rto_measure per component in the table's order (exposed
     // faces by direction, cell counts, Euler number, first and second moments of the voxel indices) and their sum; table and total

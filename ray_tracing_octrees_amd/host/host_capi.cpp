@@ -13,6 +13,7 @@
 #include "Components.h"
 #include "Distance.h"
 #include "Geodesic.h"
+#include "Skeleton.h"
 #include "Thickness.h"
 #include "Measure.h"
 #include "Camera.h"
@@ -449,6 +450,40 @@ int rtoh_rt_topology(RayTracerBVH* rt, int set, int connectivity, int64_t out[3]
     const int rc = rt->topology(set, connectivity, t);
     out[0] = t.pieces; out[1] = t.tunnels; out[2] = t.cavities;
     return rc;
+}
+// Skeletons.  rtoh_skeleton_cpu: the CPU form of the rule (Skeleton.h) on a grid: k (dims product int32) and summary may be NULL; the
+// code of rto_skeleton_field.  rtoh_skeleton_thin_cpu edits the grid in place (the number flipped, or the refusal's code);
+// rtoh_skeleton_simple is the simple-point test of one 27-bit block.
+int rtoh_skeleton_cpu(const VoxelGrid* g, int set, int connectivity, int mode, const int64_t* anchors, int64_t n, int64_t maxPasses, int32_t* out,
+                      rto_skel_summary* summary) {
+    std::vector<int32_t> k;
+    const int rc = skeletonFieldCPU(*g, set, connectivity, mode, anchors, n, maxPasses, k, summary);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(k.begin(), k.end(), out);
+    return RTO_OK;
+}
+int64_t rtoh_skeleton_thin_cpu(VoxelGrid* g, int set, int connectivity, int mode, const int64_t* anchors, int64_t n, int64_t maxPasses) {
+    return thinCPU(*g, set, connectivity, mode, anchors, n, maxPasses);
+}
+int rtoh_skeleton_simple(uint32_t mask, int connectivity) { return skeletonSimpleCPU(mask, connectivity) ? 1 : 0; }
+// RayTracerBVH::skeletonField / thin / centreline: the class's codes; centreline: *count = the voxels there are, out filled up to
+// capacity.
+int rtoh_rt_skeleton_field(RayTracerBVH* rt, int set, int connectivity, int mode, const int64_t* anchors, int64_t n, int64_t maxPasses, int32_t* k,
+                           int64_t capacity, rto_skel_summary* summary) {
+    std::vector<int32_t> f;
+    const int rc = rt->skeletonField(set, connectivity, mode, std::vector<int64_t>(anchors, anchors + (n > 0 ? n : 0)), maxPasses, k ? &f : nullptr, summary);
+    if (rc != RTO_OK) return rc;
+    if (k) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), k);
+    return RTO_OK;
+}
+int64_t rtoh_rt_thin(RayTracerBVH* rt, int mode, int64_t maxPasses) { return rt->thin(mode, maxPasses); }
+int rtoh_rt_centreline(RayTracerBVH* rt, int64_t a, int64_t b, int64_t* out, int64_t capacity, int64_t* count) {
+    std::vector<int64_t> v;
+    const int rc = rt->centreline(a, b, v);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(v.begin(), v.begin() + (size_t)std::min<int64_t>((int64_t)v.size(), capacity), out);
+    if (count) *count = (int64_t)v.size();
+    return RTO_OK;
 }
 // Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
 // NULL; the code of rto_geodesic_field.  rtoh_geodesic_paths_cpu walks a field of that grid; rtoh_geodesic_flood_cpu edits the grid
