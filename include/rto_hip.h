@@ -1195,6 +1195,60 @@ int  rto_debug_skeleton_passes(const rto_context* ctx, int64_t* launches, int64_
  * fixed point remove nothing, so no value of any field or edit depends on it. */
 int  rto_debug_set_skeleton_look(rto_context* ctx, int passes_per_look);
 
+/* ---- exposure fields: sun hours and sky view per voxel --------------------------
+ * Which air voxels see the sun at these hours, how much of the sky does each see, which stay dark: for every evaluated EMPTY voxel
+ * the sum of the weights of the directions along which nothing of the grid stands in the way.  Directional and independent of any
+ * camera; exact in integers.  No reference counterpart.  Every result is an integer that a plain loop over rto_download_voxels
+ * reproduces bit for bit.
+ *
+ * Rule:
+ *   index     voxel p = (i, j, k) has linear index v = i + dimX (j + dimY k); SOLID the voxels equal to 1, EMPTY the voxels equal
+ *             to 0.  Voxels outside the grid do not exist: they block nothing, and beyond the grid is open sky.
+ *   direction d = (a, b, c), three int32, not all zero, every |component| <= RTO_EXPO_MAX_COMP.  Only the line matters: d and g d
+ *             give the same result.
+ *   ray       the open half line centre(p) + t d, t > 0.  In doubled integer coordinates the centre is P = 2 p + 1 and voxel q is
+ *             the open cube (2 q, 2 q + 2)^3.
+ *   crossed   a voxel q != p is crossed when the ray meets q's open cube: there is a t > 0 with P + t d strictly inside on all
+ *             three axes.  A ray through an edge or a corner crosses neither of the cubes it only touches: from p, direction
+ *             (1, 1, 0) crosses p + (1, 1, 0), but neither p + (1, 0, 0) nor p + (0, 1, 0).
+ *   reach     r >= 1, in voxels: only crossed voxels with max-norm |q - p| <= r can block.  RTO_EXPO_NO_LIMIT or more: no limit;
+ *             below 1 is RTO_E_INVALID.
+ *   blocked   (p, d) is blocked when some crossed voxel inside the grid and within reach is SOLID.
+ *   weights   n int32 weights w_d >= 0 (hours, cosine weights of a sky dome, irradiance), or NULL for all ones; their sum W must
+ *             be <= 2^31 - 1.  A direction given twice counts twice.
+ *   evaluated RTO_EXPO_ALL: every EMPTY voxel.  RTO_EXPO_SKIN: the EMPTY voxels with at least one SOLID voxel among their 6 face
+ *             neighbours: the air voxel in front of every exposed face, where a facade's exposure is read.
+ *   field     e[v] as int32: for an evaluated voxel the sum of w_d over the directions that are not blocked; -1 for every other.
+ *   summary   evaluated; total, the sum of e over the evaluated voxels; dark, those with e == 0; open, those with e == W.  With
+ *             nothing evaluated: 0, 0, 0, 0.
+ * rto_exposure_field keeps the volume (int32 per voxel) resident beside the other fields, with its n, W, mode and reach; every call
+ * that changes or replaces the grid frees it as it frees them, and the readers then return RTO_E_INVALID.  Synchronous on the
+ * context's stream.
+ * Errors, in rto_geodesic_field's order, each leaving the context untouched: RTO_E_INVALID (NULL dirs; n below 1 or above
+ * RTO_EXPO_MAX_DIRS; a zero direction or a component beyond +-255; a negative weight or W above 2^31 - 1; unknown mode; reach below
+ * 1; too small a capacity; no resident exposure field, for the readers); RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the
+ * octree came from rto_upload_octree: no resident grid; more than 2^31 - 2 voxels). */
+#define RTO_EXPO_ALL      0
+#define RTO_EXPO_SKIN     1
+#define RTO_EXPO_MAX_COMP 255
+#define RTO_EXPO_MAX_DIRS 1024
+#define RTO_EXPO_NO_LIMIT 0x7fffffff
+typedef struct rto_expo_summary {   /* 32 bytes */
+    int64_t evaluated;              /* voxels with e >= 0 */
+    int64_t total;                  /* the sum of e over them */
+    int64_t dark;                   /* evaluated voxels with e == 0 */
+    int64_t open;                   /* evaluated voxels with e == W */
+} rto_expo_summary;
+
+int  rto_exposure_field(rto_context* ctx, const int32_t* dirs /* n x 3 */, const int32_t* weights /* n, may be NULL */, int n,
+                        int mode, int reach, rto_expo_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_exposure(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed). */
+int  rto_exposure_device(rto_context* ctx, int32_t** d_e);
+/* Device time in ms of the last rto_exposure_field: prepare (bit rows, selection, templates), march, summary (-1: not run). */
+int  rto_last_exposure_ms(const rto_context* ctx, float ms[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

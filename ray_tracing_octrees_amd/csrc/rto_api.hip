@@ -214,6 +214,13 @@ struct rto_context {
     int skelLook = 8;                         // passes per look at the device (rto_debug_set_skeleton_look): changes no value
     float skelMs[3] = { -1.f, -1.f, -1.f };   // the last rto_skeleton_field: init, thinning, summary
     float skelEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_skeleton: field and flip, octree rebuild, triangle rebuild
+
+    // exposure fields (rto_exposure.inc): the last field of the resident grid, with the directions, weight sum, mode and reach it
+    // was made for; dropped whenever the grid changes
+    int* d_expo = nullptr;                    // nullptr: no field resident
+    int expoN = 0, expoMode = 0, expoReach = 0;
+    int64_t expoW = 0;
+    float expoMs[3] = { -1.f, -1.f, -1.f };   // the last rto_exposure_field: prepare, march, summary
 };
 
 static thread_local std::string g_createError;
@@ -283,6 +290,9 @@ static void free_thickness(rto_context* c) { (void)hipFree(c->d_thick); c->d_thi
 // The resident skeleton field (rto_skeleton.inc): it describes one state of the grid.
 static void free_skeleton(rto_context* c) { (void)hipFree(c->d_skel); c->d_skel = nullptr; }
 
+// The resident exposure field (rto_exposure.inc): it describes one state of the grid.
+static void free_exposure(rto_context* c) { (void)hipFree(c->d_expo); c->d_expo = nullptr; }
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
@@ -290,6 +300,7 @@ static void free_octree_arrays(rto_context* c) {
     free_geodesic(c);
     free_thickness(c);
     free_skeleton(c);
+    free_exposure(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -2884,3 +2895,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_thickness.inc"
 #include "rto_measure.inc"
 #include "rto_skeleton.inc"
+#include "rto_exposure.inc"

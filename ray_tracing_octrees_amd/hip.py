@@ -54,6 +54,7 @@ SYMBOLS = (
     "rto_last_geodesic_ms", "rto_last_geodesic_edit_ms", "rto_debug_geodesic_passes", "rto_debug_set_geodesic_look",
     "rto_skeleton_field", "rto_download_skeleton", "rto_skeleton_device", "rto_edit_skeleton", "rto_last_skeleton_ms",
     "rto_last_skeleton_edit_ms", "rto_debug_skeleton_passes", "rto_debug_set_skeleton_look",
+    "rto_exposure_field", "rto_download_exposure", "rto_exposure_device", "rto_last_exposure_ms",
     "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
     "rto_debug_thickness_table",
     "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
@@ -102,6 +103,12 @@ GEO_NO_LIMIT = 0x7fffffff
 SKEL_SUMMARY_DTYPE = np.dtype([("kept", "<i8"), ("removed", "<i8"), ("passes", "<i8"), ("reserved", "<i8")])
 SKEL_TOPOLOGY, SKEL_CURVE = 0, 1
 SKEL_NO_LIMIT = 0x7fffffff
+# struct rto_expo_summary, 32 bytes: exposure fields (rto_exposure_field)
+EXPO_SUMMARY_DTYPE = np.dtype([("evaluated", "<i8"), ("total", "<i8"), ("dark", "<i8"), ("open", "<i8")])
+EXPO_ALL, EXPO_SKIN = 0, 1
+EXPO_MAX_COMP = 255      # RTO_EXPO_MAX_COMP: the largest |component| of a direction
+EXPO_MAX_DIRS = 1024     # RTO_EXPO_MAX_DIRS
+EXPO_NO_LIMIT = 0x7fffffff
 # struct rto_thick_summary, 32 bytes: local thickness fields (rto_thickness_field)
 THICK_SUMMARY_DTYPE = np.dtype([("min_t2", "<i8"), ("argmin", "<i8"), ("thin", "<i8"), ("medium", "<i8")])
 THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
@@ -135,6 +142,21 @@ def measure_physical(m, grid_min, voxel_size):
     axes = np.where(ok[..., None, None], axes, np.nan)
     return {"volume": n * vs ** 3, "area": m["faces"].sum(axis=-1).astype(np.float64) * vs * vs, "centroid": gm + (mean + 0.5) * vs,
             "covariance": cov, "axes_variance": var, "axes": axes}
+
+
+def quantize_directions(float_dirs, max_comp: int = EXPO_MAX_COMP) -> np.ndarray:
+    """Integer directions for Context.exposure_field from float vectors (n, 3), as (n, 3) int32: each vector is scaled so that its
+    largest |component| is max_comp, rounded to nearest (numpy.rint) and divided by the gcd of its components.  A zero or
+    non-finite vector is refused (ValueError), and so is a max_comp outside 1 .. EXPO_MAX_COMP."""
+    if not 1 <= int(max_comp) <= EXPO_MAX_COMP:
+        raise ValueError("max_comp must be in 1 .. EXPO_MAX_COMP")
+    d = np.asarray(float_dirs, np.float64).reshape(-1, 3)
+    top = np.abs(d).max(axis=1) if len(d) else np.empty(0)
+    if not np.isfinite(d).all() or (top == 0).any():
+        raise ValueError("a direction is zero or not finite")
+    q = np.rint(d / top[:, None] * int(max_comp)).astype(np.int64)
+    g = np.gcd.reduce(np.abs(q), axis=1)
+    return np.ascontiguousarray(q // g[:, None], np.int32)
 
 
 class RtoError(RuntimeError):
@@ -494,6 +516,10 @@ def load():
     L.rto_last_skeleton_edit_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_skeleton_passes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.rto_debug_set_skeleton_look.argtypes = [vp, C.c_int]
+    L.rto_exposure_field.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.rto_download_exposure.argtypes = [vp, vp, C.c_int64]
+    L.rto_exposure_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_last_exposure_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_thickness_field.argtypes = [vp, C.c_int, C.c_float, vp]
     L.rto_download_thickness.argtypes = [vp, vp, C.c_int64]
     L.rto_thickness_device.argtypes = [vp, C.POINTER(vp)]
@@ -1291,6 +1317,51 @@ class Context:
     def debug_set_skeleton_look(self, passes_per_look: int) -> None:
         """How many passes go out between two looks at the device (1 .. 64): changes no value."""
         self._check(self._L.rto_debug_set_skeleton_look(self._h, int(passes_per_look)))
+
+    # -- exposure fields: sun hours and sky view per voxel -------------------------------
+    def exposure_field(self, dirs, weights=None, mode: int = EXPO_SKIN, reach=None):
+        """rto_exposure_field: (the int32 (dimZ, dimY, dimX) volume e: for every evaluated EMPTY voxel (EXPO_ALL: all of them;
+        EXPO_SKIN: those with a SOLID face neighbour) the sum of the weights of the directions along which no SOLID voxel is crossed
+        within `reach` voxels, -1 for every other voxel; the summary as an EXPO_SUMMARY_DTYPE scalar).  `dirs` is (n, 3) integers
+        (quantize_directions makes them from floats), `weights` n non-negative integers or None for ones; reach None: no limit.
+        The field stays resident until the grid changes."""
+        d = np.ascontiguousarray(np.asarray(dirs, np.int64).reshape(-1, 3))
+        if d.size and (np.abs(d) > 0x7fffffff).any():
+            raise ValueError("a direction's component does not fit int32")
+        d = np.ascontiguousarray(d, np.int32)
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, np.int64).reshape(-1)
+            if w.size != len(d):
+                raise ValueError("one weight per direction")
+            if w.size and (np.abs(w) > 0x7fffffff).any():
+                raise ValueError("a weight does not fit int32")
+            w = np.ascontiguousarray(w, np.int32)
+        summary = np.zeros((), EXPO_SUMMARY_DTYPE)
+        self._check(self._L.rto_exposure_field(self._h, d.ctypes.data if d.size else None, None if w is None else w.ctypes.data, len(d),
+                                               int(mode), EXPO_NO_LIMIT if reach is None else int(reach), summary.ctypes.data))
+        return self.exposure(), summary
+
+    def exposure(self) -> np.ndarray:
+        """The resident exposure field (rto_download_exposure)."""
+        self._check(self._L.rto_exposure_device(self._h, None))             # no field resident: that error, before the dims are asked for
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(self._L.rto_download_exposure(self._h, out.ctypes.data, out.size))
+        return out
+
+    def exposure_device(self) -> int:
+        """The device pointer of the resident int32 exposure field."""
+        p = C.c_void_p()
+        self._check(self._L.rto_exposure_device(self._h, C.byref(p)))
+        return p.value or 0
+
+    def last_exposure_ms(self):
+        """Device ms of the last exposure_field: (prepare, march, summary); -1: not run."""
+        ms = (C.c_float * 3)()
+        self._check(self._L.rto_last_exposure_ms(self._h, ms))
+        return tuple(ms)
 
     # -- local thickness fields ----------------------------------------------------------
     def thickness_field(self, medium: int = SET_SOLID, max_radius: float | None = None):

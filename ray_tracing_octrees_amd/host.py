@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
@@ -186,6 +186,12 @@ def load():
     L.rtoh_rt_thin.restype = C.c_int64
     L.rtoh_rt_centreline.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64)]
     L.rtoh_rt_centreline.restype = C.c_int
+    L.rtoh_exposure_cpu.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int64)]
+    L.rtoh_exposure_cpu.restype = C.c_int
+    L.rtoh_rt_exposure_field.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]
+    L.rtoh_rt_exposure_field.restype = C.c_int
+    L.rtoh_rt_exposure.argtypes = [_vp, _vp, C.c_int64]
+    L.rtoh_rt_exposure.restype = C.c_int
     L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
     L.rtoh_rt_geodesic_field.restype = C.c_int
     L.rtoh_thickness_cpu.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]
@@ -390,6 +396,29 @@ class VoxelGrid:
         a = np.ascontiguousarray(np.asarray(anchors).reshape(-1), np.int64)
         return int(load().rtoh_skeleton_thin_cpu(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
                                                  int(maxPasses)))
+
+    def exposureField(self, dirs, weights=None, mode: int = 1, reach: int = 0x7fffffff, withSteps: bool = False):
+        """Addition: exposureFieldCPU (host/Exposure.h) -- the rule of rto_exposure_field on the CPU: (code, e int32 (dimZ, dimY, dimX)
+        or None when refused, summary as a hip.EXPO_SUMMARY_DTYPE scalar), and with withSteps the template entries tested as a
+        fourth value.  `dirs` None stands for the NULL pointer."""
+        dx, dy, dz = self.dims
+        d, w = _expo_args(dirs, weights)
+        e = np.empty((dz, dy, dx), np.int32)
+        summary = np.zeros((), EXPO_SUMMARY_DTYPE)
+        steps = C.c_int64()
+        rc = int(load().rtoh_exposure_cpu(self._h, None if d is None else d.ctypes.data, None if w is None else w.ctypes.data,
+                                          0 if d is None else len(d), int(mode), int(reach), e.ctypes.data, summary.ctypes.data, C.byref(steps)))
+        out = (rc, (e if rc == 0 else None), summary)
+        return out + (steps.value,) if withSteps else out
+
+
+def _expo_args(dirs, weights):
+    """(dirs as contiguous (n, 3) int32 or None, weights as contiguous int32 or None) for the exposure entry points."""
+    d = None if dirs is None else np.ascontiguousarray(np.asarray(dirs, np.int32).reshape(-1, 3))
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.int32).reshape(-1))
+    if d is not None and w is not None and len(w) != len(d):
+        raise ValueError("one weight per direction")
+    return d, w
 
 
 def loadCSVDataIntoVoxelGrid(vertsFilename: str, facesFilename: str, voxelSize: float = 5.0) -> VoxelGrid:
@@ -868,6 +897,23 @@ class RayTracerBVH:
         rc = int(load().rtoh_rt_skeleton_field(self._h, int(set), int(connectivity), int(mode), a.ctypes.data if a.size else None, a.size,
                                                int(maxPasses), k.ctypes.data, k.size, summary.ctypes.data))
         return rc, (k if rc == 0 else None), summary
+
+    def exposureField(self, dirs, weights=None, mode: int = 1, reach: int = 0x7fffffff):
+        """Addition: RayTracerBVH::exposureField -- (code, summary as a hip.EXPO_SUMMARY_DTYPE scalar); code is RTO_OK or the
+        refusal's (lastError).  The field stays resident: exposure() downloads it."""
+        d, w = _expo_args(dirs, weights)
+        summary = np.zeros((), EXPO_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_exposure_field(self._h, None if d is None else d.ctypes.data, None if w is None else w.ctypes.data,
+                                               0 if d is None else len(d), int(mode), int(reach), summary.ctypes.data))
+        return rc, summary
+
+    def exposure(self):
+        """Addition: RayTracerBVH::exposure -- (code, e int32 (dimZ, dimY, dimX) or None when there is no resident field)."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        e = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        rc = int(load().rtoh_rt_exposure(self._h, e.ctypes.data, e.size))
+        return rc, (e if rc == 0 else None)
 
     def thin(self, mode: int = 1, maxPasses: int = 0x7fffffff) -> int:
         """Addition: RayTracerBVH::thin -- replaces the solid by its skeleton; voxels removed, or the refusal's code (negative)."""

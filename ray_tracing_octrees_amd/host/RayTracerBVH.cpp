@@ -69,6 +69,8 @@ struct HipApi {
     decltype(&rto_skeleton_field) skeleton_field = nullptr;
     decltype(&rto_download_skeleton) download_skeleton = nullptr;
     decltype(&rto_edit_skeleton) edit_skeleton = nullptr;
+    decltype(&rto_exposure_field) exposure_field = nullptr;
+    decltype(&rto_download_exposure) download_exposure = nullptr;
     decltype(&rto_thickness_field) thickness_field = nullptr;
     decltype(&rto_download_thickness) download_thickness = nullptr;
     decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
@@ -153,6 +155,8 @@ struct HipApi {
         skeleton_field = reinterpret_cast<decltype(skeleton_field)>(sym("rto_skeleton_field"));
         download_skeleton = reinterpret_cast<decltype(download_skeleton)>(sym("rto_download_skeleton"));
         edit_skeleton = reinterpret_cast<decltype(edit_skeleton)>(sym("rto_edit_skeleton"));
+        exposure_field = reinterpret_cast<decltype(exposure_field)>(sym("rto_exposure_field"));
+        download_exposure = reinterpret_cast<decltype(download_exposure)>(sym("rto_download_exposure"));
         thickness_field = reinterpret_cast<decltype(thickness_field)>(sym("rto_thickness_field"));
         download_thickness = reinterpret_cast<decltype(download_thickness)>(sym("rto_download_thickness"));
         thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
@@ -1073,6 +1077,36 @@ int RayTracerBVH::centreline(int64_t anchorA, int64_t anchorB, std::vector<int64
     if (rc != RTO_OK) return rc;
     for (size_t v = 0; v < k.size(); v++)
         if (k[v] == 0) voxels.push_back((int64_t)v);
+    return RTO_OK;
+}
+
+// The exposure field of the first GPU's resident grid (rto_exposure_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::exposureField(const std::vector<int32_t>& dirs, const std::vector<int32_t>& weights, int mode, int reach, rto_expo_summary* summary) {
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "exposureField: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    if (dirs.size() % 3 != 0 || (!weights.empty() && weights.size() != dirs.size() / 3)) {
+        m_lastError = "exposureField: three components a direction, and one weight a direction or none";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("exposure field")) return RTO_E_HIP;
+    const int rc = api().exposure_field(m_ctx, dirs.empty() ? nullptr : dirs.data(), weights.empty() ? nullptr : weights.data(), (int)(dirs.size() / 3),
+                                        mode, reach, summary);
+    if (rc != RTO_OK) return regionFailed(rc, "exposureField");
+    return RTO_OK;
+}
+
+// The resident exposure field, downloaded.
+int RayTracerBVH::exposure(std::vector<int32_t>& e) {
+    e.clear();
+    if (!m_computeInited || !m_computeOk) {
+        m_lastError = "exposure: compute pipeline not initialized or failed";
+        return RTO_E_INVALID;
+    }
+    e.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+    const int rc = api().download_exposure(m_ctx, e.data(), (int64_t)e.size());
+    if (rc != RTO_OK) { e.clear(); return regionFailed(rc, "exposure"); }
     return RTO_OK;
 }
 

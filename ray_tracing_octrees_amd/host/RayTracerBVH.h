@@ -265,6 +265,17 @@ public:
                       rto_skel_summary* summary = nullptr);
     int64_t thin(int mode = RTO_SKEL_CURVE, int64_t maxPasses = RTO_SKEL_NO_LIMIT);
     int centreline(int64_t anchorA, int64_t anchorB, std::vector<int64_t>& voxels);
+    // Exposure fields of the resident grid (rto_exposure_field).  exposureField makes, on the first GPU, for
+    // every evaluated EMPTY voxel (RTO_EXPO_ALL: all of them; RTO_EXPO_SKIN: those with a SOLID face neighbour) the sum of the
+    // weights of the directions along which the ray from the voxel's centre crosses no SOLID voxel within `reach` voxels
+    // (RTO_EXPO_NO_LIMIT: none): `dirs` holds three int32 a direction, `weights` one a direction or nothing for all ones; the
+    // summary (may be null) gives the evaluated voxels, the sum, the dark and the fully open ones without a download.  exposure
+    // downloads the resident field: one int32 per voxel, x fastest, -1 for a voxel that is not evaluated.  Each returns RTO_OK or
+    // the refusal's code, which is negative (lastError).  They need the compute pipeline; the CPU form of the same rule for a
+    // VoxelGrid is host/Exposure.h.
+    int exposureField(const std::vector<int32_t>& dirs, const std::vector<int32_t>& weights, int mode = RTO_EXPO_SKIN, int reach = RTO_EXPO_NO_LIMIT,
+                      rto_expo_summary* summary = nullptr);
+    int exposure(std::vector<int32_t>& e);
     // Component measures of the resident grid (rto_measure_components).  measureComponents labels `set` under
     // `connectivity` on the first GPU and measures every component: one rto_measure per component in the table's order (exposed
     // faces by direction, cell counts, Euler number, first and second moments of the voxel indices) and their sum; table and total

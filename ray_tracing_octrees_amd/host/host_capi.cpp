@@ -14,6 +14,7 @@
 #include "Distance.h"
 #include "Geodesic.h"
 #include "Skeleton.h"
+#include "Exposure.h"
 #include "Thickness.h"
 #include "Measure.h"
 #include "Camera.h"
@@ -483,6 +484,29 @@ int rtoh_rt_centreline(RayTracerBVH* rt, int64_t a, int64_t b, int64_t* out, int
     if (rc != RTO_OK) return rc;
     if (out) std::copy(v.begin(), v.begin() + (size_t)std::min<int64_t>((int64_t)v.size(), capacity), out);
     if (count) *count = (int64_t)v.size();
+    return RTO_OK;
+}
+// Exposure fields.  rtoh_exposure_cpu: the CPU form of the rule (Exposure.h) on a grid: e (dims product int32), summary and steps
+// may be NULL; the code of rto_exposure_field.  rtoh_rt_exposure_field / rtoh_rt_exposure: RayTracerBVH::exposureField / exposure,
+// the class's codes; e is filled up to capacity.
+int rtoh_exposure_cpu(const VoxelGrid* g, const int32_t* dirs, const int32_t* weights, int n, int mode, int reach, int32_t* out,
+                      rto_expo_summary* summary, int64_t* steps) {
+    std::vector<int32_t> e;
+    const int rc = exposureFieldCPU(*g, dirs, weights, n, mode, reach, e, summary, steps);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(e.begin(), e.end(), out);
+    return RTO_OK;
+}
+int rtoh_rt_exposure_field(RayTracerBVH* rt, const int32_t* dirs, const int32_t* weights, int n, int mode, int reach, rto_expo_summary* summary) {
+    const size_t count = dirs && n > 0 ? (size_t)n : 0;
+    return rt->exposureField(std::vector<int32_t>(dirs, dirs + 3 * count), weights ? std::vector<int32_t>(weights, weights + count) : std::vector<int32_t>(),
+                             mode, reach, summary);
+}
+int rtoh_rt_exposure(RayTracerBVH* rt, int32_t* e, int64_t capacity) {
+    std::vector<int32_t> f;
+    const int rc = rt->exposure(f);
+    if (rc != RTO_OK) return rc;
+    if (e) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), e);
     return RTO_OK;
 }
 // Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
