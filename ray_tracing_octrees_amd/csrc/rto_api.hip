@@ -21,6 +21,10 @@ static int lean_block(int path);
 using namespace rto;
 namespace rto { struct CcComp; }   // rto_components.inc
 
+// The resident voxel fields of a context (rto_context::d_field) and the noun each goes by in error texts.
+enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldCount };
+static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure" };
+
 struct rto_context {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -181,23 +185,25 @@ struct rto_context {
     rto_measure* d_ccMeasures = nullptr;      // nullptr: no measures resident; count records, then the total
     float measureMs[2] = { -1.f, -1.f };      // the last rto_measure_components: the measuring kernels, the total
 
-    // distance fields (rto_distance.inc): the last field of the resident grid; dropped whenever the grid changes
-    int* d_dist = nullptr;                    // nullptr: no field resident
+    // resident voxel fields: the last distance, geodesic, thickness, skeleton and exposure field of the resident grid, one int32 per
+    // voxel each (nullptr: none resident).  A maker owns its new field as a FieldDraft until the call has succeeded; all five are
+    // dropped whenever the grid changes (free_fields).  What a field was made for, and the times of its maker, are kept per family below.
+    int* d_field[kFieldCount] = {};
+
+    // distance fields (rto_distance.inc)
     float distMs[4] = { -1.f, -1.f, -1.f, -1.f };
     float morphMs[3] = { -1.f, -1.f, -1.f };  // the last rto_edit_morphology: transforms and flips, octree rebuild, triangle rebuild
 
-    // geodesic fields (rto_geodesic.inc): the last field of the resident grid, with the medium and connectivity it was made for
-    // (rto_geodesic_paths walks it under them); dropped whenever the grid changes
-    int* d_geo = nullptr;                     // nullptr: no field resident
+    // geodesic fields (rto_geodesic.inc): the medium and connectivity the resident field was made for (rto_geodesic_paths walks it
+    // under them)
     int geoMedium = 0, geoConn = 0;
     int64_t geoPasses = 0, geoTilesRun = 0;
     int geoLook = 8;                          // relaxation launches per look at the device (rto_debug_set_geodesic_look): changes no value
     float geoMs[3] = { -1.f, -1.f, -1.f };    // the last rto_geodesic_field: init, relaxation, summary
     float geoEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_geodesic: field and flip, octree rebuild, triangle rebuild
 
-    // local thickness fields (rto_thickness.inc): the last field of the resident grid, with the medium and the cap c it was made
-    // for and its histogram (c + 1 bins, on the host); dropped whenever the grid changes
-    int* d_thick = nullptr;                   // nullptr: no field resident
+    // local thickness fields (rto_thickness.inc): the medium and the cap c the resident field was made for and its histogram
+    // (c + 1 bins, on the host)
     int thickMedium = 0, thickCap = 0;
     int* d_thickTab = nullptr;                // k_thick_gather's offset table for thickTabCap (0: none yet): it depends on c alone, so it
                                               // outlives fields and grids and is freed by rto_destroy
@@ -206,18 +212,14 @@ struct rto_context {
     int64_t thickBins[65] = { 0 };
     float thickMs[3] = { -1.f, -1.f, -1.f };  // the last rto_thickness_field: transform, gather, summary
 
-    // skeleton fields (rto_skeleton.inc): the last field of the resident grid, with the set, connectivity and mode it was made
-    // for; dropped whenever the grid changes
-    int* d_skel = nullptr;                    // nullptr: no field resident
+    // skeleton fields (rto_skeleton.inc): the set, connectivity and mode the resident field was made for
     int skelSet = 0, skelConn = 0, skelMode = 0;
     int64_t skelLaunches = 0, skelTilesRun = 0;
     int skelLook = 8;                         // passes per look at the device (rto_debug_set_skeleton_look): changes no value
     float skelMs[3] = { -1.f, -1.f, -1.f };   // the last rto_skeleton_field: init, thinning, summary
     float skelEditMs[3] = { -1.f, -1.f, -1.f };   // the last rto_edit_skeleton: field and flip, octree rebuild, triangle rebuild
 
-    // exposure fields (rto_exposure.inc): the last field of the resident grid, with the directions, weight sum, mode and reach it
-    // was made for; dropped whenever the grid changes
-    int* d_expo = nullptr;                    // nullptr: no field resident
+    // exposure fields (rto_exposure.inc): the directions, weight sum, mode and reach the resident field was made for
     int expoN = 0, expoMode = 0, expoReach = 0;
     int64_t expoW = 0;
     float expoMs[3] = { -1.f, -1.f, -1.f };   // the last rto_exposure_field: prepare, march, summary
@@ -250,8 +252,8 @@ static inline long long dev_env(const char* name, long long unset) {
 }
 
 // Test hook (rto_debug_fault_alloc(k), an explicit call: never the environment): the k-th (1-based) buffer allocation of the
-// frustum-update buffers / rto_comm buffers from now on fails, so that the all-or-nothing clean-up below can be exercised
-// (tests/test_gpu_parity.py, tests/_fault_alloc_worker.py).  0: never.
+// frustum-update buffers / rto_comm buffers / field drafts (FieldDraft) from now on fails, so that the all-or-nothing clean-up can be
+// exercised (tests/test_gpu_parity.py, tests/_fault_alloc_worker.py, tests/test_field_lifecycle.py).  0: never.
 static long g_faultCountdown = 0;
 static hipError_t fallible_malloc(void** p, size_t bytes) {
     if (g_faultCountdown > 0 && --g_faultCountdown == 0) { *p = nullptr; return hipErrorOutOfMemory; }
@@ -278,29 +280,15 @@ static void free_components(rto_context* c) {
     c->ccCount = 0;
 }
 
-// The resident distance field (rto_distance.inc): it describes one state of the grid.
-static void free_distance(rto_context* c) { (void)hipFree(c->d_dist); c->d_dist = nullptr; }
-
-// The resident geodesic field (rto_geodesic.inc): it describes one state of the grid.
-static void free_geodesic(rto_context* c) { (void)hipFree(c->d_geo); c->d_geo = nullptr; }
-
-// The resident local thickness field (rto_thickness.inc): it describes one state of the grid.
-static void free_thickness(rto_context* c) { (void)hipFree(c->d_thick); c->d_thick = nullptr; }
-
-// The resident skeleton field (rto_skeleton.inc): it describes one state of the grid.
-static void free_skeleton(rto_context* c) { (void)hipFree(c->d_skel); c->d_skel = nullptr; }
-
-// The resident exposure field (rto_exposure.inc): it describes one state of the grid.
-static void free_exposure(rto_context* c) { (void)hipFree(c->d_expo); c->d_expo = nullptr; }
+// The resident voxel fields: each describes one state of the grid.
+static void free_fields(rto_context* c) {
+    for (int*& d : c->d_field) { (void)hipFree(d); d = nullptr; }
+}
 
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
-    free_distance(c);
-    free_geodesic(c);
-    free_thickness(c);
-    free_skeleton(c);
-    free_exposure(c);
+    free_fields(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
         if (c->d_nodes) (void)hipFreeAsync(c->d_nodes, c->stream);
@@ -977,19 +965,150 @@ static int download_resident(rto_context* c, const char* who, void* out, int64_t
     return RTO_OK;
 }
 
+// ---------------------------------------------------------------- resident voxel fields: what their five families share
+// A field that is the call's own until the call has succeeded.  begin(): the device is set, the context's stream drained and one
+// int32 per voxel of the resident grid allocated, in that order.  publish(): the slot's old field is freed and the new one takes its
+// place.  A call that returns before publish() leaves the slot as it was and the draft goes with the scope.
+struct FieldDraft {
+    rto_context* c;
+    FieldSlot slot;
+    int* d = nullptr;
+    FieldDraft(rto_context* ctx, FieldSlot which) : c(ctx), slot(which) {}
+    FieldDraft(const FieldDraft&) = delete;
+    FieldDraft& operator=(const FieldDraft&) = delete;
+    ~FieldDraft() { (void)hipFree(d); }
+    int begin() {
+        RTO_HIP(c, hipSetDevice(c->device));
+        RTO_HIP(c, hipStreamSynchronize(c->stream));
+        RTO_HIP(c, fallible_malloc(reinterpret_cast<void**>(&d), (size_t)grid_voxels(c) * sizeof(int)));
+        return RTO_OK;
+    }
+    void publish() {
+        (void)hipFree(c->d_field[slot]);
+        c->d_field[slot] = d;
+        d = nullptr;
+    }
+};
+
+// Is the slot's field resident?  What every entry point that reads one asks first.
+static int resident_field_check(rto_context* c, const char* who, FieldSlot slot) {
+    if (c->d_field[slot]) return RTO_OK;
+    return fail(c, RTO_E_INVALID, std::string(who) + ": no " + kFieldNoun[slot] + " field is resident (not made yet, or the grid has changed since)");
+}
+
+// The rto_download_* entry of a field.
+static int download_field(rto_context* c, const char* who, FieldSlot slot, int32_t* out, int64_t capacity) {
+    if (!c) return RTO_E_INVALID;
+    const int rc = resident_field_check(c, who, slot);
+    if (rc != RTO_OK) return rc;
+    return download_resident(c, who, out, capacity, c->d_field[slot], grid_voxels(c), sizeof(int32_t));
+}
+
+// The rto_*_device entry of a field.
+static int field_device(rto_context* c, const char* who, FieldSlot slot, int32_t** d_out) {
+    if (!c) return RTO_E_INVALID;
+    const int rc = resident_field_check(c, who, slot);
+    if (rc != RTO_OK) return rc;
+    if (d_out) *d_out = c->d_field[slot];
+    return RTO_OK;
+}
+
+// The rto_last_*_ms entries: the N times the context keeps of its last call of a kind.
+template <int N> static int copy_last_ms(const rto_context* c, float (rto_context::*kept)[N], float* ms) {
+    if (!c || !ms) return RTO_E_INVALID;
+    for (int i = 0; i < N; i++) ms[i] = (c->*kept)[i];
+    return RTO_OK;
+}
+
+// `red` zeroed on the device, one launch that reduces into it between two events, read back: red and the launch's device time.
+// launch(d_red) enqueues the kernel on the context's stream.
+template <int N, class Launch> static int reduce_words(rto_context* c, Launch launch, unsigned long long (&red)[N], float* ms) {
+    hipStream_t s = c->stream;
+    StreamEvents<2> events;
+    RTO_HIP(c, events.create());
+    BuildScratch scratch(s);
+    unsigned long long* d_red = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_red, N));
+    RTO_HIP(c, hipMemsetAsync(d_red, 0, N * sizeof(unsigned long long), s));
+    RTO_HIP(c, events.record(0, s));
+    launch(d_red);
+    RTO_HIP(c, hipGetLastError());
+    RTO_HIP(c, events.record(1, s));
+    RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
+    RTO_HIP(c, hipStreamSynchronize(s));
+    RTO_HIP(c, events.elapsed(0, 1, ms));
+    return RTO_OK;
+}
+
+// One look of the host at passes that run until one of them reports nothing: d_row (kMaxLook words) is zeroed, enqueue(i, d_row + i)
+// sends pass i of `launch` <= kMaxLook, which leaves what it did in its word, and the row is read back.  Passes behind the first
+// zero word did nothing, so how many go out together changes no value: `passes` counts up to and including that word (then
+// settled), `sum` adds the words counted.
+constexpr int kMaxLook = 64;
+template <class Enqueue>
+static int look_at_passes(rto_context* c, unsigned* d_row, int launch, Enqueue enqueue, int64_t& passes, int64_t& sum, bool& settled) {
+    hipStream_t s = c->stream;
+    unsigned row[kMaxLook];
+    RTO_HIP(c, hipMemsetAsync(d_row, 0, kMaxLook * sizeof(unsigned), s));
+    for (int i = 0; i < launch; i++) {
+        const int rc = enqueue(i, d_row + i);
+        if (rc != RTO_OK) return rc;
+    }
+    RTO_HIP(c, hipMemcpyAsync(row, d_row, (size_t)launch * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    RTO_HIP(c, hipStreamSynchronize(s));
+    for (int i = 0; i < launch && !settled; i++) {
+        passes++;
+        sum += row[i];
+        settled = row[i] == 0u;
+    }
+    return RTO_OK;
+}
+
+// Is every entry of a caller's voxel list a voxel of the resident grid?  noun: "a seed", "an anchor", "a target".
+static int voxel_list_check(rto_context* c, const char* who, const char* noun, const int64_t* list, int64_t n) {
+    const int64_t nvox = grid_voxels(c);
+    for (int64_t i = 0; i < n; i++)
+        if (list[i] < 0 || list[i] >= nvox) return fail(c, RTO_E_INVALID, std::string(who) + ": " + noun + " is not a voxel of the grid");
+    return RTO_OK;
+}
+
+// A checked voxel list on the device, in the call's scratch: uploaded as it is, then handed to one-thread-per-entry kernels in
+// parts, because a launch's thread count fits 32 bits.  launch(d_part, count) enqueues the kernel for one part.
+struct VoxelList {
+    long long* d = nullptr;
+    int64_t n = 0;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the entries travel as they are");
+    hipError_t upload(BuildScratch& scratch, const int64_t* list, int64_t count, hipStream_t s) {
+        n = count;
+        if (n == 0) return hipSuccess;
+        const hipError_t e = scratch.alloc(&d, (size_t)n);
+        return e != hipSuccess ? e : hipMemcpyAsync(d, list, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s);
+    }
+    template <class Launch> int in_parts(rto_context* c, Launch launch) const {
+        for (int64_t at = 0; at < n; at += 0x40000000ll) {
+            launch(d + at, (unsigned)std::min<int64_t>(n - at, 0x40000000ll));
+            RTO_HIP(c, hipGetLastError());
+        }
+        return RTO_OK;
+    }
+};
+
 // The one way from a changed resident grid back to a renderable context: what rto_build_octree(that grid, same gridMin, same
 // voxelSize) leaves, followed by rto_build_leaf_triangles(NULL) when `triangles` -- the callers pass "were triangles resident?",
 // sampled before the call, or what their parameters ask for.  Every grid edit and the voxelizer's commit end here.
 //   dropped:  the octree's arrays and all that describes the grid or the tree as it was (free_octree_arrays): component labels,
-//             distance field, leaf triangles and their records, cull buffers and the culling switch, occupancy cells, mesh levels;
-//             every stream's tile orders and cost history are invalidated.
+//             table and measures, the five resident voxel fields (distance, geodesic, thickness, skeleton, exposure), leaf triangles
+//             and their records, cull buffers and the culling switch, occupancy cells, mesh levels; every stream's tile orders and
+//             cost history are invalidated.
 //   survives: d_vox, voxDim, gridMin, voxelSize, buildPath (and everything that is not per octree: kernel mode, frame buffers,
-//             the last extracted mesh).
+//             the last extracted mesh, the thickness gather's offset table).
 //   timing:   each build's buildMs goes to *octree_ms / *tris_ms (either may be nullptr) as soon as that build has succeeded.
 //   failure:  the failing build's code and message are returned.  The octree build fails: numNodes == 0, so the context
 //             answers RTO_E_NO_OCTREE until a build succeeds; the grid stays in d_vox; arrays the build had already allocated are
 //             released by the next free_octree_arrays or by rto_destroy.  The triangle build fails: the new octree is complete
 //             and usable, *octree_ms is written, and the triangle buffers are what rto_build_leaf_triangles leaves on that error.
+// An edit that finds it changed no voxel returns without coming here: the grid is byte for byte what it was, so nothing is
+// dropped -- octree, triangles, labels, measures, the five fields and the frustum state all stay.
 static int rebuild_from_resident_grid(rto_context* c, bool triangles, float* octree_ms, float* tris_ms) {
     const int R = root_depth_of(c->voxDim[0], c->voxDim[1], c->voxDim[2]);
     free_octree_arrays(c);

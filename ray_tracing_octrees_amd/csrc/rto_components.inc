@@ -467,6 +467,14 @@ __global__ __launch_bounds__(kBlock) void k_cc_flip(uint8_t* __restrict__ vox, c
 
 namespace {
 
+// The kCcTileX x kCcTileY x kCcTileZ tiles that cover a grid: what every kernel that runs one workgroup per tile is launched over.
+struct CcTiles {
+    int x, y, z;
+    explicit CcTiles(const int dim[3])
+        : x((dim[0] + rto::kCcTileX - 1) / rto::kCcTileX), y((dim[1] + rto::kCcTileY - 1) / rto::kCcTileY), z((dim[2] + rto::kCcTileZ - 1) / rto::kCcTileZ) {}
+    size_t count() const { return (size_t)x * y * z; }
+};
+
 // One labelling, owned by whoever holds it (the context, or rto_edit_components for the length of the call).
 struct CcResult {
     int* d_labels = nullptr;
@@ -495,8 +503,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
     RTO_HIP(c, events.create());
     struct OutGuard { CcResult* r; bool keep = false; ~OutGuard() { if (!keep) r->release(); } } og{ &out };
 
-    const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
-    const long long tiles = (long long)tilesX * tilesY * tilesZ;
+    const CcTiles T(c->voxDim);
     const unsigned chunks = (D.n + kCcChunk - 1) / kCcChunk;
     const unsigned voxBlocks = (D.n + kBlock - 1) / kBlock;
     const bool full = connectivity == RTO_CONN_FULL;
@@ -514,12 +521,12 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
     // (1) tiles
     RTO_HIP(c, events.record(0, s));
     {
-        const dim3 g((unsigned)tiles), b(kBlock);
+        const dim3 g((unsigned)T.count()), b(kBlock);
         const bool wide = D.x % kCcVec == 0;
-        if (wide && full) hipLaunchKernelGGL((k_cc_local<true, true>), g, b, 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_parent);
-        else if (wide) hipLaunchKernelGGL((k_cc_local<true, false>), g, b, 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_parent);
-        else if (full) hipLaunchKernelGGL((k_cc_local<false, true>), g, b, 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_parent);
-        else hipLaunchKernelGGL((k_cc_local<false, false>), g, b, 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_parent);
+        if (wide && full) hipLaunchKernelGGL((k_cc_local<true, true>), g, b, 0, s, c->d_vox, D, T.x, T.y, setValue, d_parent);
+        else if (wide) hipLaunchKernelGGL((k_cc_local<true, false>), g, b, 0, s, c->d_vox, D, T.x, T.y, setValue, d_parent);
+        else if (full) hipLaunchKernelGGL((k_cc_local<false, true>), g, b, 0, s, c->d_vox, D, T.x, T.y, setValue, d_parent);
+        else hipLaunchKernelGGL((k_cc_local<false, false>), g, b, 0, s, c->d_vox, D, T.x, T.y, setValue, d_parent);
         RTO_HIP(c, hipGetLastError());
     }
     RTO_HIP(c, events.record(1, s));
@@ -614,11 +621,7 @@ int rto_labels_device(rto_context* c, int32_t** d_labels, rto_component** d_comp
     return RTO_OK;
 }
 
-int rto_last_components_ms(const rto_context* c, float ms[4]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 4; i++) ms[i] = c->ccMs[i];
-    return RTO_OK;
-}
+int rto_last_components_ms(const rto_context* c, float ms[4]) { return copy_last_ms(c, &rto_context::ccMs, ms); }
 
 int rto_debug_components_passes(const rto_context* c, int* passes) {
     if (!c || !passes) return RTO_E_INVALID;
@@ -668,7 +671,7 @@ int rto_edit_components(rto_context* c, int set, int connectivity, int select, i
         RTO_HIP(c, d_count.read(s, &count));
     }
     if (changed) *changed = (int64_t)count;
-    if (count == 0) return RTO_OK;                                  // the octree, the triangles, the labels and the frustum state stay
+    if (count == 0) return RTO_OK;           // nothing is dropped: rebuild_from_resident_grid's comment
 
     return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, nullptr, nullptr);
 }

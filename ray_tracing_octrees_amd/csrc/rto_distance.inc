@@ -317,6 +317,25 @@ int dt_transform(rto_context* c, int set, int cap, int* d_out, float ms[3]) {
     return RTO_OK;
 }
 
+// The summary of a distance-like field (one int32 per voxel, kDtNone where there is no value): k_dt_summary over it, decoded.
+struct DtSummary {
+    int64_t finite = 0;                // voxels that hold a value
+    int64_t max = -1, argmax = -1;     // the largest value and the smallest voxel that holds it; -1: no voxel holds a value
+    float ms = -1.f;                   // device time of the launch
+};
+int dt_summary(rto_context* c, const int* d_field, unsigned n, DtSummary& out) {
+    using namespace rto;
+    unsigned long long red[2] = { 0ull, 0ull };                         // the key, the count
+    const int rc = reduce_words(c, [&](unsigned long long* d_red) {
+        hipLaunchKernelGGL(k_dt_summary, dim3((n + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, c->stream, d_field, n, d_red, d_red + 1);
+    }, red, &out.ms);
+    if (rc != RTO_OK) return rc;
+    out.finite = (int64_t)red[1];
+    out.max = red[1] ? (int64_t)(red[0] >> 32) : -1;
+    out.argmax = red[1] ? (int64_t)(~(unsigned)(red[0] & 0xffffffffull)) : -1;
+    return RTO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -332,61 +351,32 @@ int rto_distance_field(rto_context* c, int set, float max_dist, rto_dist_summary
         return fail(c, RTO_E_INVALID, "rto_distance_field: max_dist is beyond 2^28 quanta of voxelSize / 64");
     const int rcGrid = dt_check_grid(c, "rto_distance_field");
     if (rcGrid != RTO_OK) return rcGrid;
-    RTO_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned n = (unsigned)grid_voxels(c);
-    int* d_new = nullptr;
-    RTO_HIP(c, hipMalloc(&d_new, (size_t)n * sizeof(int)));
-    struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
+    FieldDraft draft(c, kFieldDistance);
+    const int rcDraft = draft.begin();
+    if (rcDraft != RTO_OK) return rcDraft;
     float ms[4] = { -1.f, -1.f, -1.f, -1.f };
-    const int rc = dt_transform(c, set, cap, d_new, ms);
+    const int rc = dt_transform(c, set, cap, draft.d, ms);
     if (rc != RTO_OK) return rc;
     if (summary) {
-        StreamEvents<2> events;
-        RTO_HIP(c, events.create());
-        BuildScratch scratch(s);
-        unsigned long long* d_red = nullptr;
-        RTO_HIP(c, scratch.alloc(&d_red, 2));
-        RTO_HIP(c, hipMemsetAsync(d_red, 0, 2 * sizeof(unsigned long long), s));
-        RTO_HIP(c, events.record(0, s));
-        hipLaunchKernelGGL(k_dt_summary, dim3((n + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, s, d_new, n, d_red, d_red + 1);
-        RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, events.record(1, s));
-        unsigned long long red[2] = { 0ull, 0ull };
-        RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
-        RTO_HIP(c, events.elapsed(0, 1, &ms[3]));
-        summary->finite = (int64_t)red[1];
-        summary->max_d2 = red[1] ? (int64_t)(red[0] >> 32) : -1;
-        summary->argmax = red[1] ? (int64_t)(~(unsigned)(red[0] & 0xffffffffull)) : -1;
+        DtSummary sum;
+        const int rcSum = dt_summary(c, draft.d, (unsigned)grid_voxels(c), sum);
+        if (rcSum != RTO_OK) return rcSum;
+        ms[3] = sum.ms;
+        summary->finite = sum.finite;
+        summary->max_d2 = sum.max;
+        summary->argmax = sum.argmax;
         summary->reserved = 0;
     }
-    free_distance(c);
-    c->d_dist = d_new;
-    guard.p = nullptr;
+    draft.publish();
     for (int i = 0; i < 4; i++) c->distMs[i] = ms[i];
     return RTO_OK;
 }
 
-int rto_download_distance(rto_context* c, int32_t* out, int64_t capacity) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_dist) return fail(c, RTO_E_INVALID, "rto_download_distance: no distance field is resident (not made yet, or the grid has changed since)");
-    return download_resident(c, "rto_download_distance", out, capacity, c->d_dist, grid_voxels(c), sizeof(int32_t));
-}
+int rto_download_distance(rto_context* c, int32_t* out, int64_t capacity) { return download_field(c, "rto_download_distance", kFieldDistance, out, capacity); }
 
-int rto_distance_device(rto_context* c, int32_t** d_d2) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_dist) return fail(c, RTO_E_INVALID, "rto_distance_device: no distance field is resident (not made yet, or the grid has changed since)");
-    if (d_d2) *d_d2 = c->d_dist;
-    return RTO_OK;
-}
+int rto_distance_device(rto_context* c, int32_t** d_d2) { return field_device(c, "rto_distance_device", kFieldDistance, d_d2); }
 
-int rto_last_distance_ms(const rto_context* c, float ms[4]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 4; i++) ms[i] = c->distMs[i];
-    return RTO_OK;
-}
+int rto_last_distance_ms(const rto_context* c, float ms[4]) { return copy_last_ms(c, &rto_context::distMs, ms); }
 
 int rto_edit_morphology(rto_context* c, int op, float radius, int64_t* changed) {
     using namespace rto;
@@ -449,15 +439,11 @@ int rto_edit_morphology(rto_context* c, int op, float radius, int64_t* changed) 
         RTO_HIP(c, events.elapsed(0, 1, &c->morphMs[0]));
     }
     if (changed) *changed = (int64_t)count;
-    if (count == 0) return RTO_OK;           // the grid is byte for byte what it was: octree, triangles, labels, field and frustum state stay
+    if (count == 0) return RTO_OK;           // nothing is dropped: rebuild_from_resident_grid's comment
 
     return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->morphMs[1], &c->morphMs[2]);
 }
 
-int rto_last_morphology_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->morphMs[i];
-    return RTO_OK;
-}
+int rto_last_morphology_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::morphMs, ms); }
 
 }  // extern "C"

@@ -211,7 +211,7 @@ int rto_edit_voxels(rto_context* c, const rto_brush* brushes, int n, int64_t* ch
     }
     RTO_HIP(c, events.elapsed(0, 1, &c->editMs[0]));
     if (changed) *changed = (int64_t)count;
-    if (count == 0) return RTO_OK;                                  // the octree, the triangles and the frustum state stay as they were
+    if (count == 0) return RTO_OK;           // nothing is dropped: rebuild_from_resident_grid's comment
 
     return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->editMs[1], &c->editMs[2]);
 }
@@ -225,10 +225,6 @@ int rto_download_voxels(rto_context* c, uint8_t* out, int64_t capacity, int dims
     return download_resident(c, "rto_download_voxels", out, capacity, c->d_vox, grid_voxels(c), 1);
 }
 
-int rto_last_edit_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->editMs[i];
-    return RTO_OK;
-}
+int rto_last_edit_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::editMs, ms); }
 
 }  // extern "C"

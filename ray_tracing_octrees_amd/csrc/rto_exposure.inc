@@ -236,15 +236,13 @@ int rto_exposure_field(rto_context* c, const int32_t* dirs, const int32_t* weigh
         table[(size_t)i] = ExDir{ row, len, prim[0], prim[1], prim[2], weights ? weights[i] : 1 };
     }
 
-    RTO_HIP(c, hipSetDevice(c->device));
+    FieldDraft draft(c, kFieldExposure);
+    const int rcDraft = draft.begin();
+    if (rcDraft != RTO_OK) return rcDraft;
     hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
     const unsigned nvox = (unsigned)grid_voxels(c);
     const int wordsX = (c->voxDim[0] + 31) / 32;
     const ExDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], wordsX, (unsigned)((int64_t)wordsX * c->voxDim[1] * c->voxDim[2]) };
-    int* d_new = nullptr;
-    RTO_HIP(c, hipMalloc(&d_new, (size_t)nvox * sizeof(int)));
-    struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
     float ms[3] = { -1.f, -1.f, -1.f };
     unsigned count = 0u;
     unsigned long long red[3] = { 0ull, 0ull, 0ull };
@@ -265,7 +263,7 @@ int rto_exposure_field(rto_context* c, const int32_t* dirs, const int32_t* weigh
         RTO_HIP(c, hipMemsetAsync(d_red, 0, 3 * sizeof(unsigned long long), s));
         RTO_HIP(c, hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(ExDir), hipMemcpyHostToDevice, s));
         RTO_HIP(c, hipMemcpyAsync(d_tmpl, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        RTO_HIP(c, hipMemsetAsync(d_new, 0xff, (size_t)nvox * sizeof(int), s));
+        RTO_HIP(c, hipMemsetAsync(draft.d, 0xff, (size_t)nvox * sizeof(int), s));
         const dim3 b(kBlock), perWord((D.words + kBlock - 1) / kBlock);
         if (D.x % 32 == 0) hipLaunchKernelGGL(k_expo_bits<true>, perWord, b, 0, s, c->d_vox, D, d_bits);
         else hipLaunchKernelGGL(k_expo_bits<false>, perWord, b, 0, s, c->d_vox, D, d_bits);
@@ -278,13 +276,13 @@ int rto_exposure_field(rto_context* c, const int32_t* dirs, const int32_t* weigh
         RTO_HIP(c, hipStreamSynchronize(s));
         if (count > nvox) return fail(c, RTO_E_INTERNAL, w + ": the list holds more voxels than the grid");
         if (count) {
-            hipLaunchKernelGGL(k_expo_march, dim3((count + kBlock - 1) / kBlock), b, 0, s, d_bits, D, d_list, count, d_table, d_tmpl, n, reach, d_new);
+            hipLaunchKernelGGL(k_expo_march, dim3((count + kBlock - 1) / kBlock), b, 0, s, d_bits, D, d_list, count, d_table, d_tmpl, n, reach, draft.d);
             RTO_HIP(c, hipGetLastError());
         }
         RTO_HIP(c, events.record(2, s));
         if (summary && count) {
             const unsigned blocks = std::min<unsigned>((count + kBlock - 1) / kBlock, 4096u);
-            hipLaunchKernelGGL(k_expo_summary, dim3(blocks), b, 0, s, d_new, d_list, count, (int)W, d_red);
+            hipLaunchKernelGGL(k_expo_summary, dim3(blocks), b, 0, s, draft.d, d_list, count, (int)W, d_red);
             RTO_HIP(c, hipGetLastError());
         }
         RTO_HIP(c, events.record(3, s));
@@ -298,31 +296,16 @@ int rto_exposure_field(rto_context* c, const int32_t* dirs, const int32_t* weigh
         summary->dark = (int64_t)red[1];
         summary->open = (int64_t)red[2];
     }
-    free_exposure(c);
-    c->d_expo = d_new;
-    guard.p = nullptr;
+    draft.publish();
     c->expoN = n; c->expoW = W; c->expoMode = mode; c->expoReach = reach;
     for (int i = 0; i < 3; i++) c->expoMs[i] = ms[i];
     return RTO_OK;
 }
 
-int rto_download_exposure(rto_context* c, int32_t* out, int64_t capacity) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_expo) return fail(c, RTO_E_INVALID, "rto_download_exposure: no exposure field is resident (not made yet, or the grid has changed since)");
-    return download_resident(c, "rto_download_exposure", out, capacity, c->d_expo, grid_voxels(c), sizeof(int32_t));
-}
+int rto_download_exposure(rto_context* c, int32_t* out, int64_t capacity) { return download_field(c, "rto_download_exposure", kFieldExposure, out, capacity); }
 
-int rto_exposure_device(rto_context* c, int32_t** d_e) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_expo) return fail(c, RTO_E_INVALID, "rto_exposure_device: no exposure field is resident (not made yet, or the grid has changed since)");
-    if (d_e) *d_e = c->d_expo;
-    return RTO_OK;
-}
+int rto_exposure_device(rto_context* c, int32_t** d_e) { return field_device(c, "rto_exposure_device", kFieldExposure, d_e); }
 
-int rto_last_exposure_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->expoMs[i];
-    return RTO_OK;
-}
+int rto_last_exposure_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::expoMs, ms); }
 
 }  // extern "C"

@@ -23,7 +23,6 @@ namespace rto {
 
 constexpr int kGeoHaloX = kCcTileX + 2, kGeoHaloY = kCcTileY + 2, kGeoHaloZ = kCcTileZ + 2;   // 34 x 10 x 10
 constexpr int kGeoHaloVox = kGeoHaloX * kGeoHaloY * kGeoHaloZ;                                // 3400 values, 13.3 KiB of LDS
-constexpr int kGeoMaxLook = 64;                          // relaxation launches per look of the host at the device, at most
 
 __device__ __forceinline__ int geo_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void geo_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -250,11 +249,10 @@ int geo_check_args(rto_context* c, const char* who, int medium, int connectivity
     if (limit < 0) return fail(c, RTO_E_INVALID, w + ": limit is negative");
     const int rcGrid = resident_grid_check(c, who, ": the field is 32-bit");
     if (rcGrid != RTO_OK) return rcGrid;
-    const int64_t nvox = grid_voxels(c);
     const int64_t wmax = connectivity == RTO_CONN_FULL ? 5 : 1;
-    if (wmax * (nvox - 1) >= 0x7fffffffll) return fail(c, RTO_E_UNSUPPORTED, w + ": the longest possible path does not fit the 32-bit field");
-    for (int64_t i = 0; i < n; i++)
-        if (seeds[i] < 0 || seeds[i] >= nvox) return fail(c, RTO_E_INVALID, w + ": a seed is not a voxel of the grid");
+    if (wmax * (grid_voxels(c) - 1) >= 0x7fffffffll) return fail(c, RTO_E_UNSUPPORTED, w + ": the longest possible path does not fit the 32-bit field");
+    const int rcSeeds = voxel_list_check(c, who, "a seed", seeds, n);
+    if (rcSeeds != RTO_OK) return rcSeeds;
     *limitOut = limit >= 0x7fffffffll ? (unsigned)rto::kDtNone - 1u : (unsigned)limit;
     return RTO_OK;
 }
@@ -267,55 +265,43 @@ int geo_relax(rto_context* c, const char* who, int medium, int connectivity, con
     hipStream_t s = c->stream;
     StreamEvents<3> events;
     RTO_HIP(c, events.create());
-    const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
-    const size_t tiles = (size_t)tilesX * tilesY * tilesZ;
+    const CcTiles T(c->voxDim);
+    const size_t tiles = T.count();
     const unsigned setValue = medium == RTO_SET_SOLID ? 1u : 0u;
     const bool full = connectivity == RTO_CONN_FULL, wide = D.x % kCcVec == 0;
     BuildScratch scratch(s);
-    long long* d_seeds = nullptr; int* d_active = nullptr; unsigned* d_counters = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_seeds, (size_t)n));
+    VoxelList d_seeds; int* d_active = nullptr; unsigned* d_counters = nullptr;
+    RTO_HIP(c, d_seeds.upload(scratch, seeds, n, s));
     RTO_HIP(c, scratch.alloc(&d_active, 2 * tiles));
-    RTO_HIP(c, scratch.alloc(&d_counters, (size_t)kGeoMaxLook));
-    static_assert(sizeof(long long) == sizeof(int64_t), "seeds travel as they are");
-    RTO_HIP(c, hipMemcpyAsync(d_seeds, seeds, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    RTO_HIP(c, scratch.alloc(&d_counters, (size_t)kMaxLook));
     RTO_HIP(c, events.record(0, s));
     RTO_HIP(c, hipMemsetAsync(d_active, 0, 2 * tiles * sizeof(int), s));
     hipLaunchKernelGGL(k_geo_fill, dim3((unsigned)((((int64_t)D.n + kCcVec - 1) / kCcVec + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, d_out, D.n);
     RTO_HIP(c, hipGetLastError());
-    for (int64_t at = 0; at < n; at += 0x40000000ll) {                  // a launch's thread count fits 32 bits
-        const unsigned part = (unsigned)std::min<int64_t>(n - at, 0x40000000ll);
-        hipLaunchKernelGGL(k_geo_seeds, dim3((part + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c->d_vox, D, tilesX, tilesY, setValue, d_seeds + at, part,
-                           d_out, d_active);
-        RTO_HIP(c, hipGetLastError());
-    }
+    const int rcSeeds = d_seeds.in_parts(c, [&](const long long* part, unsigned count) {
+        hipLaunchKernelGGL(k_geo_seeds, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c->d_vox, D, T.x, T.y, setValue, part, count, d_out, d_active);
+    });
+    if (rcSeeds != RTO_OK) return rcSeeds;
     RTO_HIP(c, events.record(1, s));
-    // launches until one finds no tile marked; `look` of them between two looks at the counters.  Launches behind that one find
-    // nothing marked either and write nothing, so how many go out together changes no value.
+    // launches until one finds no tile marked (its word: the tiles it ran); `look` of them between two looks (look_at_passes)
     const int64_t cap = (int64_t)D.n + 2;
-    const int look = std::max(1, std::min(c->geoLook, kGeoMaxLook));
+    const int look = std::max(1, std::min(c->geoLook, kMaxLook));
     int64_t passes = 0, tilesRun = 0;
     bool settled = false;
-    unsigned counts[kGeoMaxLook];
     while (!settled && passes < cap) {
         const int launch = (int)std::min<int64_t>(look, cap - passes);
-        RTO_HIP(c, hipMemsetAsync(d_counters, 0, kGeoMaxLook * sizeof(unsigned), s));
-        for (int i = 0; i < launch; i++) {
+        const int rcLook = look_at_passes(c, d_counters, launch, [&](int i, unsigned* ran) -> int {
             int* cur = d_active + (size_t)((passes + i) & 1) * tiles;
             int* next = d_active + (size_t)((passes + i + 1) & 1) * tiles;
             const dim3 gr((unsigned)tiles), b(kBlock);
-            if (wide && full) hipLaunchKernelGGL((k_geo_relax<true, true>), gr, b, 0, s, c->d_vox, D, tilesX, tilesY, tilesZ, setValue, limit, d_out, cur, next, d_counters + i);
-            else if (wide) hipLaunchKernelGGL((k_geo_relax<true, false>), gr, b, 0, s, c->d_vox, D, tilesX, tilesY, tilesZ, setValue, limit, d_out, cur, next, d_counters + i);
-            else if (full) hipLaunchKernelGGL((k_geo_relax<false, true>), gr, b, 0, s, c->d_vox, D, tilesX, tilesY, tilesZ, setValue, limit, d_out, cur, next, d_counters + i);
-            else hipLaunchKernelGGL((k_geo_relax<false, false>), gr, b, 0, s, c->d_vox, D, tilesX, tilesY, tilesZ, setValue, limit, d_out, cur, next, d_counters + i);
+            if (wide && full) hipLaunchKernelGGL((k_geo_relax<true, true>), gr, b, 0, s, c->d_vox, D, T.x, T.y, T.z, setValue, limit, d_out, cur, next, ran);
+            else if (wide) hipLaunchKernelGGL((k_geo_relax<true, false>), gr, b, 0, s, c->d_vox, D, T.x, T.y, T.z, setValue, limit, d_out, cur, next, ran);
+            else if (full) hipLaunchKernelGGL((k_geo_relax<false, true>), gr, b, 0, s, c->d_vox, D, T.x, T.y, T.z, setValue, limit, d_out, cur, next, ran);
+            else hipLaunchKernelGGL((k_geo_relax<false, false>), gr, b, 0, s, c->d_vox, D, T.x, T.y, T.z, setValue, limit, d_out, cur, next, ran);
             RTO_HIP(c, hipGetLastError());
-        }
-        RTO_HIP(c, hipMemcpyAsync(counts, d_counters, (size_t)launch * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
-        for (int i = 0; i < launch && !settled; i++) {
-            passes++;
-            tilesRun += counts[i];
-            settled = counts[i] == 0u;
-        }
+            return RTO_OK;
+        }, passes, tilesRun, settled);
+        if (rcLook != RTO_OK) return rcLook;
     }
     if (!settled) return fail(c, RTO_E_INTERNAL, std::string(who) + ": the relaxation did not settle within voxels + 2 passes");
     RTO_HIP(c, events.record(2, s));
@@ -326,129 +312,12 @@ int geo_relax(rto_context* c, const char* who, int medium, int connectivity, con
     return RTO_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rto_geodesic_field(rto_context* c, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit, rto_geo_summary* summary) {
-    using namespace rto;
-    if (!c) return RTO_E_INVALID;
-    unsigned lim = 0u;
-    const int rcArgs = geo_check_args(c, "rto_geodesic_field", medium, connectivity, seeds, n, limit, &lim);
-    if (rcArgs != RTO_OK) return rcArgs;
-    RTO_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned nvox = (unsigned)grid_voxels(c);
-    int* d_new = nullptr;
-    RTO_HIP(c, hipMalloc(&d_new, (size_t)nvox * sizeof(int)));
-    struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
-    GeoRun run;
-    const int rc = geo_relax(c, "rto_geodesic_field", medium, connectivity, seeds, n, lim, d_new, run);
-    if (rc != RTO_OK) return rc;
-    float summaryMs = -1.f;
-    if (summary) {
-        StreamEvents<2> events;
-        RTO_HIP(c, events.create());
-        BuildScratch scratch(s);
-        unsigned long long* d_red = nullptr;
-        RTO_HIP(c, scratch.alloc(&d_red, 2));
-        RTO_HIP(c, hipMemsetAsync(d_red, 0, 2 * sizeof(unsigned long long), s));
-        RTO_HIP(c, events.record(0, s));
-        hipLaunchKernelGGL(k_dt_summary, dim3((nvox + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, s, d_new, nvox, d_red, d_red + 1);
-        RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, events.record(1, s));
-        unsigned long long red[2] = { 0ull, 0ull };
-        RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
-        RTO_HIP(c, events.elapsed(0, 1, &summaryMs));
-        summary->reached = (int64_t)red[1];
-        summary->max_g = red[1] ? (int64_t)(red[0] >> 32) : -1;
-        summary->argmax = red[1] ? (int64_t)(~(unsigned)(red[0] & 0xffffffffull)) : -1;
-        summary->reserved = 0;
-    }
-    free_geodesic(c);
-    c->d_geo = d_new;
-    guard.p = nullptr;
-    c->geoMedium = medium; c->geoConn = connectivity;
-    c->geoPasses = run.passes; c->geoTilesRun = run.tilesRun;
-    c->geoMs[0] = run.ms[0]; c->geoMs[1] = run.ms[1]; c->geoMs[2] = summaryMs;
-    return RTO_OK;
-}
-
-int rto_download_geodesic(rto_context* c, int32_t* out, int64_t capacity) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_geo) return fail(c, RTO_E_INVALID, "rto_download_geodesic: no geodesic field is resident (not made yet, or the grid has changed since)");
-    return download_resident(c, "rto_download_geodesic", out, capacity, c->d_geo, grid_voxels(c), sizeof(int32_t));
-}
-
-int rto_geodesic_device(rto_context* c, int32_t** d_g) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_geo) return fail(c, RTO_E_INVALID, "rto_geodesic_device: no geodesic field is resident (not made yet, or the grid has changed since)");
-    if (d_g) *d_g = c->d_geo;
-    return RTO_OK;
-}
-
-int rto_geodesic_paths(rto_context* c, const int64_t* targets, int64_t n, int64_t max_len, int64_t* out_voxels, int64_t* out_len) {
-    using namespace rto;
-    if (!c) return RTO_E_INVALID;
-    if (n < 1) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: n is below 1");
-    if (!targets || !out_len) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: targets or out_len is NULL");
-    if (max_len < 0) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: max_len is negative");
-    if (max_len > 0 && !out_voxels) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: out_voxels is NULL");
-    if (!c->d_geo) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: no geodesic field is resident (not made yet, or the grid has changed since)");
-    const int64_t nvox = grid_voxels(c);
-    for (int64_t i = 0; i < n; i++)
-        if (targets[i] < 0 || targets[i] >= nvox) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: a target is not a voxel of the grid");
-    if (n > 0x40000000ll || (max_len > 0 && n > (int64_t)(0x7fffffffffffffffll / 8) / max_len))
-        return fail(c, RTO_E_INVALID, "rto_geodesic_paths: n x max_len is beyond what one call serves");
-    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)nvox };
-    RTO_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
-    BuildScratch scratch(s);
-    long long* d_targets = nullptr; long long* d_rows = nullptr; long long* d_lens = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_targets, (size_t)n));
-    RTO_HIP(c, scratch.alloc(&d_lens, (size_t)n));
-    if (max_len > 0) RTO_HIP(c, scratch.alloc(&d_rows, (size_t)n * (size_t)max_len));
-    RTO_HIP(c, hipMemcpyAsync(d_targets, targets, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    const dim3 gr((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
-    if (c->geoConn == RTO_CONN_FULL) hipLaunchKernelGGL(k_geo_paths<true>, gr, b, 0, s, c->d_geo, D, d_targets, (unsigned)n, (long long)max_len, d_rows, d_lens);
-    else hipLaunchKernelGGL(k_geo_paths<false>, gr, b, 0, s, c->d_geo, D, d_targets, (unsigned)n, (long long)max_len, d_rows, d_lens);
-    RTO_HIP(c, hipGetLastError());
-    RTO_HIP(c, hipMemcpyAsync(out_len, d_lens, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (max_len > 0) RTO_HIP(c, hipMemcpyAsync(out_voxels, d_rows, (size_t)n * (size_t)max_len * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    RTO_HIP(c, hipStreamSynchronize(s));
-    return RTO_OK;
-}
-
-int rto_last_geodesic_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->geoMs[i];
-    return RTO_OK;
-}
-
-int rto_debug_geodesic_passes(const rto_context* c, int64_t* passes, int64_t* tiles_run) {
-    if (!c || !passes) return RTO_E_INVALID;
-    *passes = c->geoPasses;
-    if (tiles_run) *tiles_run = c->geoTilesRun;
-    return RTO_OK;
-}
-
-int rto_debug_set_geodesic_look(rto_context* c, int passes_per_look) {
-    if (!c) return RTO_E_INVALID;
-    if (passes_per_look < 1 || passes_per_look > rto::kGeoMaxLook) return fail(c, RTO_E_INVALID, "rto_debug_set_geodesic_look: 1 to 64 passes per look");
-    c->geoLook = passes_per_look;
-    return RTO_OK;
-}
-
-int rto_edit_geodesic(rto_context* c, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit, int64_t* changed) {
-    using namespace rto;
-    if (!c) return RTO_E_INVALID;
-    if (changed) *changed = 0;
-    unsigned lim = 0u;
-    const int rcArgs = geo_check_args(c, "rto_edit_geodesic", medium, connectivity, seeds, n, limit, &lim);
-    if (rcArgs != RTO_OK) return rcArgs;
+// A grid edit that is a flip by a field of the call's own (rto_edit_geodesic, and rto_edit_skeleton in rto_skeleton.inc; arguments
+// already checked): compute(d_field) makes the field in the call's scratch, flip(d_field, nvox, blocks, d_count) enqueues the
+// kernel that flips the voxels the field selects, one thread per kCcVec voxels, and counts them; then the voxel edits' rebuild.
+// editMs: field and flip, octree rebuild, triangle rebuild.
+template <class Compute, class Flip>
+int edit_by_field(rto_context* c, float (&editMs)[3], int64_t* changed, Compute compute, Flip flip) {
     RTO_HIP(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     RTO_HIP(c, hipStreamSynchronize(s));
@@ -464,31 +333,131 @@ int rto_edit_geodesic(rto_context* c, int medium, int connectivity, const int64_
         RTO_HIP(c, scratch.alloc(&d_field, (size_t)nvox));
         RTO_HIP(c, d_count.alloc(scratch));
         RTO_HIP(c, events.record(0, s));
-        GeoRun run;
-        const int rc = geo_relax(c, "rto_edit_geodesic", medium, connectivity, seeds, n, lim, d_field, run);
+        const int rc = compute(d_field);
         if (rc != RTO_OK) return rc;                                    // the grid has not been written yet
         RTO_HIP(c, d_count.clear(s));
-        const unsigned blocks = (unsigned)((((int64_t)nvox + kCcVec - 1) / kCcVec + kBlock - 1) / kBlock);
-        const unsigned from = medium == RTO_SET_SOLID ? 1u : 0u, to = medium == RTO_SET_SOLID ? 0u : 1u;
-        // only voxels of the medium hold a finite value, so the threshold of rto_edit_morphology is the flood's flip as well
-        if (nvox % kCcVec == 0) hipLaunchKernelGGL(k_morph_flip<true>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, (const uint8_t*)nullptr, nvox, from, to, d_count.d);
-        else hipLaunchKernelGGL(k_morph_flip<false>, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, (const uint8_t*)nullptr, nvox, from, to, d_count.d);
+        flip(d_field, nvox, (unsigned)((((int64_t)nvox + rto::kCcVec - 1) / rto::kCcVec + kBlock - 1) / kBlock), d_count.d);
         RTO_HIP(c, hipGetLastError());
         RTO_HIP(c, events.record(1, s));
         RTO_HIP(c, d_count.read(s, &count));
         RTO_HIP(c, events.elapsed(0, 1, &ms[0]));
     }
-    for (int i = 0; i < 3; i++) c->geoEditMs[i] = ms[i];
+    for (int i = 0; i < 3; i++) editMs[i] = ms[i];
     if (changed) *changed = (int64_t)count;
-    if (count == 0) return RTO_OK;           // the grid is byte for byte what it was: octree, triangles, labels, both fields and frustum state stay
+    if (count == 0) return RTO_OK;           // nothing is dropped: rebuild_from_resident_grid's comment
 
-    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->geoEditMs[1], &c->geoEditMs[2]);
+    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &editMs[1], &editMs[2]);
 }
 
-int rto_last_geodesic_edit_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->geoEditMs[i];
+
+}  // namespace
+
+extern "C" {
+
+int rto_geodesic_field(rto_context* c, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit, rto_geo_summary* summary) {
+    using namespace rto;
+    if (!c) return RTO_E_INVALID;
+    unsigned lim = 0u;
+    const int rcArgs = geo_check_args(c, "rto_geodesic_field", medium, connectivity, seeds, n, limit, &lim);
+    if (rcArgs != RTO_OK) return rcArgs;
+    FieldDraft draft(c, kFieldGeodesic);
+    const int rcDraft = draft.begin();
+    if (rcDraft != RTO_OK) return rcDraft;
+    GeoRun run;
+    const int rc = geo_relax(c, "rto_geodesic_field", medium, connectivity, seeds, n, lim, draft.d, run);
+    if (rc != RTO_OK) return rc;
+    float summaryMs = -1.f;
+    if (summary) {
+        DtSummary sum;
+        const int rcSum = dt_summary(c, draft.d, (unsigned)grid_voxels(c), sum);
+        if (rcSum != RTO_OK) return rcSum;
+        summaryMs = sum.ms;
+        summary->reached = sum.finite;
+        summary->max_g = sum.max;
+        summary->argmax = sum.argmax;
+        summary->reserved = 0;
+    }
+    draft.publish();
+    c->geoMedium = medium; c->geoConn = connectivity;
+    c->geoPasses = run.passes; c->geoTilesRun = run.tilesRun;
+    c->geoMs[0] = run.ms[0]; c->geoMs[1] = run.ms[1]; c->geoMs[2] = summaryMs;
     return RTO_OK;
 }
+
+int rto_download_geodesic(rto_context* c, int32_t* out, int64_t capacity) { return download_field(c, "rto_download_geodesic", kFieldGeodesic, out, capacity); }
+
+int rto_geodesic_device(rto_context* c, int32_t** d_g) { return field_device(c, "rto_geodesic_device", kFieldGeodesic, d_g); }
+
+int rto_geodesic_paths(rto_context* c, const int64_t* targets, int64_t n, int64_t max_len, int64_t* out_voxels, int64_t* out_len) {
+    using namespace rto;
+    if (!c) return RTO_E_INVALID;
+    if (n < 1) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: n is below 1");
+    if (!targets || !out_len) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: targets or out_len is NULL");
+    if (max_len < 0) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: max_len is negative");
+    if (max_len > 0 && !out_voxels) return fail(c, RTO_E_INVALID, "rto_geodesic_paths: out_voxels is NULL");
+    const int rcField = resident_field_check(c, "rto_geodesic_paths", kFieldGeodesic);
+    if (rcField != RTO_OK) return rcField;
+    const int rcTargets = voxel_list_check(c, "rto_geodesic_paths", "a target", targets, n);
+    if (rcTargets != RTO_OK) return rcTargets;
+    if (n > 0x40000000ll || (max_len > 0 && n > (int64_t)(0x7fffffffffffffffll / 8) / max_len))
+        return fail(c, RTO_E_INVALID, "rto_geodesic_paths: n x max_len is beyond what one call serves");
+    const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)grid_voxels(c) };
+    RTO_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    RTO_HIP(c, hipStreamSynchronize(s));
+    BuildScratch scratch(s);
+    long long* d_targets = nullptr; long long* d_rows = nullptr; long long* d_lens = nullptr;
+    RTO_HIP(c, scratch.alloc(&d_targets, (size_t)n));
+    RTO_HIP(c, scratch.alloc(&d_lens, (size_t)n));
+    if (max_len > 0) RTO_HIP(c, scratch.alloc(&d_rows, (size_t)n * (size_t)max_len));
+    RTO_HIP(c, hipMemcpyAsync(d_targets, targets, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    const dim3 gr((unsigned)((n + kBlock - 1) / kBlock)), b(kBlock);
+    if (c->geoConn == RTO_CONN_FULL) hipLaunchKernelGGL(k_geo_paths<true>, gr, b, 0, s, c->d_field[kFieldGeodesic], D, d_targets, (unsigned)n, (long long)max_len, d_rows, d_lens);
+    else hipLaunchKernelGGL(k_geo_paths<false>, gr, b, 0, s, c->d_field[kFieldGeodesic], D, d_targets, (unsigned)n, (long long)max_len, d_rows, d_lens);
+    RTO_HIP(c, hipGetLastError());
+    RTO_HIP(c, hipMemcpyAsync(out_len, d_lens, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (max_len > 0) RTO_HIP(c, hipMemcpyAsync(out_voxels, d_rows, (size_t)n * (size_t)max_len * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    RTO_HIP(c, hipStreamSynchronize(s));
+    return RTO_OK;
+}
+
+int rto_last_geodesic_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::geoMs, ms); }
+
+int rto_debug_geodesic_passes(const rto_context* c, int64_t* passes, int64_t* tiles_run) {
+    if (!c || !passes) return RTO_E_INVALID;
+    *passes = c->geoPasses;
+    if (tiles_run) *tiles_run = c->geoTilesRun;
+    return RTO_OK;
+}
+
+int rto_debug_set_geodesic_look(rto_context* c, int passes_per_look) {
+    if (!c) return RTO_E_INVALID;
+    if (passes_per_look < 1 || passes_per_look > kMaxLook) return fail(c, RTO_E_INVALID, "rto_debug_set_geodesic_look: 1 to 64 passes per look");
+    c->geoLook = passes_per_look;
+    return RTO_OK;
+}
+
+int rto_edit_geodesic(rto_context* c, int medium, int connectivity, const int64_t* seeds, int64_t n, int64_t limit, int64_t* changed) {
+    using namespace rto;
+    if (!c) return RTO_E_INVALID;
+    if (changed) *changed = 0;
+    unsigned lim = 0u;
+    const int rcArgs = geo_check_args(c, "rto_edit_geodesic", medium, connectivity, seeds, n, limit, &lim);
+    if (rcArgs != RTO_OK) return rcArgs;
+    const unsigned from = medium == RTO_SET_SOLID ? 1u : 0u, to = medium == RTO_SET_SOLID ? 0u : 1u;
+    return edit_by_field(
+        c, c->geoEditMs, changed,
+        [&](int* d_field) {
+            GeoRun run;
+            return geo_relax(c, "rto_edit_geodesic", medium, connectivity, seeds, n, lim, d_field, run);
+        },
+        // only voxels of the medium hold a finite value, so the threshold of rto_edit_morphology is the flood's flip as well
+        [&](const int* d_field, unsigned nvox, unsigned blocks, unsigned long long* d_count) {
+            if (nvox % kCcVec == 0) hipLaunchKernelGGL(k_morph_flip<true>, dim3(blocks), dim3(kBlock), 0, c->stream, c->d_vox, d_field, (const uint8_t*)nullptr, nvox, from, to, d_count);
+            else hipLaunchKernelGGL(k_morph_flip<false>, dim3(blocks), dim3(kBlock), 0, c->stream, c->d_vox, d_field, (const uint8_t*)nullptr, nvox, from, to, d_count);
+        });
+}
+
+int rto_last_geodesic_edit_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::geoEditMs, ms); }
 
 }  // extern "C"

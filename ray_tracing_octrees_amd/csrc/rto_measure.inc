@@ -426,16 +426,16 @@ int rto_measure_components(rto_context* c, rto_measure* total) {
     RTO_HIP(c, hipMemsetAsync(table.d, 0, ((size_t)count + 1) * sizeof(rto_measure), s));
     BuildScratch scratch(s);
     if (count) {
-        const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
-        const unsigned tiles = (unsigned)((long long)tilesX * tilesY * tilesZ);
+        const CcTiles T(c->voxDim);
+        const unsigned tiles = (unsigned)T.count();
         rto_measure* d_slots = nullptr;                                 // one per tile; every workgroup writes its own
         RTO_HIP(c, scratch.alloc(&d_slots, (size_t)tiles));
         const dim3 g(tiles), b(kBlock);
         const bool wide = D.x % kCcVec == 0, full = c->ccConn == RTO_CONN_FULL;
-        if (wide && full) hipLaunchKernelGGL((k_measure<true, true>), g, b, 0, s, c->d_ccLabels, D, tilesX, tilesY, table.d, d_slots);
-        else if (wide) hipLaunchKernelGGL((k_measure<true, false>), g, b, 0, s, c->d_ccLabels, D, tilesX, tilesY, table.d, d_slots);
-        else if (full) hipLaunchKernelGGL((k_measure<false, true>), g, b, 0, s, c->d_ccLabels, D, tilesX, tilesY, table.d, d_slots);
-        else hipLaunchKernelGGL((k_measure<false, false>), g, b, 0, s, c->d_ccLabels, D, tilesX, tilesY, table.d, d_slots);
+        if (wide && full) hipLaunchKernelGGL((k_measure<true, true>), g, b, 0, s, c->d_ccLabels, D, T.x, T.y, table.d, d_slots);
+        else if (wide) hipLaunchKernelGGL((k_measure<true, false>), g, b, 0, s, c->d_ccLabels, D, T.x, T.y, table.d, d_slots);
+        else if (full) hipLaunchKernelGGL((k_measure<false, true>), g, b, 0, s, c->d_ccLabels, D, T.x, T.y, table.d, d_slots);
+        else hipLaunchKernelGGL((k_measure<false, false>), g, b, 0, s, c->d_ccLabels, D, T.x, T.y, table.d, d_slots);
         RTO_HIP(c, hipGetLastError());
         hipLaunchKernelGGL(k_measure_fold, dim3((tiles + kBlock - 1) / kBlock), b, 0, s, d_slots, tiles, table.d);
         RTO_HIP(c, hipGetLastError());
@@ -476,10 +476,6 @@ int rto_measures_device(rto_context* c, rto_measure** d_measures, int64_t* count
     return RTO_OK;
 }
 
-int rto_last_measure_ms(const rto_context* c, float ms[2]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    ms[0] = c->measureMs[0]; ms[1] = c->measureMs[1];
-    return RTO_OK;
-}
+int rto_last_measure_ms(const rto_context* c, float ms[2]) { return copy_last_ms(c, &rto_context::measureMs, ms); }
 
 }  // extern "C"

@@ -346,10 +346,6 @@ int rto_download_mesh(rto_context* c, float* tris, int64_t capacity, int32_t* tr
     return RTO_OK;
 }
 
-int rto_last_mesh_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->meshMs[i];
-    return RTO_OK;
-}
+int rto_last_mesh_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::meshMs, ms); }
 
 }  // extern "C"

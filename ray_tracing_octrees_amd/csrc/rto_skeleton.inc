@@ -32,7 +32,6 @@ namespace rto {
 constexpr int kSkRowsY = kCcTileY + 2, kSkRowsZ = kCcTileZ + 2;          // halo rows
 constexpr int kSkRows = kSkRowsY * kSkRowsZ;                             // 100 row windows, 800 bytes of LDS
 constexpr int kSkTileRows = kCcTileY * kCcTileZ;                         // 64 words of a tile
-constexpr int kSkMaxLook = 64;                                           // passes per look of the host at the device, at most
 static_assert(kCcTileX == 32, "a tile row is one word");
 static_assert(kBlock == (kCcTileX / 2) * (kCcTileY / 2) * (kCcTileZ / 2), "one thread per voxel of a subfield");
 static_assert(kSkRows <= kBlock && kSkTileRows <= kWave, "one thread per row window; one wave for the tile's words");
@@ -304,10 +303,7 @@ int skel_check_args(rto_context* c, const char* who, int set, int connectivity, 
     if (max_passes < 1) return fail(c, RTO_E_INVALID, w + ": max_passes is below 1");
     const int rcGrid = resident_grid_check(c, who, ": the field is 32-bit");
     if (rcGrid != RTO_OK) return rcGrid;
-    const int64_t nvox = grid_voxels(c);
-    for (int64_t i = 0; i < n; i++)
-        if (anchors[i] < 0 || anchors[i] >= nvox) return fail(c, RTO_E_INVALID, w + ": an anchor is not a voxel of the grid");
-    return RTO_OK;
+    return voxel_list_check(c, who, "an anchor", anchors, n);
 }
 
 // The field into d_out (one int32 per voxel; arguments already checked).  The context is not touched, but for the stream.
@@ -320,20 +316,18 @@ int skel_thin(rto_context* c, const char* who, int set, int connectivity, int mo
     hipStream_t s = c->stream;
     StreamEvents<3> events;
     RTO_HIP(c, events.create());
-    const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
-    const size_t tiles = (size_t)tilesX * tilesY * tilesZ;
+    const CcTiles T(c->voxDim);
+    const size_t tiles = T.count();
     const unsigned setValue = set == RTO_SET_SOLID ? 1u : 0u;
     const bool full = connectivity == RTO_CONN_FULL, curve = mode == RTO_SKEL_CURVE;
     BuildScratch scratch(s);
-    long long* d_anchors = nullptr; unsigned* d_bits = nullptr; int* d_stamp = nullptr; unsigned* d_removed = nullptr; unsigned* d_runs = nullptr;
-    if (n > 0) RTO_HIP(c, scratch.alloc(&d_anchors, (size_t)n));
+    VoxelList d_anchors; unsigned* d_bits = nullptr; int* d_stamp = nullptr; unsigned* d_removed = nullptr; unsigned* d_runs = nullptr;
+    RTO_HIP(c, d_anchors.upload(scratch, anchors, n, s));
     RTO_HIP(c, scratch.alloc(&d_bits, 3 * (size_t)D.words));            // X, M, A
     RTO_HIP(c, scratch.alloc(&d_stamp, tiles));
-    RTO_HIP(c, scratch.alloc(&d_removed, (size_t)kSkMaxLook));
+    RTO_HIP(c, scratch.alloc(&d_removed, (size_t)kMaxLook));
     RTO_HIP(c, scratch.alloc(&d_runs, tiles));
     unsigned* d_X = d_bits; unsigned* d_M = d_bits + D.words; unsigned* d_A = d_bits + 2 * (size_t)D.words;
-    static_assert(sizeof(long long) == sizeof(int64_t), "anchors travel as they are");
-    if (n > 0) RTO_HIP(c, hipMemcpyAsync(d_anchors, anchors, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
     RTO_HIP(c, events.record(0, s));
     RTO_HIP(c, hipMemsetAsync(d_A, 0, (size_t)D.words * sizeof(unsigned), s));
     RTO_HIP(c, hipMemsetAsync(d_stamp, 0, tiles * sizeof(int), s));
@@ -342,44 +336,36 @@ int skel_thin(rto_context* c, const char* who, int set, int connectivity, int mo
     if (D.x % 32 == 0) hipLaunchKernelGGL(k_skel_init<true>, perWord, b, 0, s, c->d_vox, D, setValue, d_X, d_out);
     else hipLaunchKernelGGL(k_skel_init<false>, perWord, b, 0, s, c->d_vox, D, setValue, d_X, d_out);
     RTO_HIP(c, hipGetLastError());
-    for (int64_t at = 0; at < n; at += 0x40000000ll) {                  // a launch's thread count fits 32 bits
-        const unsigned part = (unsigned)std::min<int64_t>(n - at, 0x40000000ll);
-        hipLaunchKernelGGL(k_skel_anchors, dim3((part + kBlock - 1) / kBlock), b, 0, s, d_anchors + at, part, D, d_A);
-        RTO_HIP(c, hipGetLastError());
-    }
+    const int rcAnchors = d_anchors.in_parts(c, [&](const long long* part, unsigned count) {
+        hipLaunchKernelGGL(k_skel_anchors, dim3((count + kBlock - 1) / kBlock), b, 0, s, part, count, D, d_A);
+    });
+    if (rcAnchors != RTO_OK) return rcAnchors;
     RTO_HIP(c, events.record(1, s));
-    // passes until one removes nothing; `look` of them between two looks at their flags.  Passes behind that one remove nothing
-    // either, so how many go out together changes no value.  Every pass but the last removes a voxel: voxels + 1 passes at most.
+    // passes until one removes nothing (its word: did it remove a voxel); `look` of them between two looks (look_at_passes).
+    // Every pass but the last removes a voxel: voxels + 1 passes at most.
     const int64_t cap = nvox + 1;
     const int64_t most = std::min<int64_t>(max_passes, cap);
-    const int look = std::max(1, std::min(c->skelLook, kSkMaxLook));
-    int64_t passes = 0, launches = 0, tilesRun = 0;
+    const int look = std::max(1, std::min(c->skelLook, kMaxLook));
+    int64_t passes = 0, launches = 0, tilesRun = 0, flagSum = 0;        // flagSum: the words' sum, of no use for flags
     bool settled = false;
-    unsigned flags[kSkMaxLook];
     while (!settled && passes < most) {
         const int launch = (int)std::min<int64_t>(look, most - passes);
-        RTO_HIP(c, hipMemsetAsync(d_removed, 0, kSkMaxLook * sizeof(unsigned), s));
-        for (int i = 0; i < launch; i++) {
+        const int rcLook = look_at_passes(c, d_removed, launch, [&](int i, unsigned* cnt) -> int {
             const int pass = (int)(passes + i + 1);
             if (full) hipLaunchKernelGGL(k_skel_mark<true>, perWord, b, 0, s, d_X, d_A, D, d_M);
             else hipLaunchKernelGGL(k_skel_mark<false>, perWord, b, 0, s, d_X, d_A, D, d_M);
             RTO_HIP(c, hipGetLastError());
             for (int sub = 0; sub < 8; sub++) {
                 const dim3 gr((unsigned)tiles);
-                unsigned* cnt = d_removed + i;
-                if (curve) hipLaunchKernelGGL((k_skel_step<true, true>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, tilesX, tilesY, tilesZ, pass, sub, cnt, d_runs);
-                else if (full) hipLaunchKernelGGL((k_skel_step<true, false>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, tilesX, tilesY, tilesZ, pass, sub, cnt, d_runs);
-                else hipLaunchKernelGGL((k_skel_step<false, false>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, tilesX, tilesY, tilesZ, pass, sub, cnt, d_runs);
+                if (curve) hipLaunchKernelGGL((k_skel_step<true, true>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, T.x, T.y, T.z, pass, sub, cnt, d_runs);
+                else if (full) hipLaunchKernelGGL((k_skel_step<true, false>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, T.x, T.y, T.z, pass, sub, cnt, d_runs);
+                else hipLaunchKernelGGL((k_skel_step<false, false>), gr, b, 0, s, d_X, d_M, d_out, d_stamp, D, T.x, T.y, T.z, pass, sub, cnt, d_runs);
                 RTO_HIP(c, hipGetLastError());
             }
-        }
+            return RTO_OK;
+        }, passes, flagSum, settled);
+        if (rcLook != RTO_OK) return rcLook;
         launches += 9 * (int64_t)launch;
-        RTO_HIP(c, hipMemcpyAsync(flags, d_removed, (size_t)launch * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
-        for (int i = 0; i < launch && !settled; i++) {
-            passes++;
-            settled = flags[i] == 0u;
-        }
     }
     if (!settled && passes >= cap) return fail(c, RTO_E_INTERNAL, std::string(who) + ": the thinning did not end within voxels + 1 passes");
     RTO_HIP(c, events.record(2, s));
@@ -406,65 +392,38 @@ int rto_skeleton_field(rto_context* c, int set, int connectivity, int mode, cons
     if (!c) return RTO_E_INVALID;
     const int rcArgs = skel_check_args(c, "rto_skeleton_field", set, connectivity, mode, anchors, n, max_passes);
     if (rcArgs != RTO_OK) return rcArgs;
-    RTO_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned nvox = (unsigned)grid_voxels(c);
-    int* d_new = nullptr;
-    RTO_HIP(c, hipMalloc(&d_new, (size_t)nvox * sizeof(int)));
-    struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
+    FieldDraft draft(c, kFieldSkeleton);
+    const int rcDraft = draft.begin();
+    if (rcDraft != RTO_OK) return rcDraft;
     SkelRun run;
-    const int rc = skel_thin(c, "rto_skeleton_field", set, connectivity, mode, anchors, n, max_passes, d_new, run);
+    const int rc = skel_thin(c, "rto_skeleton_field", set, connectivity, mode, anchors, n, max_passes, draft.d, run);
     if (rc != RTO_OK) return rc;
     float summaryMs = -1.f;
     if (summary) {
-        StreamEvents<2> events;
-        RTO_HIP(c, events.create());
-        BuildScratch scratch(s);
-        unsigned long long* d_red = nullptr;
-        RTO_HIP(c, scratch.alloc(&d_red, 3));
-        RTO_HIP(c, hipMemsetAsync(d_red, 0, 3 * sizeof(unsigned long long), s));
-        RTO_HIP(c, events.record(0, s));
-        const unsigned blocks = std::min<unsigned>((nvox + kBlock - 1) / kBlock, 4096u);
-        hipLaunchKernelGGL(k_skel_summary, dim3(blocks), dim3(kBlock), 0, s, d_new, nvox, d_red);
-        RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, events.record(1, s));
+        const unsigned nvox = (unsigned)grid_voxels(c);
         unsigned long long red[3] = { 0ull, 0ull, 0ull };
-        RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
-        RTO_HIP(c, hipStreamSynchronize(s));
-        RTO_HIP(c, events.elapsed(0, 1, &summaryMs));
+        const int rcSum = reduce_words(c, [&](unsigned long long* d_red) {
+            const unsigned blocks = std::min<unsigned>((nvox + kBlock - 1) / kBlock, 4096u);
+            hipLaunchKernelGGL(k_skel_summary, dim3(blocks), dim3(kBlock), 0, c->stream, draft.d, nvox, d_red);
+        }, red, &summaryMs);
+        if (rcSum != RTO_OK) return rcSum;
         summary->kept = (int64_t)red[0];
         summary->removed = (int64_t)red[1];
         summary->passes = (int64_t)red[2];
         summary->reserved = 0;
     }
-    free_skeleton(c);
-    c->d_skel = d_new;
-    guard.p = nullptr;
+    draft.publish();
     c->skelSet = set; c->skelConn = connectivity; c->skelMode = mode;
     c->skelLaunches = run.launches; c->skelTilesRun = run.tilesRun;
     c->skelMs[0] = run.ms[0]; c->skelMs[1] = run.ms[1]; c->skelMs[2] = summaryMs;
     return RTO_OK;
 }
 
-int rto_download_skeleton(rto_context* c, int32_t* out, int64_t capacity) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_skel) return fail(c, RTO_E_INVALID, "rto_download_skeleton: no skeleton field is resident (not made yet, or the grid has changed since)");
-    return download_resident(c, "rto_download_skeleton", out, capacity, c->d_skel, grid_voxels(c), sizeof(int32_t));
-}
+int rto_download_skeleton(rto_context* c, int32_t* out, int64_t capacity) { return download_field(c, "rto_download_skeleton", kFieldSkeleton, out, capacity); }
 
-int rto_skeleton_device(rto_context* c, int32_t** d_k) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_skel) return fail(c, RTO_E_INVALID, "rto_skeleton_device: no skeleton field is resident (not made yet, or the grid has changed since)");
-    if (d_k) *d_k = c->d_skel;
-    return RTO_OK;
-}
+int rto_skeleton_device(rto_context* c, int32_t** d_k) { return field_device(c, "rto_skeleton_device", kFieldSkeleton, d_k); }
 
-int rto_last_skeleton_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->skelMs[i];
-    return RTO_OK;
-}
+int rto_last_skeleton_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::skelMs, ms); }
 
 int rto_debug_skeleton_passes(const rto_context* c, int64_t* launches, int64_t* tiles_run) {
     if (!c || !launches) return RTO_E_INVALID;
@@ -475,7 +434,7 @@ int rto_debug_skeleton_passes(const rto_context* c, int64_t* launches, int64_t* 
 
 int rto_debug_set_skeleton_look(rto_context* c, int passes_per_look) {
     if (!c) return RTO_E_INVALID;
-    if (passes_per_look < 1 || passes_per_look > rto::kSkMaxLook) return fail(c, RTO_E_INVALID, "rto_debug_set_skeleton_look: 1 to 64 passes per look");
+    if (passes_per_look < 1 || passes_per_look > kMaxLook) return fail(c, RTO_E_INVALID, "rto_debug_set_skeleton_look: 1 to 64 passes per look");
     c->skelLook = passes_per_look;
     return RTO_OK;
 }
@@ -486,43 +445,17 @@ int rto_edit_skeleton(rto_context* c, int set, int connectivity, int mode, const
     if (changed) *changed = 0;
     const int rcArgs = skel_check_args(c, "rto_edit_skeleton", set, connectivity, mode, anchors, n, max_passes);
     if (rcArgs != RTO_OK) return rcArgs;
-    RTO_HIP(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
-    const unsigned nvox = (unsigned)grid_voxels(c);
-    float ms[3] = { -1.f, -1.f, -1.f };
-    unsigned long long count = 0;
-    {
-        StreamEvents<2> events;
-        RTO_HIP(c, events.create());
-        BuildScratch scratch(s);
-        int* d_field = nullptr;
-        ChangedCount d_count;
-        RTO_HIP(c, scratch.alloc(&d_field, (size_t)nvox));
-        RTO_HIP(c, d_count.alloc(scratch));
-        RTO_HIP(c, events.record(0, s));
-        SkelRun run;
-        const int rc = skel_thin(c, "rto_edit_skeleton", set, connectivity, mode, anchors, n, max_passes, d_field, run);
-        if (rc != RTO_OK) return rc;                                    // the grid has not been written yet
-        RTO_HIP(c, d_count.clear(s));
-        const unsigned blocks = (unsigned)((((int64_t)nvox + kCcVec - 1) / kCcVec + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_skel_flip, dim3(blocks), dim3(kBlock), 0, s, c->d_vox, d_field, nvox, set == RTO_SET_SOLID ? 0u : 1u, d_count.d);
-        RTO_HIP(c, hipGetLastError());
-        RTO_HIP(c, events.record(1, s));
-        RTO_HIP(c, d_count.read(s, &count));
-        RTO_HIP(c, events.elapsed(0, 1, &ms[0]));
-    }
-    for (int i = 0; i < 3; i++) c->skelEditMs[i] = ms[i];
-    if (changed) *changed = (int64_t)count;
-    if (count == 0) return RTO_OK;           // the grid is byte for byte what it was: octree, triangles, labels and every field stay
-
-    return rebuild_from_resident_grid(c, c->d_triOffset != nullptr, &c->skelEditMs[1], &c->skelEditMs[2]);
+    return edit_by_field(
+        c, c->skelEditMs, changed,
+        [&](int* d_field) {
+            SkelRun run;
+            return skel_thin(c, "rto_edit_skeleton", set, connectivity, mode, anchors, n, max_passes, d_field, run);
+        },
+        [&](const int* d_field, unsigned nvox, unsigned blocks, unsigned long long* d_count) {
+            hipLaunchKernelGGL(k_skel_flip, dim3(blocks), dim3(kBlock), 0, c->stream, c->d_vox, d_field, nvox, set == RTO_SET_SOLID ? 0u : 1u, d_count);
+        });
 }
 
-int rto_last_skeleton_edit_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->skelEditMs[i];
-    return RTO_OK;
-}
+int rto_last_skeleton_edit_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::skelEditMs, ms); }
 
 }  // extern "C"

@@ -190,17 +190,15 @@ int rto_thickness_field(rto_context* c, int medium, float max_radius, rto_thick_
     }
     const int rcGrid = dt_check_grid(c, "rto_thickness_field");
     if (rcGrid != RTO_OK) return rcGrid;
-    RTO_HIP(c, hipSetDevice(c->device));
+    FieldDraft draft(c, kFieldThickness);
+    const int rcDraft = draft.begin();
+    if (rcDraft != RTO_OK) return rcDraft;
     hipStream_t s = c->stream;
-    RTO_HIP(c, hipStreamSynchronize(s));
     const CcDims D{ c->voxDim[0], c->voxDim[1], c->voxDim[2], (unsigned)grid_voxels(c) };
     const unsigned n = D.n;
-    int* d_new = nullptr;
-    RTO_HIP(c, hipMalloc(&d_new, (size_t)n * sizeof(int)));
-    struct Guard { int* p; ~Guard() { (void)hipFree(p); } } guard{ d_new };
     int h = 0;
     while ((h + 1) * (h + 1) < cap) h++;                                // isqrt(cap - 1)
-    const int tilesX = (D.x + kCcTileX - 1) / kCcTileX, tilesY = (D.y + kCcTileY - 1) / kCcTileY, tilesZ = (D.z + kCcTileZ - 1) / kCcTileZ;
+    const CcTiles T(c->voxDim);
     // The offset table depends on c alone: the context keeps the one of the last c, and a call at the same c uploads nothing.
     // A new one is the call's own until the call has succeeded, like the field.
     struct TabGuard { int* p; ~TabGuard() { (void)hipFree(p); } } newTab{ nullptr };
@@ -227,10 +225,10 @@ int rto_thickness_field(rto_context* c, int medium, float max_radius, rto_thick_
         RTO_HIP(c, hipMemsetAsync(d_red, 0, ((size_t)kThickMaxC + 1) * sizeof(unsigned long long), s));
         RTO_HIP(c, hipMemsetAsync(d_red + kThickMaxC + 1, 0xff, sizeof(unsigned long long), s));
         RTO_HIP(c, events.record(0, s));
-        hipLaunchKernelGGL(k_thick_gather, dim3((unsigned)((size_t)tilesX * tilesY * tilesZ)), dim3(kBlock), 0, s, d_D, D, tilesX, tilesY, cap, h, d_tab, d_new);
+        hipLaunchKernelGGL(k_thick_gather, dim3((unsigned)T.count()), dim3(kBlock), 0, s, d_D, D, T.x, T.y, cap, h, d_tab, draft.d);
         RTO_HIP(c, hipGetLastError());
         RTO_HIP(c, events.record(1, s));
-        hipLaunchKernelGGL(k_thick_summary, dim3((n + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, s, d_new, n, cap, d_red, d_red + kThickMaxC + 1);
+        hipLaunchKernelGGL(k_thick_summary, dim3((n + kDtChunk - 1) / kDtChunk), dim3(kBlock), 0, s, draft.d, n, cap, d_red, d_red + kThickMaxC + 1);
         RTO_HIP(c, hipGetLastError());
         RTO_HIP(c, events.record(2, s));
         RTO_HIP(c, hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s));
@@ -247,9 +245,7 @@ int rto_thickness_field(rto_context* c, int medium, float max_radius, rto_thick_
         summary->thin = thin;
         summary->medium = mediumCount;
     }
-    free_thickness(c);
-    c->d_thick = d_new;
-    guard.p = nullptr;
+    draft.publish();
     if (newTab.p) {
         (void)hipFree(c->d_thickTab);
         c->d_thickTab = newTab.p; c->thickTabCap = cap;
@@ -262,22 +258,14 @@ int rto_thickness_field(rto_context* c, int medium, float max_radius, rto_thick_
     return RTO_OK;
 }
 
-int rto_download_thickness(rto_context* c, int32_t* out, int64_t capacity) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_thick) return fail(c, RTO_E_INVALID, "rto_download_thickness: no thickness field is resident (not made yet, or the grid has changed since)");
-    return download_resident(c, "rto_download_thickness", out, capacity, c->d_thick, grid_voxels(c), sizeof(int32_t));
-}
+int rto_download_thickness(rto_context* c, int32_t* out, int64_t capacity) { return download_field(c, "rto_download_thickness", kFieldThickness, out, capacity); }
 
-int rto_thickness_device(rto_context* c, int32_t** d_t2) {
-    if (!c) return RTO_E_INVALID;
-    if (!c->d_thick) return fail(c, RTO_E_INVALID, "rto_thickness_device: no thickness field is resident (not made yet, or the grid has changed since)");
-    if (d_t2) *d_t2 = c->d_thick;
-    return RTO_OK;
-}
+int rto_thickness_device(rto_context* c, int32_t** d_t2) { return field_device(c, "rto_thickness_device", kFieldThickness, d_t2); }
 
 int rto_thickness_histogram(rto_context* c, int64_t* out, int64_t capacity, int64_t* bins) {
     if (!c) return RTO_E_INVALID;
-    if (!c->d_thick) return fail(c, RTO_E_INVALID, "rto_thickness_histogram: no thickness field is resident (not made yet, or the grid has changed since)");
+    const int rcField = resident_field_check(c, "rto_thickness_histogram", kFieldThickness);
+    if (rcField != RTO_OK) return rcField;
     if (out && capacity < (int64_t)c->thickCap + 1) return fail(c, RTO_E_INVALID, "rto_thickness_histogram: capacity is below c + 1");
     if (bins) *bins = (int64_t)c->thickCap + 1;
     if (out) for (int t = 0; t <= c->thickCap; t++) out[t] = c->thickBins[t];
@@ -291,10 +279,6 @@ int rto_debug_thickness_table(const rto_context* c, int* table_c, int64_t* built
     return RTO_OK;
 }
 
-int rto_last_thickness_ms(const rto_context* c, float ms[3]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 3; i++) ms[i] = c->thickMs[i];
-    return RTO_OK;
-}
+int rto_last_thickness_ms(const rto_context* c, float ms[3]) { return copy_last_ms(c, &rto_context::thickMs, ms); }
 
 }  // extern "C"

@@ -445,10 +445,6 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
     return RTO_OK;
 }
 
-int rto_last_voxelize_ms(const rto_context* c, float ms[4]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    for (int i = 0; i < 4; i++) ms[i] = c->voxelizeMs[i];
-    return RTO_OK;
-}
+int rto_last_voxelize_ms(const rto_context* c, float ms[4]) { return copy_last_ms(c, &rto_context::voxelizeMs, ms); }
 
 }  // extern "C"

@@ -575,6 +575,28 @@ class Context:
         if rc != RTO_OK:
             raise RtoError(rc, self._L.rto_last_error(self._h).decode())
 
+    def _last_ms(self, symbol: str, n: int):
+        """The n device times an rto_last_*_ms entry reports, as a tuple."""
+        ms = (C.c_float * n)()
+        self._check(getattr(self._L, symbol)(self._h, ms))
+        return tuple(ms)
+
+    def _device_pointer(self, symbol: str) -> int:
+        """The device pointer an rto_*_device entry of a resident int32 field reports."""
+        p = C.c_void_p()
+        self._check(getattr(self._L, symbol)(self._h, C.byref(p)))
+        return p.value or 0
+
+    def _resident_field(self, device_symbol: str, download_symbol: str, outputs: int = 1) -> np.ndarray:
+        """A resident per-voxel int32 product as (dimZ, dimY, dimX).  The device getter is asked first, with none of its `outputs`
+        wanted: when nothing is resident the error is its own, raised before the dims are asked for."""
+        self._check(getattr(self._L, device_symbol)(self._h, *([None] * outputs)))
+        dims = (C.c_int * 3)()
+        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        self._check(getattr(self._L, download_symbol)(self._h, out.ctypes.data, out.size))
+        return out
+
     @property
     def device_name(self) -> str:
         buf = C.create_string_buffer(256)
@@ -1033,9 +1055,7 @@ class Context:
 
     def last_edit_ms(self):
         """Device ms of the last edit: (brushes, octree rebuild, triangle rebuild); -1 for a step that did not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_edit_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_edit_ms", 3)
 
     # -- connected components --------------------------------------------------
     def label_components(self, set: int = SET_SOLID, connectivity: int = CONN_FACE) -> np.ndarray:
@@ -1059,12 +1079,7 @@ class Context:
 
     def component_labels(self) -> np.ndarray:
         """The resident label volume as int32 (dimZ, dimY, dimX): the component's number, -1 outside the set."""
-        self._check(self._L.rto_labels_device(self._h, None, None, None))     # no labels resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_labels(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_labels_device", "rto_download_labels", outputs=3)
 
     def component_labels_device(self):
         """(device pointer of the int32 label volume, device pointer of the 48-byte table records, count)."""
@@ -1074,9 +1089,7 @@ class Context:
 
     def last_components_ms(self):
         """Device ms of the last labelling: (tile-local labelling, merging, flatten + ranking, statistics); -1: not run."""
-        ms = (C.c_float * 4)()
-        self._check(self._L.rto_last_components_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_components_ms", 4)
 
     def components_passes(self) -> int:
         """Merge launches of the last labelling (2: one merge, one clean check)."""
@@ -1117,9 +1130,7 @@ class Context:
 
     def last_measure_ms(self):
         """Device ms of the last measure_components: (the measuring kernels, the total); -1: not run."""
-        ms = (C.c_float * 2)()
-        self._check(self._L.rto_last_measure_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_measure_ms", 2)
 
     def topology(self, set: int = SET_SOLID, connectivity: int = CONN_FACE):
         """(pieces, tunnels, cavities) of the set under `connectivity`.  Three steps: label the complement under the dual
@@ -1147,24 +1158,15 @@ class Context:
 
     def distance(self) -> np.ndarray:
         """The resident field (rto_download_distance)."""
-        self._check(self._L.rto_distance_device(self._h, None))             # no field resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_distance(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_distance_device", "rto_download_distance")
 
     def distance_device(self) -> int:
         """The device pointer of the resident int32 field."""
-        p = C.c_void_p()
-        self._check(self._L.rto_distance_device(self._h, C.byref(p)))
-        return p.value or 0
+        return self._device_pointer("rto_distance_device")
 
     def last_distance_ms(self):
         """Device ms of the last distance_field: (x pass, y pass, z pass, summary); -1: not run."""
-        ms = (C.c_float * 4)()
-        self._check(self._L.rto_last_distance_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_distance_ms", 4)
 
     def edit_morphology(self, op: int, radius: float) -> int:
         """rto_edit_morphology: MORPH_DILATE / MORPH_ERODE / MORPH_OPEN / MORPH_CLOSE by `radius` (world units), rebuilt as
@@ -1175,9 +1177,7 @@ class Context:
 
     def last_morphology_ms(self):
         """Device ms of the last edit_morphology: (transforms and flips, octree rebuild, triangle rebuild); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_morphology_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_morphology_ms", 3)
 
     # -- geodesic fields, paths and flood edits ---------------------------------------
     def _voxel_indices(self, voxels) -> np.ndarray:
@@ -1204,18 +1204,11 @@ class Context:
 
     def geodesic(self) -> np.ndarray:
         """The resident geodesic field (rto_download_geodesic)."""
-        self._check(self._L.rto_geodesic_device(self._h, None))             # no field resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_geodesic(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_geodesic_device", "rto_download_geodesic")
 
     def geodesic_device(self) -> int:
         """The device pointer of the resident int32 geodesic field."""
-        p = C.c_void_p()
-        self._check(self._L.rto_geodesic_device(self._h, C.byref(p)))
-        return p.value or 0
+        return self._device_pointer("rto_geodesic_device")
 
     def geodesic_paths(self, targets, max_len: int):
         """rto_geodesic_paths on the resident field: (rows, lengths) -- rows (n, max_len) int64, each the first voxels of the path
@@ -1239,15 +1232,11 @@ class Context:
 
     def last_geodesic_ms(self):
         """Device ms of the last geodesic_field: (init, relaxation, summary); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_geodesic_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_geodesic_ms", 3)
 
     def last_geodesic_edit_ms(self):
         """Device ms of the last edit_geodesic: (field and flip, octree rebuild, triangle rebuild); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_geodesic_edit_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_geodesic_edit_ms", 3)
 
     def geodesic_passes(self, tiles: bool = False):
         """Relaxation launches of the last geodesic_field, the closing one that found no tile included; with tiles=True the pair
@@ -1274,18 +1263,11 @@ class Context:
 
     def skeleton(self) -> np.ndarray:
         """The resident skeleton field (rto_download_skeleton)."""
-        self._check(self._L.rto_skeleton_device(self._h, None))             # no field resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_skeleton(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_skeleton_device", "rto_download_skeleton")
 
     def skeleton_device(self) -> int:
         """The device pointer of the resident int32 skeleton field."""
-        p = C.c_void_p()
-        self._check(self._L.rto_skeleton_device(self._h, C.byref(p)))
-        return p.value or 0
+        return self._device_pointer("rto_skeleton_device")
 
     def edit_skeleton(self, set: int = SET_SOLID, connectivity: int = CONN_FULL, mode: int = SKEL_TOPOLOGY, anchors=(), max_passes=None) -> int:
         """rto_edit_skeleton: replaces `set` by its skeleton (every voxel the thinning removes is flipped), rebuilt as edit_voxels
@@ -1298,15 +1280,11 @@ class Context:
 
     def last_skeleton_ms(self):
         """Device ms of the last skeleton_field: (init, thinning, summary); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_skeleton_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_skeleton_ms", 3)
 
     def last_skeleton_edit_ms(self):
         """Device ms of the last edit_skeleton: (field and flip, octree rebuild, triangle rebuild); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_skeleton_edit_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_skeleton_edit_ms", 3)
 
     def skeleton_passes(self):
         """(kernel launches, tiles run summed over the sub-steps) of the last skeleton_field's thinning."""
@@ -1344,24 +1322,15 @@ class Context:
 
     def exposure(self) -> np.ndarray:
         """The resident exposure field (rto_download_exposure)."""
-        self._check(self._L.rto_exposure_device(self._h, None))             # no field resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_exposure(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_exposure_device", "rto_download_exposure")
 
     def exposure_device(self) -> int:
         """The device pointer of the resident int32 exposure field."""
-        p = C.c_void_p()
-        self._check(self._L.rto_exposure_device(self._h, C.byref(p)))
-        return p.value or 0
+        return self._device_pointer("rto_exposure_device")
 
     def last_exposure_ms(self):
         """Device ms of the last exposure_field: (prepare, march, summary); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_exposure_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_exposure_ms", 3)
 
     # -- local thickness fields ----------------------------------------------------------
     def thickness_field(self, medium: int = SET_SOLID, max_radius: float | None = None):
@@ -1377,18 +1346,11 @@ class Context:
 
     def thickness(self) -> np.ndarray:
         """The resident thickness field (rto_download_thickness)."""
-        self._check(self._L.rto_thickness_device(self._h, None))            # no field resident: that error, before the dims are asked for
-        dims = (C.c_int * 3)()
-        self._check(self._L.rto_download_voxels(self._h, None, 0, dims))
-        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
-        self._check(self._L.rto_download_thickness(self._h, out.ctypes.data, out.size))
-        return out
+        return self._resident_field("rto_thickness_device", "rto_download_thickness")
 
     def thickness_device(self) -> int:
         """The device pointer of the resident int32 thickness field."""
-        p = C.c_void_p()
-        self._check(self._L.rto_thickness_device(self._h, C.byref(p)))
-        return p.value or 0
+        return self._device_pointer("rto_thickness_device")
 
     def thickness_histogram(self) -> np.ndarray:
         """rto_thickness_histogram: int64 bins[t], t = 0 .. c: the medium voxels of the resident field with t2 = t."""
@@ -1400,9 +1362,7 @@ class Context:
 
     def last_thickness_ms(self):
         """Device ms of the last thickness_field: (transform, gather, summary); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_thickness_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_thickness_ms", 3)
 
     def thickness_table(self):
         """rto_debug_thickness_table: (the c the gather's kept offset table was made for, 0: none yet; tables built so far)."""
@@ -1487,9 +1447,7 @@ class Context:
 
     def last_voxelize_ms(self):
         """Device ms of the last voxelization: (face setup + scan, fill, recentring reduction, octree build); -1: not run."""
-        ms = (C.c_float * 4)()
-        self._check(self._L.rto_last_voxelize_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_voxelize_ms", 4)
 
     # -- mesh extraction ---------------------------------------------------
     @staticmethod
@@ -1534,9 +1492,7 @@ class Context:
 
     def last_mesh_ms(self):
         """Device ms of the last extraction: (count + cull, ranking passes, emit); -1: not run."""
-        ms = (C.c_float * 3)()
-        self._check(self._L.rto_last_mesh_ms(self._h, ms))
-        return tuple(ms)
+        return self._last_ms("rto_last_mesh_ms", 3)
 
     def scene_bounds(self) -> SceneBounds:
         b = SceneBounds()

@@ -518,8 +518,7 @@ bool RayTracerBVH::pickSpan(const Camera& camera, int px, int py, int width, int
 std::vector<MCTriangle> RayTracerBVH::extractMeshPlanes(int kind, const float* planes, float extraMargin) {
     std::vector<MCTriangle> out;
     m_lastError.clear();                       // an empty list with lastError() empty is an empty mesh, not a failure
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "extractMesh: compute pipeline not initialized or failed";
+    if (!computeUsable("extractMesh")) {
         std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
         return out;
     }
@@ -551,8 +550,7 @@ std::vector<MCTriangle> RayTracerBVH::extractMeshPlanes(int kind, const float* p
 }
 
 std::vector<MCTriangle> RayTracerBVH::extractMesh(int kind, const Camera& camera, float aspect, float extraMargin) {
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "extractMesh: compute pipeline not initialized or failed";
+    if (!computeUsable("extractMesh")) {
         std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
         return {};
     }
@@ -691,12 +689,33 @@ int RayTracerBVH::regionFailed(int rc, const char* what) {
     return rc;
 }
 
+// Is the compute pipeline usable?  If not, lastError() says so in `who`'s name.
+bool RayTracerBVH::computeUsable(const char* who) {
+    if (m_computeInited && m_computeOk) return true;
+    m_lastError = std::string(who) + ": compute pipeline not initialized or failed";
+    return false;
+}
+
+// A per-voxel field of the first GPU's resident grid: make() makes it resident; when the caller gave a vector, it is sized for the
+// grid and filled by `download`, and left empty on any failure.  The code is RTO_OK or the refusal's.
+template <class Make>
+int RayTracerBVH::fieldInto(const char* who, const char* what, std::vector<int32_t>* out, Make&& make, int (*download)(rto_context*, int32_t*, int64_t)) {
+    if (out) out->clear();
+    if (!computeUsable(who)) return RTO_E_INVALID;
+    if (m_numNodes > 0 && !makeGridResident(what)) return RTO_E_HIP;
+    int rc = make();
+    if (rc == RTO_OK && out) {
+        out->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+        rc = download(m_ctx, out->data(), (int64_t)out->size());
+        if (rc != RTO_OK) out->clear();
+    }
+    if (rc != RTO_OK) return regionFailed(rc, who);
+    return RTO_OK;
+}
+
 int RayTracerBVH::locate(const std::vector<rto_host::vec3>& points, std::vector<PointLocation>& out) {
     out.assign(points.size(), PointLocation());
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "locate: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("locate")) return RTO_E_INVALID;
     if (points.empty()) return RTO_OK;
     std::vector<float> in(3 * points.size());
     for (size_t i = 0; i < points.size(); i++) { in[3 * i] = points[i].x; in[3 * i + 1] = points[i].y; in[3 * i + 2] = points[i].z; }
@@ -713,10 +732,7 @@ int RayTracerBVH::locate(const std::vector<rto_host::vec3>& points, std::vector<
 
 int RayTracerBVH::census(const std::vector<VoxelBrush>& regions, std::vector<RegionCensus>& out) {
     out.assign(regions.size(), RegionCensus());
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "census: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("census")) return RTO_E_INVALID;
     if (regions.empty()) return RTO_OK;
     std::vector<rto_brush> in(regions.size());
     for (size_t i = 0; i < regions.size(); i++) {
@@ -736,10 +752,7 @@ int RayTracerBVH::census(const std::vector<VoxelBrush>& regions, std::vector<Reg
 
 int RayTracerBVH::nearestSolid(const std::vector<rto_host::vec3>& points, std::vector<NearestSolid>& out, float maxDist) {
     out.assign(points.size(), NearestSolid());
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "nearestSolid: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("nearestSolid")) return RTO_E_INVALID;
     if (points.empty()) return RTO_OK;
     std::vector<rto_near_point> in(points.size());
     for (size_t i = 0; i < points.size(); i++) in[i] = rto_near_point{ points[i].x, points[i].y, points[i].z, maxDist };
@@ -889,29 +902,14 @@ int64_t RayTracerBVH::flipComponentAt(int i, int j, int k, int set, int connecti
 
 // The distance field of the first GPU's resident grid (rto_distance_field); the code is RTO_OK or the refusal's.
 int RayTracerBVH::distanceField(int set, float maxDist, std::vector<int32_t>* d2, rto_dist_summary* summary) {
-    if (d2) d2->clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "distanceField: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
-    if (m_numNodes > 0 && !makeGridResident("distance field")) return RTO_E_HIP;
-    int rc = api().distance_field(m_ctx, set, maxDist, summary);
-    if (rc == RTO_OK && d2) {
-        d2->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
-        rc = api().download_distance(m_ctx, d2->data(), (int64_t)d2->size());
-        if (rc != RTO_OK) d2->clear();
-    }
-    if (rc != RTO_OK) return regionFailed(rc, "distanceField");
-    return RTO_OK;
+    return fieldInto("distanceField", "distance field", d2, [&] { return api().distance_field(m_ctx, set, maxDist, summary); },
+                     api().download_distance);
 }
 
 // rto_edit_morphology on every GPU: the number of voxels changed, or the refusal's code (negative).
 int64_t RayTracerBVH::editMorphology(int op, float radius) {
     m_lastEditChanged = -1;
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "morphology: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("morphology")) return RTO_E_INVALID;
     if (m_numNodes > 0 && !makeGridResident("morphology")) return RTO_E_HIP;
     int64_t changed = 0;
     for (rto_context* c : m_ctxs) {
@@ -952,20 +950,9 @@ int RayTracerBVH::thickestPoint(ThickestPoint& out) {
 // The geodesic field of the first GPU's resident grid (rto_geodesic_field); the code is RTO_OK or the refusal's.
 int RayTracerBVH::geodesicField(const std::vector<int64_t>& seeds, int medium, int connectivity, int64_t limit, std::vector<int32_t>* g,
                                 rto_geo_summary* summary) {
-    if (g) g->clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "geodesicField: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
-    if (m_numNodes > 0 && !makeGridResident("geodesic field")) return RTO_E_HIP;
-    int rc = api().geodesic_field(m_ctx, medium, connectivity, seeds.data(), (int64_t)seeds.size(), limit, summary);
-    if (rc == RTO_OK && g) {
-        g->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
-        rc = api().download_geodesic(m_ctx, g->data(), (int64_t)g->size());
-        if (rc != RTO_OK) g->clear();
-    }
-    if (rc != RTO_OK) return regionFailed(rc, "geodesicField");
-    return RTO_OK;
+    return fieldInto("geodesicField", "geodesic field", g,
+                     [&] { return api().geodesic_field(m_ctx, medium, connectivity, seeds.data(), (int64_t)seeds.size(), limit, summary); },
+                     api().download_geodesic);
 }
 
 // The paths of the last geodesicField to `targets` (rto_geodesic_paths): rows of maxLen voxels, -1 behind each path; the full lengths.
@@ -973,10 +960,7 @@ int RayTracerBVH::pathsTo(const std::vector<int64_t>& targets, int64_t maxLen, s
     voxels.clear();
     lengths.clear();
     if (maxLen < 0 || targets.empty()) { m_lastError = "pathsTo: no targets, or a negative maxLen"; return RTO_E_INVALID; }
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "pathsTo: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("pathsTo")) return RTO_E_INVALID;
     voxels.assign(targets.size() * (size_t)maxLen, -1);
     lengths.assign(targets.size(), -1);
     const int rc = api().geodesic_paths(m_ctx, targets.data(), (int64_t)targets.size(), maxLen, maxLen > 0 ? voxels.data() : nullptr, lengths.data());
@@ -987,10 +971,7 @@ int RayTracerBVH::pathsTo(const std::vector<int64_t>& targets, int64_t maxLen, s
 // rto_edit_geodesic on every GPU: the number of voxels flipped, or the refusal's code (negative).
 int64_t RayTracerBVH::floodFrom(const std::vector<int64_t>& seeds, int medium, int connectivity, int64_t limit) {
     m_lastEditChanged = -1;
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "floodFrom: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("floodFrom")) return RTO_E_INVALID;
     if (m_numNodes > 0 && !makeGridResident("flood")) return RTO_E_HIP;
     int64_t changed = 0;
     for (rto_context* c : m_ctxs) {
@@ -1027,29 +1008,18 @@ int RayTracerBVH::farthestPoint(const std::vector<int64_t>& seeds, int medium, i
 // The skeleton field of the first GPU's resident grid (rto_skeleton_field); the code is RTO_OK or the refusal's.
 int RayTracerBVH::skeletonField(int set, int connectivity, int mode, const std::vector<int64_t>& anchors, int64_t maxPasses, std::vector<int32_t>* k,
                                 rto_skel_summary* summary) {
-    if (k) k->clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "skeletonField: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
-    if (m_numNodes > 0 && !makeGridResident("skeleton field")) return RTO_E_HIP;
-    int rc = api().skeleton_field(m_ctx, set, connectivity, mode, anchors.empty() ? nullptr : anchors.data(), (int64_t)anchors.size(), maxPasses, summary);
-    if (rc == RTO_OK && k) {
-        k->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
-        rc = api().download_skeleton(m_ctx, k->data(), (int64_t)k->size());
-        if (rc != RTO_OK) k->clear();
-    }
-    if (rc != RTO_OK) return regionFailed(rc, "skeletonField");
-    return RTO_OK;
+    return fieldInto("skeletonField", "skeleton field", k,
+                     [&] {
+                         return api().skeleton_field(m_ctx, set, connectivity, mode, anchors.empty() ? nullptr : anchors.data(), (int64_t)anchors.size(),
+                                                     maxPasses, summary);
+                     },
+                     api().download_skeleton);
 }
 
 // rto_edit_skeleton of the solid under RTO_CONN_FULL on every GPU: the number of voxels removed, or the refusal's code (negative).
 int64_t RayTracerBVH::thin(int mode, int64_t maxPasses) {
     m_lastEditChanged = -1;
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "thin: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("thin")) return RTO_E_INVALID;
     if (m_numNodes > 0 && !makeGridResident("thin")) return RTO_E_HIP;
     int64_t changed = 0;
     for (rto_context* c : m_ctxs) {
@@ -1082,10 +1052,7 @@ int RayTracerBVH::centreline(int64_t anchorA, int64_t anchorB, std::vector<int64
 
 // The exposure field of the first GPU's resident grid (rto_exposure_field); the code is RTO_OK or the refusal's.
 int RayTracerBVH::exposureField(const std::vector<int32_t>& dirs, const std::vector<int32_t>& weights, int mode, int reach, rto_expo_summary* summary) {
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "exposureField: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("exposureField")) return RTO_E_INVALID;
     if (dirs.size() % 3 != 0 || (!weights.empty() && weights.size() != dirs.size() / 3)) {
         m_lastError = "exposureField: three components a direction, and one weight a direction or none";
         return RTO_E_INVALID;
@@ -1100,10 +1067,7 @@ int RayTracerBVH::exposureField(const std::vector<int32_t>& dirs, const std::vec
 // The resident exposure field, downloaded.
 int RayTracerBVH::exposure(std::vector<int32_t>& e) {
     e.clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "exposure: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("exposure")) return RTO_E_INVALID;
     e.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
     const int rc = api().download_exposure(m_ctx, e.data(), (int64_t)e.size());
     if (rc != RTO_OK) { e.clear(); return regionFailed(rc, "exposure"); }
@@ -1112,20 +1076,8 @@ int RayTracerBVH::exposure(std::vector<int32_t>& e) {
 
 // The local thickness field of the first GPU's resident grid (rto_thickness_field); the code is RTO_OK or the refusal's.
 int RayTracerBVH::thicknessField(int medium, float maxRadius, std::vector<int32_t>* t2, rto_thick_summary* summary) {
-    if (t2) t2->clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "thicknessField: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
-    if (m_numNodes > 0 && !makeGridResident("thickness field")) return RTO_E_HIP;
-    int rc = api().thickness_field(m_ctx, medium, maxRadius, summary);
-    if (rc == RTO_OK && t2) {
-        t2->resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
-        rc = api().download_thickness(m_ctx, t2->data(), (int64_t)t2->size());
-        if (rc != RTO_OK) t2->clear();
-    }
-    if (rc != RTO_OK) return regionFailed(rc, "thicknessField");
-    return RTO_OK;
+    return fieldInto("thicknessField", "thickness field", t2, [&] { return api().thickness_field(m_ctx, medium, maxRadius, summary); },
+                     api().download_thickness);
 }
 
 int RayTracerBVH::thinnestPoint(int medium, float maxRadius, ThinnestPoint& out) {
@@ -1145,10 +1097,7 @@ int RayTracerBVH::thinnestPoint(int medium, float maxRadius, ThinnestPoint& out)
 // The histogram of the last thicknessField (rto_thickness_histogram): c + 1 bins; empty with the refusal's code when none is resident.
 int RayTracerBVH::thicknessHistogram(std::vector<int64_t>& bins) {
     bins.clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "thicknessHistogram: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("thicknessHistogram")) return RTO_E_INVALID;
     int64_t count = 0;
     int rc = api().thickness_histogram(m_ctx, nullptr, 0, &count);
     if (rc == RTO_OK) {
@@ -1163,10 +1112,7 @@ int RayTracerBVH::thicknessHistogram(std::vector<int64_t>& bins) {
 // that labelling; the code is RTO_OK or the refusal's.
 int RayTracerBVH::measureComponents(int set, int connectivity, std::vector<rto_measure>* table, rto_measure* total) {
     if (table) table->clear();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "measureComponents: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("measureComponents")) return RTO_E_INVALID;
     if (m_numNodes > 0 && !makeGridResident("component measures")) return RTO_E_HIP;
     int64_t count = 0;
     int rc = api().label_components(m_ctx, set, connectivity, &count);
@@ -1208,10 +1154,7 @@ int RayTracerBVH::centroid(int set, Centroid& out) {
 // tunnels = pieces + cavities - euler.  The set's labels and measures stay resident.
 int RayTracerBVH::topology(int set, int connectivity, Topology& out) {
     out = Topology();
-    if (!m_computeInited || !m_computeOk) {
-        m_lastError = "topology: compute pipeline not initialized or failed";
-        return RTO_E_INVALID;
-    }
+    if (!computeUsable("topology")) return RTO_E_INVALID;
     if (m_numNodes > 0 && !makeGridResident("topology")) return RTO_E_HIP;
     // an unknown set or connectivity goes through as it is: the library refuses it with its message
     const int other = set == RTO_SET_SOLID ? RTO_SET_EMPTY : (set == RTO_SET_EMPTY ? RTO_SET_SOLID : set);

@@ -360,7 +360,10 @@ private:
     template <class F> bool forEachContext(F&& call, const char* what);
     bool renderFrame(const rto_frame& f, int mode);
     int regionFailed(int rc, const char* what);
+    bool computeUsable(const char* who);
     bool makeGridResident(const char* what);
+    template <class Make>
+    int fieldInto(const char* who, const char* what, std::vector<int32_t>* out, Make&& make, int (*download)(rto_context*, int32_t*, int64_t));
     int64_t editComponents(int set, int connectivity, int select, int64_t arg);
     int64_t editMorphology(int op, float radius);
     mutable std::string m_lastError;

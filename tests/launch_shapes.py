@@ -95,7 +95,7 @@ TABLE = {
     "skel_window:words-per-row>=2": ("sk_window: wx > 0, wx + 1 < D.wordsX", "33 x 1 x 1"),
     "skel_step:voxel-beyond-grid": ("k_skel_step: !inGrid, a dim off its tile", "1 x 1 x 1"),
     "skel_step:tiles-all-inside": ("k_skel_step: inGrid for every thread", "32 x 8 x 8"),
-    "skel_anchors:none": ("skel_thin: n == 0, no list, no launch", "no anchors"),
+    "skel_anchors:none": ("skel_thin: n == 0, VoxelList::upload makes no list and in_parts launches nothing", "no anchors"),
     "skel_anchors:blocks==1": ("skel_thin: 1 <= n <= kBlock anchors", "1 anchor"),
     "skel_anchors:blocks>=2": ("skel_thin: n > kBlock anchors", "257 anchors"),
     "skel_summary:round==1": ("k_skel_summary: nvox <= 4096 x 256", "1 x 1 x 1"),
@@ -109,8 +109,8 @@ BY_INSPECTION = {
     "geo:longest-path>=2^31-1": ("k_geo_relax: a path length beyond int32", "geo_check_args refuses: 'the longest possible path does not fit'"),
     "measure:dim>32768": ("k_measure: tile-local sums beyond 32 bits", "rto_measure_components refuses: 'a dimension of the grid is above 32768'"),
     "edit_brushes:blocks>2^31-1": ("rto_edit_voxels: blocks > 0x7fffffff", "rto_edit_voxels refuses: 'the brushes' box is too large for one launch'"),
-    "geo_seeds:launches>=2": ("geo_relax: at += 2^30, above 2^30 seeds", "cannot hold: the list alone is 8 GiB on the host and again on the device"),
-    "skel_anchors:launches>=2": ("skel_thin: at += 2^30, above 2^30 anchors", "cannot hold: the list alone is 8 GiB on the host and again on the device"),
+    "geo_seeds:launches>=2": ("geo_relax: VoxelList::in_parts, at += 2^30, above 2^30 seeds", "cannot hold: the list alone is 8 GiB on the host and again on the device"),
+    "skel_anchors:launches>=2": ("skel_thin: VoxelList::in_parts, at += 2^30, above 2^30 anchors", "cannot hold: the list alone is 8 GiB on the host and again on the device"),
 }
 
 # the kernels' classes by the operation whose source file holds them
@@ -135,7 +135,7 @@ def _voxels(dims):
 
 
 def _tiles(dims):
-    return tuple((d + t - 1) // t for d, t in zip(dims, TILE))         # cc_label, geo_relax, skel_thin: tilesX, tilesY, tilesZ
+    return tuple((d + t - 1) // t for d, t in zip(dims, TILE))         # CcTiles (cc_label, geo_relax, skel_thin, ...): the tiles along x, y, z
 
 
 def _off_tile(dims):
