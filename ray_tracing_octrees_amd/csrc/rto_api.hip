@@ -912,7 +912,7 @@ static int build_octree_resident(rto_context* c, const uint8_t* voxels, int R) {
             const int lv = R - (int)L;
             const int nb = (int)((lb.m + kBlock - 1) / kBlock);
             hipLaunchKernelGGL(k_build_classify, dim3(nb), dim3(kBlock), 0, s, V, lb.coords, lb.m, lv, lb.state, lb.flag, d_bc[L]);
-            hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, s, d_bc[L], nb, d_bb[L], c->d_visibleCount);
+            hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, s, d_bc[L], nb, d_bb[L], c->d_visibleCount);
             hipLaunchKernelGGL(k_build_rank_children, dim3(nb), dim3(kBlock), 0, s, lb.flag, lb.coords, lb.m, d_bb[L], (1 << lv) / 2, lb.rank,
                                L + 1 < levels.size() ? levels[L + 1].coords : (int4*)nullptr);
         }
@@ -1343,7 +1343,7 @@ static int sync_cull_state(rto_context* c) {
         const int64_t n = c->numNodes;
         const int nb = (int)((n + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_vis_block_counts, dim3(nb), dim3(kBlock), 0, c->stream, c->d_vis, n, c->d_blockCount);
-        hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
+        hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, c->stream, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
         RTO_HIP(c, hipGetLastError());
         int64_t count = 0;
         RTO_HIP(c, hipMemcpyAsync(&count, c->d_visibleCount, sizeof count, hipMemcpyDeviceToHost, c->stream));
@@ -1367,7 +1367,7 @@ static int ensure_compact(rto_context* c, hipStream_t s) {
     const int nb = (int)((n + kBlock - 1) / kBlock);
     if (c->cullAsync) {                                    // k_cull_desc leaves flags only: count and scan them now
         hipLaunchKernelGGL(k_vis_block_counts, dim3(nb), dim3(kBlock), 0, s, c->d_vis, n, c->d_blockCount);
-        hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, s, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
+        hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, s, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
     }
     hipLaunchKernelGGL(k_cull_remap, dim3(nb), dim3(kBlock), 0, s, c->d_vis, n, c->d_blockBase, c->d_remap);
     hipLaunchKernelGGL(k_cull_compact, dim3(nb), dim3(kBlock), 0, s, c->d_nodes, n, c->d_remap, c->d_compact);
@@ -1487,7 +1487,7 @@ static int update_frustum_planes(rto_context* c, const float planes[24], float m
     // arbitrary arrays (generic kernel): per-node flags + scan, the count and the root's flag come back in one copy
     if (capturing) return fail(c, RTO_E_UNSUPPORTED, "rto_update_frustum: capturable for canonical BFS octrees only");
     hipLaunchKernelGGL(k_cull_flags, dim3(nb), dim3(kBlock), 0, c->stream, C, c->d_nodes, n, c->d_vis, c->d_blockCount, c->d_visibleCount + 1);
-    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
+    hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, c->stream, c->d_blockCount, nb, c->d_blockBase, c->d_visibleCount);
     RTO_HIP(c, hipGetLastError());
     int64_t back[2] = { 0, 0 };                     // visible nodes, the root's flag: one read-back
     RTO_HIP(c, hipMemcpyAsync(back, c->d_visibleCount, sizeof back, hipMemcpyDeviceToHost, c->stream));
@@ -2140,7 +2140,7 @@ static int build_triangle_records(rto_context* c, hipStream_t s) {
     RTO_HIP(c, scratch.alloc(&d_bs, (size_t)nb)); RTO_HIP(c, scratch.alloc(&d_bb, (size_t)nb)); RTO_HIP(c, scratch.alloc(&d_total, 1));
     hipLaunchKernelGGL(k_unified_count, dim3(nb), dim3(kBlock), 0, s, c->d_desc, n, d_count);
     hipLaunchKernelGGL(k_block_sums, dim3(nb), dim3(kBlock), 0, s, d_count, n, d_bs);
-    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, s, d_bs, nb, d_bb, d_total);
+    hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, s, d_bs, nb, d_bb, d_total);
     hipLaunchKernelGGL(k_block_exclusive_scan, dim3(nb), dim3(kBlock), 0, s, d_count, n, d_bb, d_total, d_first);
     RTO_HIP(c, hipGetLastError());
     int64_t total = 0;
@@ -2501,7 +2501,7 @@ int rto_build_leaf_triangles(rto_context* c, const uint8_t* voxels, int dimX, in
     }
     // scan -> triOffset
     hipLaunchKernelGGL(k_block_sums, dim3(nb), dim3(kBlock), 0, s, d_count, n, d_bs);
-    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, s, d_bs, nb, d_bb, d_total);
+    hipLaunchKernelGGL((k_scan_counts<1024, int, int64_t>), dim3(1), dim3(1024), 0, s, d_bs, nb, d_bb, d_total);
     hipLaunchKernelGGL(k_block_exclusive_scan, dim3(nb), dim3(kBlock), 0, s, d_count, n, d_bb, d_total, c->d_triOffset);
     RTO_HIP(c, hipGetLastError());
     int64_t total = 0;

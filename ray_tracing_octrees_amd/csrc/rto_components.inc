@@ -9,7 +9,7 @@
 // Phases: (1) k_cc_local: one workgroup labels one 32 x 8 x 8 tile in LDS and writes a 32-bit parent per voxel (the global index
 // of the tile-local root, kCcNone outside the set); (2) k_cc_merge unites the trees of every neighbour pair that straddles a tile
 // face with agent-scope atomics, and runs again until a pass finds every such pair already joined; (3) k_cc_flatten points every
-// voxel at its root and counts roots per chunk, k_cc_scan / k_cc_rank number the roots in index order, k_cc_label writes the
+// voxel at its root and counts roots per chunk, k_scan_counts / k_cc_rank number the roots in index order, k_cc_label writes the
 // volume; (4) k_cc_stats fills the table.  Every dependence between workgroups crosses a kernel boundary: no kernel waits for
 // another workgroup.  Parents only ever decrease, so every find chain and every retry loop strictly descends.
 
@@ -193,42 +193,8 @@ __global__ __launch_bounds__(kBlock) void k_cc_flatten(unsigned* __restrict__ pa
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) roots += __shfl_xor(roots, off);
-    __shared__ int waveSum[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = roots;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        blockCount[blockIdx.x] = (unsigned)s;
-    }
-}
-
-// Exclusive scan of the chunk counts in place, one workgroup; total[0] = the number of components.
-__global__ __launch_bounds__(kBlock) void k_cc_scan(unsigned* __restrict__ blockCount, unsigned numBlocks, unsigned* __restrict__ total) {
-    __shared__ unsigned waveSum[kBlock / kWave];
-    __shared__ unsigned carry;
-    const int t = (int)threadIdx.x, lane = t % kWave, wave = t / kWave;
-    if (t == 0) carry = 0u;
-    __syncthreads();
-    for (unsigned b0 = 0; b0 < numBlocks; b0 += kBlock) {
-        const unsigned i = b0 + (unsigned)t;
-        const unsigned c = i < numBlocks ? blockCount[i] : 0u;
-        unsigned inc = c;
-        for (int off = 1; off < kWave; off <<= 1) {
-            const unsigned o = __shfl_up(inc, off);
-            if (lane >= off) inc += o;
-        }
-        if (lane == kWave - 1) waveSum[wave] = inc;
-        __syncthreads();
-        unsigned before = carry;
-        for (int w = 0; w < wave; w++) before += waveSum[w];
-        if (i < numBlocks) blockCount[i] = before + inc - c;
-        __syncthreads();
-        if (t == kBlock - 1) carry = before + inc;
-        __syncthreads();
-    }
-    if (t == 0) total[0] = carry;
+    roots = block_sum<kBlock>(roots);
+    if (threadIdx.x == 0) blockCount[blockIdx.x] = (unsigned)roots;
 }
 
 struct CcComp {                    // rto_component's layout
@@ -242,20 +208,15 @@ static_assert(sizeof(CcComp) == 48, "rto_component is 48 bytes");
 // starts its table entry.
 __global__ __launch_bounds__(kBlock) void k_cc_rank(const unsigned* __restrict__ parent, unsigned n, const unsigned* __restrict__ blockBase,
                                                    int* __restrict__ labels, CcComp* __restrict__ comps) {
-    __shared__ unsigned waveCount[kBlock / kWave];
     const unsigned base = blockIdx.x * (unsigned)kCcChunk;
-    const int lane = (int)threadIdx.x % kWave, wave = (int)threadIdx.x / kWave;
     unsigned rank = blockBase[blockIdx.x];
     for (int j = 0; j < kCcPerThread; j++) {
         const unsigned v = base + (unsigned)j * kBlock + threadIdx.x;
         const bool isRoot = v < n && parent[v] == v;
-        const unsigned long long m = __ballot(isRoot);
-        if (lane == 0) waveCount[wave] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned before = 0, all = 0;
-        for (int w = 0; w < kBlock / kWave; w++) { before += w < wave ? waveCount[w] : 0u; all += waveCount[w]; }
+        int all;
+        const int before = block_rank<kBlock>(isRoot, &all);             // roots of this row of the chunk before v
         if (isRoot) {
-            const unsigned r = rank + before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+            const unsigned r = rank + (unsigned)before;
             labels[v] = (int)r;
             CcComp c;
             c.root = (long long)v; c.voxels = 0;
@@ -551,7 +512,7 @@ int cc_label(rto_context* c, const char* who, int set, int connectivity, CcResul
     // (3) flatten, rank, label
     hipLaunchKernelGGL(k_cc_flatten, dim3(chunks), dim3(kBlock), 0, s, d_parent, D.n, d_blockCount);
     RTO_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(k_cc_scan, dim3(1), dim3(kBlock), 0, s, d_blockCount, chunks, d_total);
+    hipLaunchKernelGGL((k_scan_counts<kBlock, unsigned, unsigned>), dim3(1), dim3(kBlock), 0, s, d_blockCount, (int)chunks, d_blockCount, d_total);
     RTO_HIP(c, hipGetLastError());
     unsigned total = 0;
     RTO_HIP(c, hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, s));

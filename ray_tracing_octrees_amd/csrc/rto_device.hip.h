@@ -45,6 +45,9 @@ constexpr int kWave = 64;
 #define RTO_BLOCK 256             // A/B builds (-DRTO_BLOCK=n), traversal kernel at config 2: 64 -> 67.4 us, 128 -> 69.0, 256 -> 66.3, 512 -> 71.3
 #endif
 constexpr int kBlock = RTO_BLOCK;         // 4 waves, each owns one 8x8 pixel tile
+}  // namespace rto
+#include "rto_collectives.hip.h"          // wave and workgroup sums, ranks and scans, and their barrier contract
+namespace rto {
 #ifndef RTO_PACKED3_WAVES
 #define RTO_PACKED3_WAVES 6       // waves per SIMD for the default traversal kernel (8 forces spills and measured 6 % slower)
 #endif
@@ -306,19 +309,12 @@ __device__ __forceinline__ void wave_accumulate(Counters* c, int steps, bool hit
     }
 }
 
-// The tail of a kernel (blocks of kBlock threads) that counts: every thread's count is added to *total -- a wave reduction, the
-// waves' sums through LDS, then one 64-bit atomic per block (none for a block that counted nothing).  EVERY thread of the block
-// must reach the call (it holds a barrier): call it outside the kernel's bounds test, with count == 0 for threads that own nothing.
+// The tail of a kernel (blocks of kBlock threads) that counts: every thread's count is added to *total with one 64-bit atomic per
+// block (none for a block that counted nothing).  A block collective: EVERY thread of the block must reach the call, outside the
+// kernel's bounds test, with count == 0 for threads that own nothing.
 __device__ __forceinline__ void block_add_count(int count, unsigned long long* total) {
-    for (int off = kWave / 2; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    __shared__ int waveSum[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        if (s) atomicAdd(total, (unsigned long long)s);
-    }
+    const int s = block_sum<kBlock>(count);
+    if (threadIdx.x == 0 && s) atomicAdd(total, (unsigned long long)s);
 }
 
 // ================================================================ generic kernel
@@ -1983,42 +1979,30 @@ __global__ __launch_bounds__(kBlock) void k_cull_flags(CullParams C, const rto_n
     if (threadIdx.x == 0) blockCount[blockIdx.x] = cnt;
 }
 
-// single block: exclusive scan of the per-block counts; total -> *visibleCount
-__global__ __launch_bounds__(1024) void k_scan_block_counts(const int* __restrict__ blockCount, int nb,
-                                                             int* __restrict__ blockBase, int64_t* __restrict__ visibleCount) {
-    __shared__ int partial[1024];
-    const int t = threadIdx.x;
-    const int per = (nb + 1023) / 1024;
-    const int lo = t * per, hi = min(lo + per, nb);
-    int s = 0;
-    for (int i = lo; i < hi; i++) s += blockCount[i];
-    partial[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {   // Hillis-Steele inclusive scan
-        int v = (t >= off) ? partial[t - off] : 0;
-        __syncthreads();
-        partial[t] += v;
-        __syncthreads();
+// ONE workgroup of THREADS: exclusive scan of n per-block counts (base may be counts: in place), the total -> *total.  Rounds of
+// THREADS counts, the sum so far carried in a register.  The single-workgroup leg of every scan here: the visible nodes, the
+// build's ranks and the leaf triangles (1024 threads), the components' roots (kBlock), the voxelizer's pairs (1024, 64-bit).
+template <int THREADS, typename T, typename TOTAL>
+__global__ __launch_bounds__(THREADS) void k_scan_counts(const T* counts, int n, T* base, TOTAL* __restrict__ total) {
+    T carry = 0;
+    for (int i0 = 0; i0 < n; i0 += THREADS) {
+        const unsigned i = (unsigned)i0 + threadIdx.x;
+        T all;
+        const T before = block_exclusive_scan<THREADS>(i < (unsigned)n ? counts[i] : T(0), &all);
+        if (i < (unsigned)n) base[i] = carry + before;
+        carry += all;
+        __syncthreads();                                     // the partials are read: the next round may write them
     }
-    int run = partial[t] - s;   // exclusive prefix of this thread's chunk
-    for (int i = lo; i < hi; i++) { blockBase[i] = run; run += blockCount[i]; }
-    if (t == 1023) *visibleCount = partial[1023];
+    if (threadIdx.x == 0) *total = (TOTAL)carry;
 }
 
 // old index -> new index (-1 if culled): S/RT:765-772
 __global__ __launch_bounds__(kBlock) void k_cull_remap(const uint8_t* __restrict__ vis, int64_t n,
                                                         const int* __restrict__ blockBase, int* __restrict__ remap) {
-    __shared__ int waveTotal[kBlock / kWave];
     int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool v = (i < n) && vis[i];
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __builtin_popcountll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) waveTotal[wave] = __builtin_popcountll(b);
-    __syncthreads();
-    int base = blockBase[blockIdx.x];
-    for (int w = 0; w < wave; w++) base += waveTotal[w];
-    if (i < n) remap[i] = v ? base + before : -1;
+    const int r = blockBase[blockIdx.x] + block_rank<kBlock>(v);      // visible nodes before this one
+    if (i < n) remap[i] = v ? r : -1;
 }
 
 // S/RT:778-802: copy visible nodes, remap children of non-leaf nodes (culled child -> -1)
@@ -2083,11 +2067,17 @@ __global__ void k_start_at_root(StartState* __restrict__ start, int depth, long 
 // (ticket) reduces the blocks' counts / first visible indices and records where traversals start (StartState): the root, or
 // -- root culled, descendants visible: S/RT:765-812 -- the first visible node in BFS order, whose descriptor it finds by
 // walking down from the root along the node's coordinates.  Partials cross XCDs: agent-scope stores / loads around the ticket.
+struct CullPart { long long count; int first; };                    // visible nodes: how many, and the first in BFS order
+struct OpCullPart {
+    __device__ __forceinline__ CullPart operator()(CullPart a, const CullPart& b) const {
+        a.count += b.count; a.first = min(a.first, b.first);
+        return a;
+    }
+};
 __global__ __launch_bounds__(kBlock) void k_cull_desc(CullParams C, const int4* __restrict__ descPos, const int* __restrict__ descFirstChild,
                                                        const rto_node* __restrict__ nodes, int64_t nInternal, int depth,
                                                        uint2* __restrict__ desc, uint8_t* __restrict__ vis,
                                                        int* __restrict__ blockCount, int* __restrict__ blockFirst, StartState* __restrict__ start) {
-    __shared__ int redCount[kBlock / kWave], redFirst[kBlock / kWave];
     __shared__ int isLast, rootSeen;
     const int64_t d = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int cnt = 0, first = 0x7fffffff;
@@ -2131,15 +2121,10 @@ __global__ __launch_bounds__(kBlock) void k_cull_desc(CullParams C, const int4* 
         }
         return;
     }
-    for (int off = 32; off > 0; off >>= 1) { cnt += __shfl_down(cnt, off); first = min(first, __shfl_down(first, off)); }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { redCount[wave] = cnt; redFirst[wave] = first; }
-    __syncthreads();
+    const CullPart mine = block_reduce<kBlock>(CullPart{ cnt, first }, OpCullPart());        // this block's visible nodes
     if (threadIdx.x == 0) {
-        int c = 0, f = 0x7fffffff;
-        for (int w = 0; w < kBlock / kWave; w++) { c += redCount[w]; f = min(f, redFirst[w]); }
-        __hip_atomic_store(&blockCount[blockIdx.x], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&blockFirst[blockIdx.x], f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&blockCount[blockIdx.x], (int)mine.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&blockFirst[blockIdx.x], mine.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();                                     // release: the partials before the ticket
         drain_vector_memory();                               // ... and acknowledged before it (the wait the compiler may drop)
         const unsigned t = atomicAdd(&start->ticket, 1u);
@@ -2155,13 +2140,9 @@ __global__ __launch_bounds__(kBlock) void k_cull_desc(CullParams C, const int4* 
         total += __hip_atomic_load(&blockCount[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         f = min(f, __hip_atomic_load(&blockFirst[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
-    for (int off = 32; off > 0; off >>= 1) { total += __shfl_down(total, off); f = min(f, __shfl_down(f, off)); }
-    __shared__ long long redTotal[kBlock / kWave];
-    if (lane == 0) { redTotal[wave] = total; redFirst[wave] = f; }
-    __syncthreads();
+    const CullPart all = block_reduce<kBlock>(CullPart{ total, f }, OpCullPart());          // every block's (the partials: the barriers above)
     if (threadIdx.x != 0) return;
-    total = 0; f = 0x7fffffff;
-    for (int w = 0; w < kBlock / kWave; w++) { total += redTotal[w]; f = min(f, redFirst[w]); }
+    total = all.count; f = all.first;
     StartState st;
     st.visible = total > 0 ? 1 : 0;
     st.desc = 0; st.x = st.y = st.z = 0; st.shift = depth; st.leaf = 0; st.solid = 0;
@@ -3438,7 +3419,6 @@ __global__ __launch_bounds__(kBlock) void k_pyramid_level(const uint8_t* __restr
 __global__ __launch_bounds__(kBlock) void k_pyramid_level1_wide(const uint8_t* __restrict__ vox, int dimX, int dimY, int dimZ,
                                                                  uint8_t* __restrict__ out, int nx, int ny, int nz,
                                                                  int* __restrict__ blockMixed) {
-    __shared__ int waveTotal[kBlock / kWave];
     const int groupsX = nx / 8;
     const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const size_t total = (size_t)groupsX * ny * nz;
@@ -3472,23 +3452,18 @@ __global__ __launch_bounds__(kBlock) void k_pyramid_level1_wide(const uint8_t* _
         }
         *reinterpret_cast<unsigned long long*>(out + ((size_t)k * ny + j) * nx + (size_t)gx * 8) = packed;
     }
-    for (int off = 32; off > 0; off >>= 1) mixedCount += __shfl_down(mixedCount, off);
-    if ((threadIdx.x & 63) == 0) waveTotal[threadIdx.x >> 6] = mixedCount;
-    __syncthreads();
-    if (threadIdx.x == 0) { int s = 0; for (int w = 0; w < kBlock / kWave; w++) s += waveTotal[w]; blockMixed[blockIdx.x] = s; }
+    const int s = block_sum<kBlock>(mixedCount);
+    if (threadIdx.x == 0) blockMixed[blockIdx.x] = s;
 }
 
 // one block per pyramid level: levelMixed[l] = sum of that level's per-block counts
 struct LevelCountView { const int* blockMixed[kMaxDepth + 1]; int numBlocks[kMaxDepth + 1]; };
 __global__ __launch_bounds__(1024) void k_sum_level_counts(LevelCountView V, long long* __restrict__ levelMixed) {
-    __shared__ long long partial[1024 / kWave];
     const int l = blockIdx.x + 1;
     long long sum = 0;
     for (int i = threadIdx.x; i < V.numBlocks[l]; i += 1024) sum += V.blockMixed[l][i];
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) { long long t = 0; for (int w = 0; w < 1024 / kWave; w++) t += partial[w]; levelMixed[l] = t; }
+    sum = block_sum<1024>(sum);
+    if (threadIdx.x == 0) levelMixed[l] = sum;
 }
 
 // classify the nodes of one tree level: internal flag + per-block internal count
@@ -3727,7 +3702,7 @@ __global__ __launch_bounds__(kBlock) void k_mb_bricks(const uint8_t* __restrict_
     }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        for (int o = 32; o > 0; o >>= 1) { lo[a] = min(lo[a], __shfl_down(lo[a], o)); hi[a] = max(hi[a], __shfl_down(hi[a], o)); }
+        lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]);
         if ((threadIdx.x & 63) == 0) { if (lo[a] != 0x7fffffff) atomicMin(&box[a], lo[a]); if (hi[a] != -0x7fffffff) atomicMax(&box[3 + a], hi[a]); }
     }
     for (int t = threadIdx.x; t < nb * (4096 / 4); t += kBlock) reinterpret_cast<unsigned*>(ct[t >> 10])[t & 1023] = 0;      // level 1 has no mixed children
@@ -3800,10 +3775,8 @@ __device__ __forceinline__ int mb_level_of(const MbLevels& Lv, long long idx) {
 // level totals -> bases of every tree level.
 __global__ __launch_bounds__(1024) void k_mb_top_scan(MbLevels Lv, const int* __restrict__ brickBox, int numBricks, int* __restrict__ chunkSum,
                                                       MbTables* __restrict__ T) {
-    __shared__ int part[1024 / kWave][6];
-    __shared__ int waveTotal[1024 / kWave];
     __shared__ long long mixedOf[kMbMaxDepth + 2];              // [l] mixed cells of pyramid level l
-    const int R = Lv.R, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int R = Lv.R, t = threadIdx.x;
     const int B = R < kMbBrickLevels ? R : kMbBrickLevels;
     for (int l = B + 1; l <= R; l++) {
         const long long cells = 1ll << (3 * (R - l));
@@ -3820,23 +3793,15 @@ __global__ __launch_bounds__(1024) void k_mb_top_scan(MbLevels Lv, const int* __
         __threadfence_block();
         __syncthreads();
     }
-    int lo[3] = { 0x7fffffff, 0x7fffffff, 0x7fffffff }, hi[3] = { -0x7fffffff, -0x7fffffff, -0x7fffffff };
+    IntBox box = { { 0x7fffffff, 0x7fffffff, 0x7fffffff }, { -0x7fffffff, -0x7fffffff, -0x7fffffff } };
     for (int b = t; b < numBricks; b += 1024)
 #pragma unroll
-        for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], brickBox[(size_t)b * 6 + a]); hi[a] = max(hi[a], brickBox[(size_t)b * 6 + 3 + a]); }
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-        for (int o = 32; o > 0; o >>= 1) { lo[a] = min(lo[a], __shfl_down(lo[a], o)); hi[a] = max(hi[a], __shfl_down(hi[a], o)); }
-    if (lane == 0)
-#pragma unroll
-        for (int a = 0; a < 3; a++) { part[wave][a] = lo[a]; part[wave][3 + a] = hi[a]; }
+        for (int a = 0; a < 3; a++) { box.lo[a] = min(box.lo[a], brickBox[(size_t)b * 6 + a]); box.hi[a] = max(box.hi[a], brickBox[(size_t)b * 6 + 3 + a]); }
     __threadfence();
-    __syncthreads();
-    if (t < 6) {
-        int v = part[0][t];
-        for (int w = 1; w < 1024 / kWave; w++) v = t < 3 ? min(v, part[w][t]) : max(v, part[w][t]);
-        if (t < 3) T->solidLo[t] = v; else T->solidHi[t - 3] = v;
-    }
+    box = block_reduce<1024>(box, OpBoxUnion());
+    if (t == 0)
+#pragma unroll
+        for (int a = 0; a < 3; a++) { T->solidLo[a] = box.lo[a]; T->solidHi[a] = box.hi[a]; }
     // ---- the scan.  The sums were made by atomics (the bricks' and this block's own): read them at the L2
     if (t == 0) mixedOf[R] = Lv.state[R][0] == 2 ? 1 : 0;
     for (int l = 2; l <= R; l++) {
@@ -3846,12 +3811,8 @@ __global__ __launch_bounds__(1024) void k_mb_top_scan(MbLevels Lv, const int* __
         const int first = min(t * per, nb), last = min(first + per, nb);
         int s = 0;
         for (int i = first; i < last; i++) s += __hip_atomic_load(&chunkSum[c0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int incl = s;
-        for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-        if (lane == kWave - 1) waveTotal[wave] = incl;
-        __syncthreads();
-        int run = incl - s, all = 0;
-        for (int w = 0; w < 1024 / kWave; w++) { const int v = waveTotal[w]; if (w < wave) run += v; all += v; }
+        int all;
+        int run = block_exclusive_scan<1024>(s, &all);
         for (int i = first; i < last; i++) {
             const int v = __hip_atomic_load(&chunkSum[c0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             chunkSum[c0 + i] = run; run += v;
@@ -3879,11 +3840,9 @@ __global__ __launch_bounds__(1024) void k_mb_top_scan(MbLevels Lv, const int* __
 // internal node with every lane busy (mixed cells are ~1 % of the level-1 cells of a surface scene).
 __global__ __launch_bounds__(kBlock) void k_mb_group_ranks(MbLevels Lv, const int* __restrict__ chunkBase, const MbTables* __restrict__ T,
                                                             unsigned* __restrict__ cellOf) {
-    __shared__ int waveTotal[kBlock / kWave];
     const long long c0 = (long long)blockIdx.x * kMbChunk;
     const int l = mb_level_of(Lv, c0);
     const long long cells = 1ll << (3 * (Lv.R - l)), local0 = c0 - Lv.cntOffset[l];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // each thread owns 4 consecutive cells
     const long long p0 = local0 + (long long)threadIdx.x * 4;
     int v[4], sum = 0;
@@ -3895,12 +3854,7 @@ __global__ __launch_bounds__(kBlock) void k_mb_group_ranks(MbLevels Lv, const in
 #pragma unroll
         for (int q = 0; q < 4; q++) { v[q] = p0 + q < cells ? Lv.cnt[l][p0 + q] : 0; sum += v[q]; }
     }
-    int incl = sum;
-    for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-    if (lane == kWave - 1) waveTotal[wave] = incl;
-    __syncthreads();
-    int run = chunkBase[blockIdx.x] + incl - sum;
-    for (int w = 0; w < wave; w++) run += waveTotal[w];
+    int run = chunkBase[blockIdx.x] + block_exclusive_scan<kBlock>(sum);
     const long long dBase = T->internalBase[Lv.R - (l - 1)];                // descriptors of tree level R-(l-1) = the mixed cells of level l-1
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -4032,7 +3986,7 @@ __global__ __launch_bounds__(kBlock) void k_solid_bbox(const rto_node* __restric
 // Only cells on a leaf's three max faces can straddle occupancy (a leaf is uniform, a cell reads corners x..x+1),
 // so a leaf of edge s has at most 3s^2-3s+1 candidate cells, enumerated in the same z, y, x order.
 //   count:  one thread per leaf up to kLeafSerialCandidates candidates, one wave per larger leaf
-//   scan :  block sums -> k_scan_block_counts -> per-block exclusive scan = triOffset
+//   scan :  block sums -> k_scan_counts -> per-block exclusive scan = triOffset
 //   emit :  same walk, writing at triOffset[node] + running count
 struct LeafTriParams {
     const rto_node* nodes;
@@ -4187,11 +4141,7 @@ __global__ __launch_bounds__(kBlock) void k_leaftri_big(LeafTriParams P, const i
             cs = P.cases[cell_case(P, L.x0 + i, L.y0 + j, L.z0 + k)];
         }
         const int nt = (int)(cs >> 60);
-        int incl = nt;                                         // inclusive wave prefix of the triangle counts
-        for (int off = 1; off < kWave; off <<= 1) {
-            const int up = __shfl_up(incl, off);
-            if (lane >= off) incl += up;
-        }
+        const int incl = wave_inclusive_scan(nt);              // the triangle counts of lanes 0 .. lane
         if (EMIT && nt) emit_cell_triangles(P, L.x0 + i, L.y0 + j, L.z0 + k, cs, tris + (size_t)(run + incl - nt) * 12);
         run += __shfl(incl, kWave - 1);
     }
@@ -4215,32 +4165,17 @@ __global__ __launch_bounds__(kBlock) void k_leaftri_bigsum(LeafTriParams P, cons
 
 // block sums of an int array (for the exclusive scan that turns triCount into triOffset)
 __global__ __launch_bounds__(kBlock) void k_block_sums(const int* __restrict__ v, int64_t n, int* __restrict__ blockSum) {
-    __shared__ int waveTotal[kBlock / kWave];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    int x = i < n ? v[i] : 0;
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
-    if ((threadIdx.x & 63) == 0) waveTotal[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < kBlock / kWave; w++) t += waveTotal[w]; blockSum[blockIdx.x] = t; }
+    const int t = block_sum<kBlock>(i < n ? v[i] : 0);
+    if (threadIdx.x == 0) blockSum[blockIdx.x] = t;
 }
 
 // out[i] = blockBase[block] + exclusive prefix within the block; out[n] = total
 __global__ __launch_bounds__(kBlock) void k_block_exclusive_scan(const int* __restrict__ v, int64_t n, const int* __restrict__ blockBase,
                                                                   const int64_t* __restrict__ total, int* __restrict__ out) {
-    __shared__ int waveTotal[kBlock / kWave];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = i < n ? v[i] : 0;
-    int incl = x;
-    for (int off = 1; off < kWave; off <<= 1) {
-        const int up = __shfl_up(incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == kWave - 1) waveTotal[wave] = incl;
-    __syncthreads();
-    int base = blockBase[blockIdx.x];
-    for (int w = 0; w < wave; w++) base += waveTotal[w];
-    if (i < n) out[i] = base + incl - x;
+    const int before = block_exclusive_scan<kBlock>(i < n ? v[i] : 0);
+    if (i < n) out[i] = blockBase[blockIdx.x] + before;
     if (i == 0) out[n] = (int)*total;
 }
 
@@ -4278,12 +4213,7 @@ __global__ __launch_bounds__(kBlock) void k_cells_fill(const uint2* __restrict__
         if (l <= L) sel = (w & 0xffu) | (l == L ? ((w >> 8) & 0xffu) : 0u);
     }
     const int n = __builtin_popcount(sel);
-    int incl = n;                                              // wave-level prefix sum: one atomic per wave
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < kWave; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-    int base = 0;
-    if (lane == kWave - 1 && incl > 0) base = atomicAdd(cursor, incl);
-    base = __shfl(base, kWave - 1) + incl - n;
+    int base = wave_append(n, cursor);              // one atomic per wave
     const int half = p.w >> 1;
     while (sel) {
         const int k = __builtin_ctz(sel);

@@ -164,8 +164,8 @@ __global__ __launch_bounds__(kBlock) void k_dt_axis(int* __restrict__ f, CcDims 
 }
 
 // ---- summary: the largest finite value and the smallest voxel that holds it, as one max over the key (d2 << 32) | ~v (a smaller
-// v is a larger key; every real key is above 0 because v < 2^31), and the number of finite values.  A wave reduction, the
-// workgroup's four waves through LDS, then one 64-bit atomic max and one 64-bit atomic add per workgroup.
+// v is a larger key; every real key is above 0 because v < 2^31), and the number of finite values: one 64-bit atomic max and one
+// 64-bit atomic add per workgroup.
 __global__ __launch_bounds__(kBlock) void k_dt_summary(const int* __restrict__ d2, unsigned n, unsigned long long* __restrict__ key,
                                                       unsigned long long* __restrict__ finite) {
     const unsigned base = blockIdx.x * (unsigned)kDtChunk;
@@ -183,20 +183,12 @@ __global__ __launch_bounds__(kBlock) void k_dt_summary(const int* __restrict__ d
             }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-        count += __shfl_xor(count, off);
-    }
-    __shared__ unsigned long long waveBest[kBlock / kWave];
-    __shared__ unsigned waveCount[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) { waveBest[threadIdx.x / kWave] = best; waveCount[threadIdx.x / kWave] = count; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long b = 0ull, s = 0ull;
-        for (int w = 0; w < kBlock / kWave; w++) { b = waveBest[w] > b ? waveBest[w] : b; s += waveCount[w]; }
-        if (s) { atomicMax(key, b); atomicAdd(finite, s); }
-    }
+    struct __attribute__((packed, aligned(4))) DtBest { unsigned long long key; unsigned count; };      // 12 bytes: three words a wave in LDS
+    const DtBest all = block_reduce<kBlock>(DtBest{ best, count }, [](DtBest a, const DtBest& b) {
+        a.key = b.key > a.key ? b.key : a.key; a.count += b.count;
+        return a;
+    });
+    if (threadIdx.x == 0 && all.count) { atomicMax(key, all.key); atomicAdd(finite, (unsigned long long)all.count); }
 }
 
 // ---- morphology: the threshold.  Every voxel equal to `from` whose field value is finite (in reach of the cap the field was made

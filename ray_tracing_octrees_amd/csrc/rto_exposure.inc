@@ -76,22 +76,10 @@ __global__ __launch_bounds__(kBlock) void k_expo_select(const unsigned* __restri
         }
         v0 = row * (unsigned)D.x + wx * 32u;
     }
-    const int lane = (int)threadIdx.x % kWave;
-    const unsigned mine = (unsigned)__popc(cand);
-    unsigned upto = mine;                                               // the counts of lanes 0 .. lane
-    for (int off = 1; off < kWave; off <<= 1) {
-        const unsigned below = __shfl_up(upto, off);
-        if (lane >= off) upto += below;
-    }
-    const unsigned all = __shfl(upto, kWave - 1);
-    if (all) {                                                          // wave-uniform
-        unsigned base = 0u;
-        if (lane == kWave - 1) base = atomicAdd(count, all);
-        unsigned at = __shfl(base, kWave - 1) + upto - mine;
-        while (cand) {
-            list[at++] = v0 + (unsigned)(__ffs(cand) - 1);
-            cand &= cand - 1u;
-        }
+    unsigned at = wave_append((unsigned)__popc(cand), count);
+    while (cand) {
+        list[at++] = v0 + (unsigned)(__ffs(cand) - 1);
+        cand &= cand - 1u;
     }
 }
 
@@ -142,29 +130,21 @@ __global__ __launch_bounds__(kBlock) void k_expo_march(const unsigned* __restric
 // ---- summary over the list.  out[0]: the sum of e; out[1]: voxels with e == 0; out[2]: voxels with e == W (zero before the launch).
 __global__ __launch_bounds__(kBlock) void k_expo_summary(const int* __restrict__ e, const unsigned* __restrict__ list, unsigned count, int W,
                                                         unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long waveSums[kBlock / kWave][3];
-    unsigned long long total = 0ull;
-    unsigned dark = 0u, open = 0u;
+    struct ExSums { unsigned long long total; unsigned dark, open; } s = { 0ull, 0u, 0u };
     for (unsigned i = blockIdx.x * (unsigned)kBlock + threadIdx.x; i < count; i += gridDim.x * (unsigned)kBlock) {
         const int q = e[list[i]];
-        total += (unsigned long long)q;
-        dark += q == 0 ? 1u : 0u;
-        open += q == W ? 1u : 0u;
+        s.total += (unsigned long long)q;
+        s.dark += q == 0 ? 1u : 0u;
+        s.open += q == W ? 1u : 0u;
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        total += __shfl_xor(total, off);
-        dark += __shfl_xor(dark, off);
-        open += __shfl_xor(open, off);
-    }
-    const int lane = (int)threadIdx.x % kWave, wave = (int)threadIdx.x / kWave;
-    if (lane == 0) { waveSums[wave][0] = total; waveSums[wave][1] = dark; waveSums[wave][2] = open; }
-    __syncthreads();
+    s = block_reduce<kBlock>(s, [](ExSums a, const ExSums& b) {
+        a.total += b.total; a.dark += b.dark; a.open += b.open;
+        return a;
+    });
     if (threadIdx.x == 0) {
-        unsigned long long a = 0ull, b = 0ull, c = 0ull;
-        for (int w = 0; w < kBlock / kWave; w++) { a += waveSums[w][0]; b += waveSums[w][1]; c += waveSums[w][2]; }
-        if (a) atomicAdd(&out[0], a);
-        if (b) atomicAdd(&out[1], b);
-        if (c) atomicAdd(&out[2], c);
+        if (s.total) atomicAdd(&out[0], s.total);
+        if (s.dark) atomicAdd(&out[1], (unsigned long long)s.dark);
+        if (s.open) atomicAdd(&out[2], (unsigned long long)s.open);
     }
 }
 

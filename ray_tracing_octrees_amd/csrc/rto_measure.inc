@@ -259,20 +259,14 @@ __global__ __launch_bounds__(kBlock) void k_measure(const int* __restrict__ labe
     // the wave: one label among the lanes that hold any -> one set of sums
     const int lane = t % kWave, wave = t / kWave;
     const bool have = a.label >= 0;
-    const unsigned long long holders = __ballot(have);
-    int first = -1;
-    bool uniform = false;
-    if (holders) {
-        first = __shfl(a.label, (int)__ffsll((long long)holders) - 1);
-        uniform = __ballot(have && a.label != first) == 0ull;
-    }
+    int first;
+    const bool uniform = wave_uniform_label(have, a.label, first);
     unsigned e[kMsLocal];
     ms_expand<FULL>(a, ly, lz, e);                                       // all zero in a lane that holds nothing
     if (uniform) {
 #pragma unroll
         for (int k = 0; k < kMsLocal; k++) {
-            unsigned v = e[k];
-            for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            const unsigned v = wave_sum(e[k]);
             if (lane == 0) waveSums[wave][k] = v;
         }
         if (lane == 0) waveLabel[wave] = first;
@@ -335,18 +329,12 @@ __global__ __launch_bounds__(kBlock) void k_measure_fold(const rto_measure* __re
     g[kMsEuler] = 0ull;
     const int lane = (int)threadIdx.x % kWave, wave = (int)threadIdx.x / kWave;
     const bool have = label >= 0;
-    const unsigned long long holders = __ballot(have);
-    int first = -1;
-    bool uniform = false;
-    if (holders) {
-        first = __shfl(label, (int)__ffsll((long long)holders) - 1);
-        uniform = __ballot(have && label != first) == 0ull;
-    }
+    int first;
+    const bool uniform = wave_uniform_label(have, label, first);
     if (uniform) {
 #pragma unroll
         for (int k = 0; k < kMsWords; k++) {
-            unsigned long long v = g[k];
-            for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            const unsigned long long v = wave_sum(g[k]);
             if (lane == 0) waveSums[wave][k] = v;
         }
         if (lane == 0) waveLabel[wave] = first;

@@ -244,28 +244,21 @@ __global__ __launch_bounds__(kBlock) void k_skel_step(unsigned* X, const unsigne
 
 // ---- summary.  out[0]: voxels with k == 0; out[1]: with k > 0; out[2]: the largest k (zero before the launch).
 __global__ __launch_bounds__(kBlock) void k_skel_summary(const int* __restrict__ k, unsigned n, unsigned long long* __restrict__ out) {
-    __shared__ unsigned waveSums[kBlock / kWave][3];
-    unsigned kept = 0u, gone = 0u, top = 0u;
+    struct SkelSums { unsigned kept, gone, top; } s = { 0u, 0u, 0u };
     for (unsigned v = blockIdx.x * (unsigned)kBlock + threadIdx.x; v < n; v += gridDim.x * (unsigned)kBlock) {
         const int q = k[v];
-        kept += q == 0 ? 1u : 0u;
-        gone += q > 0 ? 1u : 0u;
-        top = max(top, (unsigned)max(q, 0));
+        s.kept += q == 0 ? 1u : 0u;
+        s.gone += q > 0 ? 1u : 0u;
+        s.top = max(s.top, (unsigned)max(q, 0));
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        kept += __shfl_xor(kept, off);
-        gone += __shfl_xor(gone, off);
-        top = max(top, __shfl_xor(top, off));
-    }
-    const int lane = (int)threadIdx.x % kWave, wave = (int)threadIdx.x / kWave;
-    if (lane == 0) { waveSums[wave][0] = kept; waveSums[wave][1] = gone; waveSums[wave][2] = top; }
-    __syncthreads();
+    s = block_reduce<kBlock>(s, [](SkelSums a, const SkelSums& b) {
+        a.kept += b.kept; a.gone += b.gone; a.top = max(a.top, b.top);
+        return a;
+    });
     if (threadIdx.x == 0) {
-        unsigned long long a = 0ull, b = 0ull, c = 0ull;
-        for (int w = 0; w < kBlock / kWave; w++) { a += waveSums[w][0]; b += waveSums[w][1]; c = max(c, (unsigned long long)waveSums[w][2]); }
-        if (a) atomicAdd(&out[0], a);
-        if (b) atomicAdd(&out[1], b);
-        if (c) atomicMax(&out[2], c);
+        if (s.kept) atomicAdd(&out[0], (unsigned long long)s.kept);
+        if (s.gone) atomicAdd(&out[1], (unsigned long long)s.gone);
+        if (s.top) atomicMax(&out[2], (unsigned long long)s.top);
     }
 }
 

@@ -31,7 +31,6 @@ static_assert(kThickTabHead % 4 == 0 && kThickTabHead >= kThickMaxC + 1, "the of
 __global__ __launch_bounds__(kBlock) void k_thick_gather(const int* __restrict__ d2, CcDims D, int tilesX, int tilesY, int c, int h,
                                                         const int* __restrict__ tab, int* __restrict__ out) {
     __shared__ uint8_t B[kThickLds];                      // min(d2, c) of the tile and its halo of h voxels; 0 outside the grid
-    __shared__ int waveMax[kBlock / kWave];
     const int t = (int)threadIdx.x;
     const unsigned bid = blockIdx.x;
     const int x0 = (int)(bid % (unsigned)tilesX) * kCcTileX, y0 = (int)((bid / (unsigned)tilesX) % (unsigned)tilesY) * kCcTileY,
@@ -66,13 +65,8 @@ __global__ __launch_bounds__(kBlock) void k_thick_gather(const int* __restrict__
         B[i] = (uint8_t)v;
         m = max(m, v);
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off));
-    if ((t % kWave) == 0) waveMax[t / kWave] = m;
-    __syncthreads();
-    int M = 0;                                                          // the largest D of the block: no ball in reach is larger
-#pragma unroll
-    for (int w = 0; w < kBlock / kWave; w++) M = max(M, waveMax[w]);
-    M = __builtin_amdgcn_readfirstlane(M);
+    // the largest D of the block: no ball in reach is larger (the barrier of the maximum is also the one after which B is read)
+    const int M = __builtin_amdgcn_readfirstlane(block_max<kBlock>(m));
     const int lim = min(c, M);                                          // an offset with o^2 >= M is inside no ball
     int at[kThickPerThread], best[kThickPerThread];
 #pragma unroll

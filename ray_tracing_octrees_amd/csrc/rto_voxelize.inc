@@ -6,7 +6,7 @@
 // the flat (face, voxel) pair space (DESIGN.md section 13):
 //   k_vox_setup        one thread per face: float vertices, voxel box, the per-face terms of the test in the reference's order
 //                      (v0, v1, d00, d01, d11, 1 / denom) and the number of voxels in the box (0: skipped or degenerate face);
-//   k_vox_scan_*       exclusive scan of those counts (block sums, one block over them, block-local scans);
+//   k_vox_scan_faces   exclusive scan of those counts (block sums, k_scan_counts over them, block-local scans);
 //   k_vox_fill         each block finds its first and last face once by binary search in the offsets; each thread then walks
 //                      its run of kVoxRun consecutive pairs forward, with the per-voxel part of the test only;
 //   k_vox_bbox         the FILLED voxels' integer box and count (recentring and the result's filled count).
@@ -85,59 +85,16 @@ __global__ __launch_bounds__(kBlock) void k_vox_setup(const double* __restrict__
         }
         counts[f] = cnt;
     }
-    // block sum for the scan
-    for (int off = kWave / 2; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    __shared__ long long waveSum[kBlock / kWave];
-    if ((threadIdx.x % kWave) == 0) waveSum[threadIdx.x / kWave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long s = 0;
-        for (int w = 0; w < kBlock / kWave; w++) s += waveSum[w];
-        blockSums[blockIdx.x] = s;
-    }
-}
-
-// Exclusive scan of nb block sums in place by one block of 1024 threads; total -> *total.
-__global__ __launch_bounds__(1024) void k_vox_scan_blocks(long long* __restrict__ sums, int nb, long long* __restrict__ total) {
-    __shared__ long long part[1024];
-    __shared__ long long carry;
-    const int t = (int)threadIdx.x;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += 1024) {
-        const long long x = base + t < nb ? sums[base + t] : 0;
-        part[t] = x;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {            // Hillis-Steele inclusive scan
-            const long long y = t >= off ? part[t - off] : 0;
-            __syncthreads();
-            part[t] += y;
-            __syncthreads();
-        }
-        if (base + t < nb) sums[base + t] = carry + part[t] - x;
-        __syncthreads();
-        if (t == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (t == 0) *total = carry;
+    cnt = block_sum<kBlock>(cnt);                              // for the scan
+    if (threadIdx.x == 0) blockSums[blockIdx.x] = cnt;
 }
 
 // offsets[f] = exclusive prefix of counts (block-local scan + the block's base); offsets[nf] = total.
 __global__ __launch_bounds__(kBlock) void k_vox_scan_faces(const long long* __restrict__ counts, int nf, const long long* __restrict__ blockBase,
                                                            const long long* __restrict__ total, long long* __restrict__ offsets) {
-    __shared__ long long part[kBlock];
-    const int t = (int)threadIdx.x;
-    const int f = (int)blockIdx.x * kBlock + t;
-    const long long x = f < nf ? counts[f] : 0;
-    part[t] = x;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const long long y = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += y;
-        __syncthreads();
-    }
-    if (f < nf) offsets[f] = blockBase[blockIdx.x] + part[t] - x;
+    const int f = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+    const long long before = block_exclusive_scan<kBlock>(f < nf ? counts[f] : 0ll);
+    if (f < nf) offsets[f] = blockBase[blockIdx.x] + before;
     if (f == 0) offsets[nf] = *total;
 }
 
@@ -224,27 +181,15 @@ __global__ __launch_bounds__(kBlock) void k_vox_bbox(const uint8_t* __restrict__
             if (++x == dimX) { x = 0; if (++y == dimY) { y = 0; z++; } }
         }
     }
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        cnt += __shfl_xor(cnt, off);
-        for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], __shfl_xor(lo[a], off)); hi[a] = max(hi[a], __shfl_xor(hi[a], off)); }
-    }
-    __shared__ int sLo[kBlock / kWave][3], sHi[kBlock / kWave][3];
-    __shared__ unsigned long long sCnt[kBlock / kWave];
-    const int w = (int)threadIdx.x / kWave;
-    if ((threadIdx.x % kWave) == 0) {
-        sCnt[w] = cnt;
-        for (int a = 0; a < 3; a++) { sLo[w][a] = lo[a]; sHi[w][a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < kBlock / kWave; k++) {
-            cnt += sCnt[k];
-            for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], sLo[k][a]); hi[a] = max(hi[a], sHi[k][a]); }
-        }
-        if (cnt) {
-            atomicAdd(filled, cnt);
-            for (int a = 0; a < 3; a++) { atomicMin(&box[a], lo[a]); atomicMax(&box[3 + a], hi[a]); }
-        }
+    struct VoxFilled { unsigned long long cnt; IntBox box; };
+    const VoxFilled all = block_reduce<kBlock>(VoxFilled{ cnt, { { lo[0], lo[1], lo[2] }, { hi[0], hi[1], hi[2] } } }, [](VoxFilled a, const VoxFilled& b) {
+        a.cnt += b.cnt; a.box = OpBoxUnion()(a.box, b.box);
+        return a;
+    });
+    if (threadIdx.x == 0 && all.cnt) {
+        atomicAdd(filled, all.cnt);
+#pragma unroll
+        for (int a = 0; a < 3; a++) { atomicMin(&box[a], all.box.lo[a]); atomicMax(&box[3 + a], all.box.hi[a]); }
     }
 }
 
@@ -371,7 +316,7 @@ int rto_voxelize_mesh(rto_context* c, const double* xyz, int64_t nv, const int32
             RTO_HIP(c, hipMemsetAsync(d_invalid, 0, sizeof(int), s));
             RTO_HIP(c, events.record(0, s));
             hipLaunchKernelGGL(rto::k_vox_setup, dim3((unsigned)nb), dim3(kBlock), 0, s, d_xyz, d_tris, nfi, g, d_faces, d_counts, d_sums, d_invalid);
-            hipLaunchKernelGGL(rto::k_vox_scan_blocks, dim3(1), dim3(1024), 0, s, d_sums, nb, d_total);
+            hipLaunchKernelGGL((rto::k_scan_counts<1024, long long, long long>), dim3(1), dim3(1024), 0, s, d_sums, nb, d_sums, d_total);
             hipLaunchKernelGGL(rto::k_vox_scan_faces, dim3((unsigned)nb), dim3(kBlock), 0, s, d_counts, nfi, d_sums, d_total, d_off);
             RTO_HIP(c, hipGetLastError());
             RTO_HIP(c, events.record(1, s));

@@ -34,8 +34,8 @@ TABLE = {
     "cc_local:wide:chunk-beyond-row": ("k_cc_local<WIDE>: c0 >= D.x, dimX = 16 mod 32", "16 x 1 x 1"),
     "cc_local:rows-beyond-grid": ("k_cc_local: !rowIn, dimY % 8 or dimZ % 8", "1 x 1 x 1"),
     "cc_local:rows-all-inside": ("k_cc_local: rowIn for every thread", "1 x 8 x 8"),
-    "cc_scan:rounds==1": ("k_cc_scan: numBlocks <= kBlock", "1 x 1 x 1"),
-    "cc_scan:rounds>=2": ("k_cc_scan: numBlocks > kBlock, above 256 x 4096 voxels", "1,048,577 voxels"),
+    "cc_scan:rounds==1": ("k_scan_counts<kBlock> behind k_cc_flatten: n <= kBlock chunks", "1 x 1 x 1"),
+    "cc_scan:rounds>=2": ("k_scan_counts<kBlock>: i0 += THREADS, n > kBlock chunks, above 256 x 4096 voxels", "1,048,577 voxels"),
     "cc_stats:all-whole": ("k_cc_stats: whole for every thread, n % 32 == 0", "32 x 1 x 1"),
     "cc_stats:tail-partial": ("k_cc_stats: !whole in the last thread, n % 32 != 0", "1 x 1 x 1"),
     "cc_label:count==0": ("cc_label: total == 0, k_cc_stats and k_cc_touches are not launched", "a grid without the set"),
@@ -182,7 +182,7 @@ def label(dims, count=None):
     """rto_label_components.  count: the components of the labelled set, None when the caller does not know it."""
     n = _voxels(dims)
     out = _row_kernel("cc_local", dims, "chunk-beyond-row")
-    out.add("cc_scan:rounds" + ("==1" if (n + CHUNK - 1) // CHUNK <= BLOCK else ">=2"))      # b0 += kBlock over the chunks
+    out.add("cc_scan:rounds" + ("==1" if (n + CHUNK - 1) // CHUNK <= BLOCK else ">=2"))      # i0 += THREADS over the chunks
     out.add("cc_stats:" + ("all-whole" if n % 32 == 0 else "tail-partial"))                  # v0 + kCcStatPerThread <= D.n
     if count == 0:
         out.add("cc_label:count==0")                                    # if (total)

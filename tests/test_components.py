@@ -23,7 +23,7 @@ SETS = (cr.SET_SOLID, cr.SET_EMPTY)
 CONNS = (cr.CONN_FACE, cr.CONN_FULL)
 TILE = (32, 8, 8)           # k_cc_local's tile, x, y, z (rto_components.inc)
 # VGPRs the build gives; a kernel that grows past its line here has changed
-CC_VGPR = {"k_cc_local": 38, "k_cc_merge": 20, "k_cc_flatten": 14, "k_cc_scan": 22, "k_cc_rank": 26, "k_cc_label": 8,
+CC_VGPR = {"k_cc_local": 38, "k_cc_merge": 20, "k_cc_flatten": 14, "k_scan_countsILi256Ejj": 24, "k_cc_rank": 26, "k_cc_label": 8,
            "k_cc_stats": 28, "k_cc_touches": 8, "k_cc_largest": 8, "k_cc_select": 4, "k_cc_flip": 28}
 
 
@@ -312,14 +312,14 @@ def test_component_abi_layout_and_exports():
 
 
 def test_component_kernels_keep_their_budgets():
-    """The built assembly (the product's flags): every k_cc_* kernel without scratch, spills or v_mfma, at the VGPR counts DESIGN.md
+    """The built assembly (the product's flags): every k_cc_* kernel and the components' k_scan_counts without scratch, spills or v_mfma, at the VGPR counts DESIGN.md
     section 18 states; the 16-byte forms of k_cc_local and k_cc_flip move rows with dwordx4 accesses."""
     import test_isa_contract as isa
     asm = isa.built_asm()
     if asm is None:
         pytest.fail("no hipcc: the budget cannot be checked")
     meta = isa.kernel_meta(asm)
-    names = [k for k in meta if "k_cc_" in k]
+    names = [k for k in meta if "k_cc_" in k or "k_scan_countsILi256Ejj" in k]     # the scan of the chunk counts: the shared kernel's kBlock, unsigned form
     assert len(names) == 16, names              # local x4, merge x2, flip x2, eight others
     seen = set()
     for k in names:

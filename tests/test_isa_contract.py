@@ -176,7 +176,7 @@ def test_tie_update_of_the_closest_hit_kernel_has_no_lane_mask_operand():
 
 def test_no_short_circuit_updates_with_calls_inside_divergent_loops():
     """The shape that was miscompiled -- `a || (b && c && f(..))` deciding an update -- must not reappear in device code."""
-    for name in ("rto_device.hip.h", "rto_query.inc", "rto_tri_query.inc", "rto_lit.inc"):
+    for name in ("rto_device.hip.h", "rto_collectives.hip.h", "rto_query.inc", "rto_tri_query.inc", "rto_lit.inc"):
         src = open(os.path.join(CSRC, name)).read()
         src = re.sub(r"//[^\n]*", "", src)
         bad = re.findall(r"if\s*\([^;{}]*\|\|\s*\([^;{}()]*&&[^;{}()]*&&[^;{}]*\w+\([^;{}]*\)\s*\)\s*\)\s*\{?[^;]*=", src)

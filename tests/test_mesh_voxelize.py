@@ -139,13 +139,13 @@ def test_voxelize_abi_layout_and_exports():
 
 
 def test_voxelize_kernels_keep_their_budgets():
-    """The built assembly (the product's flags): every k_vox_* kernel without scratch, spills or v_mfma, within the VGPR budget."""
+    """The built assembly (the product's flags): every k_vox_* kernel and the voxelizer's k_scan_counts without scratch, spills or v_mfma, within the VGPR budget."""
     import test_isa_contract as isa
     asm = isa.built_asm()
     if asm is None:
         pytest.fail("no hipcc: the budget cannot be checked")
     meta = isa.kernel_meta(asm)
-    names = [k for k in meta if "k_vox_" in k]
+    names = [k for k in meta if "k_vox_" in k or "k_scan_countsILi1024Exx" in k]      # the scan of the block sums: the shared kernel's 64-bit form
     assert len(names) == 5, names
     for k in names:
         m = meta[k]

@@ -89,7 +89,7 @@ def test_many_small_carries_between_scan_chunks():
     c = family("many_small")
     cnt = _counts(c)
     blocks = -(-len(cnt) // 256)                                   # k_vox_setup blocks: one block sum each
-    assert blocks > 2 * 1024                                       # three chunks of k_vox_scan_blocks: the carry runs twice
+    assert blocks > 2 * 1024                                       # three rounds of k_scan_counts: the carry runs twice
     assert not cnt[:5000].any() and not cnt[-5000:].any()          # runs without voxels at both ends
     assert (cnt == 0).sum() > 50_000
     chunk = 1024 * 256                                             # faces behind one chunk of block sums

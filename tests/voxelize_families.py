@@ -2,7 +2,7 @@
 generator returns a Case: rows (float64 [n, 3]), faces (int32 [m, 3]), the voxel size asked for, and grid = None (AUTO) or the
 FIXED (dims (x, y, z), grid_min float32[3], voxel_size float32).
 
-- many_small: 600 k faces of a few voxels each, so k_vox_scan_blocks carries between three chunks of 1024 block sums, with long
+- many_small: 600 k faces of a few voxels each, so k_scan_counts carries between three rounds of 1024 block sums, with long
   runs of faces that have no voxels (outside the grid, degenerate, a NaN row) at the start, the end and inside the list.
 - boundaries: faces whose pair spans start and end exactly on multiples of 16 (one k_vox_fill thread's run) and 4096 (one
   block), single-voxel faces, faces of 4095 / 4096 / 4097 pairs and empty faces on those boundaries.

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--dirs", type=int, default=64)
     ap.add_argument("--reach", type=int, default=16, help="the reach of the limited runs")
     ap.add_argument("--cpu-only", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the comparison with, and the timing of, the CPU form (no steps, no ns_per_step)")
     a = ap.parse_args()
     from geodesic_bench import calgary, copy_ms, sphere      # the scenes and the copy floor of section 20's table
     dirs = hip.quantize_directions(hemisphere(a.dirs))
@@ -53,24 +54,29 @@ def main():
         for mode in modes:
             for reach in (None, a.reach):
                 r = hip.EXPO_NO_LIMIT if reach is None else reach
-                t0 = time.perf_counter()
-                rc, want, ws, steps = vg.exposureField(dirs, weights, mode, r, withSteps=True)
-                cpu = (time.perf_counter() - t0) * 1e3
-                assert rc == 0
-                line = dict(base, mode="skin" if mode == hip.EXPO_SKIN else "all", reach=reach, evaluated=int(ws["evaluated"]), steps=int(steps),
-                            dark=int(ws["dark"]), open=int(ws["open"]), cpu_ms=round(cpu, 1))
+                line = dict(base, mode="skin" if mode == hip.EXPO_SKIN else "all", reach=reach)
+                want, steps = None, 0
+                if not a.no_cpu:
+                    t0 = time.perf_counter()
+                    rc, want, ws, steps = vg.exposureField(dirs, weights, mode, r, withSteps=True)
+                    cpu = (time.perf_counter() - t0) * 1e3
+                    assert rc == 0
+                    line.update(evaluated=int(ws["evaluated"]), steps=int(steps), dark=int(ws["dark"]), open=int(ws["open"]), cpu_ms=round(cpu, 1))
                 if ctx:
                     got, gs = ctx.exposure_field(dirs, weights, mode, reach)          # the warm-up call, and the comparison
-                    if not np.array_equal(got, want) or gs.tobytes() != ws.tobytes():
+                    if want is not None and (not np.array_equal(got, want) or gs.tobytes() != ws.tobytes()):
                         raise SystemExit(f"{name} mode {mode} reach {reach}: the field differs from the CPU answer")
+                    if want is None:
+                        line.update(evaluated=int(gs["evaluated"]), dark=int(gs["dark"]), open=int(gs["open"]))
                     del got
                     ms = []
                     for k in range(a.rounds):
                         ctx._check(ctx._L.rto_exposure_field(ctx._h, dirs.ctypes.data, weights.ctypes.data, len(dirs), mode, r, gs.ctypes.data))
                         ms.append(ctx.last_exposure_ms())
                     m = np.median(np.asarray(ms, np.float64), axis=0)
-                    line.update(prepare_ms=round(float(m[0]), 4), march_ms=round(float(m[1]), 4), summary_ms=round(float(m[2]), 4),
-                                ns_per_step=round(float(m[1]) * 1e6 / max(int(steps), 1), 5))
+                    line.update(prepare_ms=round(float(m[0]), 4), march_ms=round(float(m[1]), 4), summary_ms=round(float(m[2]), 4))
+                    if steps:
+                        line.update(ns_per_step=round(float(m[1]) * 1e6 / int(steps), 5))
                 del want
                 print(json.dumps(line), flush=True)
 
