@@ -1249,6 +1249,85 @@ int  rto_exposure_device(rto_context* ctx, int32_t** d_e);
 /* Device time in ms of the last rto_exposure_field: prepare (bit rows, selection, templates), march, summary (-1: not run). */
 int  rto_last_exposure_ms(const rto_context* ctx, float ms[3]);
 
+/* ---- part segmentation: watershed of the distance field, parts and necks ----------
+ * Which parts is one component made of?  Two grains that touch, two rooms joined by a door, the pores and throats of one
+ * cavity: every voxel of a set climbs to the nearest local maximum of its distance to the surface, and basins whose connecting
+ * neck is wide relative to the smaller of the two are merged.  No reference counterpart.  Every result is an integer that a plain
+ * loop over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule.  Index, sets and connectivity are rto_label_components'; voxels outside the grid belong to no set.
+ *   height    for v in the set S, h[v] is rto_distance_field's uncapped d2 from v to the voxels of the grid NOT in S (the transform
+ *             of the other set): h >= 1 on S, 0 off it; RTO_DIST_NONE on all of S when the grid has no voxel outside S.
+ *   order     key(v) = (h[v], -v), compared lexicographically: a strict total order, so plateaus do not exist.
+ *   ascent    up(v) is the neighbour of v under the connectivity, inside S, with the largest key, if that key exceeds key(v);
+ *             otherwise v is a peak and up(v) = v.  The basin of a peak is every voxel whose up chain ends there.  Basins are
+ *             numbered in ascending order of their peak's linear index.
+ *   passes    for every pair of adjacent voxels (a, b) of S in different basins the pass height is min(h[a], h[b]) and its index
+ *             min(a, b).  A basin edge (A < B by number) holds s, the largest pass height; at, the smallest pass index that
+ *             attains it; pairs, the number of such voxel pairs.
+ *   merge     ratio is an integer in [0, RTO_PARTS_RATIO_MAX].  Basin edges are processed in the order (s descending, A ascending,
+ *             B ascending); a union-find over basins carries P(cluster), the largest peak height in it.  Edge (A, B) joins
+ *             find(A) != find(B) exactly when 1,000,000 s >= ratio^2 min(P(find A), P(find B)) in int64; on a join P becomes the
+ *             larger of the two.  ratio = 0 joins every adjacent pair: the parts are the components and the label volume equals
+ *             rto_label_components' bit for bit.  ratio = 1001 joins nothing: the parts are the basins.  ratio = 1000 joins only
+ *             across passes as high as the lower peak (the fragments of a flat top).  No monotonicity in ratio is claimed: merges
+ *             raise P and make later tests stricter.
+ *   parts     the clusters, numbered in ascending order of their smallest voxel index; the label volume is int32, -1 off S.
+ *   necks     one per pair of adjacent parts, sorted by (part_lo, part_hi): h is the largest s among the basin edges between the
+ *             two, at is that edge's (ties in s go to the smaller at), pairs is summed.  sqrt(h) voxels is the throat radius.
+ *   cut       rto_edit_parts segments afresh (the resident result is not consulted) and flips every voxel v of S that has a
+ *             neighbour u in S, under the connectivity, with part[u] > part[v].  Afterwards no two voxels of different parts are
+ *             adjacent.  *changed (may be NULL) = voxels flipped; when it is > 0 the context is left exactly as
+ *             rto_edit_components leaves it after a change; changed == 0 touches nothing.
+ * rto_segment_parts keeps the label volume and both tables resident; they describe the grid they were made from, and every call
+ * that changes or replaces the grid frees them (the calls that free the component labels): the readers then return
+ * RTO_E_INVALID.  An empty set gives 0 parts, a volume of -1 and empty tables.  Synchronous on the context's stream.
+ * Errors, each leaving the context untouched: RTO_E_INVALID (unknown set or connectivity, ratio outside [0, 1001], too small a
+ * capacity, nothing resident for the readers); RTO_E_NO_OCTREE; RTO_E_UNSUPPORTED (rto_distance_field's conditions, and a grid of
+ * more than 2^31 - 2 voxels); RTO_E_INTERNAL (the ascent did not flatten in 32 rounds, or the basin-edge table was still full after
+ * 8 doublings: a defect). */
+#define RTO_PARTS_RATIO_MAX 1001
+typedef struct rto_part {           /* 64 bytes; the first 48 have rto_component's layout */
+    int64_t root;                   /* smallest linear voxel index of the part */
+    int64_t voxels;                 /* its size */
+    int32_t lo[3], hi[3];           /* inclusive voxel bounding box */
+    int32_t touches;                /* as rto_component.touches */
+    int32_t basins;                 /* basins merged into the part */
+    int64_t peak;                   /* the voxel of the part with the largest key */
+    int32_t peak_h;                 /* h there */
+    int32_t reserved;               /* 0 */
+} rto_part;
+typedef struct rto_neck {           /* 32 bytes */
+    int32_t part_lo, part_hi;       /* part_lo < part_hi */
+    int32_t h;                      /* the highest pass between the two parts */
+    int32_t reserved;               /* 0 */
+    int64_t at;                     /* the smallest pass index that attains it */
+    int64_t pairs;                  /* adjacent voxel pairs between the two parts: the contact area */
+} rto_neck;
+typedef struct rto_parts_summary {  /* 32 bytes */
+    int64_t parts, basins, necks;
+    int64_t pairs;                  /* summed over the necks */
+} rto_parts_summary;
+
+int  rto_segment_parts(rto_context* ctx, int set, int connectivity, int ratio, rto_parts_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_part_labels(rto_context* ctx, int32_t* out, int64_t capacity);
+/* out == NULL: the count alone. */
+int  rto_download_parts(rto_context* ctx, rto_part* out, int64_t capacity, int64_t* count);
+int  rto_download_necks(rto_context* ctx, rto_neck* out, int64_t capacity, int64_t* count);
+/* The resident label volume and tables (device pointers the context owns, valid until they are freed); any pointer may be NULL. */
+int  rto_parts_device(rto_context* ctx, int32_t** d_labels, rto_part** d_parts, int64_t* parts, rto_neck** d_necks, int64_t* necks);
+int  rto_edit_parts(rto_context* ctx, int set, int connectivity, int ratio, int64_t* changed /* may be NULL */);
+/* The last rto_segment_parts in ms: the transform, the ascent with its flatten rounds, ranking with the basin table, basin edges
+ * (device time each), and the host's merge with the downloads, uploads and the relabel launch (host clock); -1: not run. */
+int  rto_last_parts_ms(const rto_context* ctx, float ms[5]);
+/* The last rto_segment_parts: basins, basin edges downloaded (one record each), flatten launches up to and including the first
+ * that changed nothing, and the slots of the edge table that held them (0: fewer than two basins, no table).  Any may be NULL. */
+int  rto_debug_parts(const rto_context* ctx, int64_t* basins, int64_t* edges, int* rounds, int64_t* capacity);
+/* The first capacity of the edge table from now on (rounded up to a power of two; 0: sized from the basin count).  A table that
+ * fills up is discarded and made again with twice the slots, at most 8 times: no value depends on the capacity. */
+int  rto_debug_parts_capacity(rto_context* ctx, int64_t first_capacity);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -22,8 +22,8 @@ using namespace rto;
 namespace rto { struct CcComp; }   // rto_components.inc
 
 // The resident voxel fields of a context (rto_context::d_field) and the noun each goes by in error texts.
-enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldCount };
-static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure" };
+enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldParts, kFieldCount };
+static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure", "part label" };
 
 struct rto_context {
     int device = -1;
@@ -185,9 +185,10 @@ struct rto_context {
     rto_measure* d_ccMeasures = nullptr;      // nullptr: no measures resident; count records, then the total
     float measureMs[2] = { -1.f, -1.f };      // the last rto_measure_components: the measuring kernels, the total
 
-    // resident voxel fields: the last distance, geodesic, thickness, skeleton and exposure field of the resident grid, one int32 per
-    // voxel each (nullptr: none resident).  A maker owns its new field as a FieldDraft until the call has succeeded; all five are
-    // dropped whenever the grid changes (free_fields).  What a field was made for, and the times of its maker, are kept per family below.
+    // resident voxel fields: the last distance, geodesic, thickness, skeleton and exposure field and the last part labels of the
+    // resident grid, one int32 per voxel each (nullptr: none resident).  A maker owns its new field as a FieldDraft until the call
+    // has succeeded; all six are dropped whenever the grid changes (free_fields).  What a field was made for, and the times of its
+    // maker, are kept per family below.
     int* d_field[kFieldCount] = {};
 
     // distance fields (rto_distance.inc)
@@ -223,6 +224,16 @@ struct rto_context {
     int expoN = 0, expoMode = 0, expoReach = 0;
     int64_t expoW = 0;
     float expoMs[3] = { -1.f, -1.f, -1.f };   // the last rto_exposure_field: prepare, march, summary
+
+    // part segmentation (rto_parts.inc): the label volume is d_field[kFieldParts]; the part and neck tables of that volume, its
+    // summary and what the last rto_segment_parts did (basin edges downloaded, edge-table slots, flatten rounds)
+    rto_part* d_partTab = nullptr;
+    rto_neck* d_neckTab = nullptr;
+    rto_parts_summary partsSum = { 0, 0, 0, 0 };
+    int64_t partsEdges = 0, partsTableCap = 0;
+    int64_t partsFirstCap = 0;                // the first edge-table capacity (rto_debug_parts_capacity); 0: sized from the basin count
+    int partsRounds = 0;
+    float partsMs[5] = { -1.f, -1.f, -1.f, -1.f, -1.f };   // the last rto_segment_parts: transform, ascent + flatten, ranking + basin table, edges, host merge + relabel
 };
 
 static thread_local std::string g_createError;
@@ -285,9 +296,17 @@ static void free_fields(rto_context* c) {
     for (int*& d : c->d_field) { (void)hipFree(d); d = nullptr; }
 }
 
+// The part and neck tables of the resident part labels (rto_parts.inc); the label volume itself is a field (free_fields).
+static void free_parts(rto_context* c) {
+    (void)hipFree(c->d_partTab); c->d_partTab = nullptr;
+    (void)hipFree(c->d_neckTab); c->d_neckTab = nullptr;
+    c->partsSum = rto_parts_summary{ 0, 0, 0, 0 };
+}
+
 // The octree's arrays and everything derived from them; the voxel grid rto_build_octree keeps stays (rebuild_from_resident_grid builds from it).
 static void free_octree_arrays(rto_context* c) {
     free_components(c);
+    free_parts(c);
     free_fields(c);
     if (c->asyncPooled) {
         (void)hipDeviceSynchronize();          // like hipFree: frames on caller streams may still read the arrays
@@ -965,7 +984,7 @@ static int download_resident(rto_context* c, const char* who, void* out, int64_t
     return RTO_OK;
 }
 
-// ---------------------------------------------------------------- resident voxel fields: what their five families share
+// ---------------------------------------------------------------- resident voxel fields: what their six families share
 // A field that is the call's own until the call has succeeded.  begin(): the device is set, the context's stream drained and one
 // int32 per voxel of the resident grid allocated, in that order.  publish(): the slot's old field is freed and the new one takes its
 // place.  A call that returns before publish() leaves the slot as it was and the draft goes with the scope.
@@ -1097,9 +1116,9 @@ struct VoxelList {
 // voxelSize) leaves, followed by rto_build_leaf_triangles(NULL) when `triangles` -- the callers pass "were triangles resident?",
 // sampled before the call, or what their parameters ask for.  Every grid edit and the voxelizer's commit end here.
 //   dropped:  the octree's arrays and all that describes the grid or the tree as it was (free_octree_arrays): component labels,
-//             table and measures, the five resident voxel fields (distance, geodesic, thickness, skeleton, exposure), leaf triangles
-//             and their records, cull buffers and the culling switch, occupancy cells, mesh levels; every stream's tile orders and
-//             cost history are invalidated.
+//             table and measures, the six resident voxel fields (distance, geodesic, thickness, skeleton, exposure, part
+//             labels) with the part and neck tables, leaf triangles and their records, cull buffers and the culling switch,
+//             occupancy cells, mesh levels; every stream's tile orders and cost history are invalidated.
 //   survives: d_vox, voxDim, gridMin, voxelSize, buildPath (and everything that is not per octree: kernel mode, frame buffers,
 //             the last extracted mesh, the thickness gather's offset table).
 //   timing:   each build's buildMs goes to *octree_ms / *tris_ms (either may be nullptr) as soon as that build has succeeded.
@@ -1108,7 +1127,7 @@ struct VoxelList {
 //             released by the next free_octree_arrays or by rto_destroy.  The triangle build fails: the new octree is complete
 //             and usable, *octree_ms is written, and the triangle buffers are what rto_build_leaf_triangles leaves on that error.
 // An edit that finds it changed no voxel returns without coming here: the grid is byte for byte what it was, so nothing is
-// dropped -- octree, triangles, labels, measures, the five fields and the frustum state all stay.
+// dropped -- octree, triangles, labels, measures, the six fields and the frustum state all stay.
 static int rebuild_from_resident_grid(rto_context* c, bool triangles, float* octree_ms, float* tris_ms) {
     const int R = root_depth_of(c->voxDim[0], c->voxDim[1], c->voxDim[2]);
     free_octree_arrays(c);
@@ -3015,3 +3034,4 @@ int rto_synchronize(rto_context* c) {
 #include "rto_measure.inc"
 #include "rto_skeleton.inc"
 #include "rto_exposure.inc"
+#include "rto_parts.inc"

@@ -58,6 +58,8 @@ SYMBOLS = (
     "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
     "rto_debug_thickness_table",
     "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
+    "rto_segment_parts", "rto_download_part_labels", "rto_download_parts", "rto_download_necks", "rto_parts_device", "rto_edit_parts",
+    "rto_last_parts_ms", "rto_debug_parts", "rto_debug_parts_capacity",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -116,6 +118,12 @@ THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
 MEASURE_DTYPE = np.dtype([("voxels", "<i8"), ("faces", "<i8", (6,)), ("cells", "<i8", (3,)), ("euler", "<i8"), ("sum", "<i8", (3,)),
                           ("sum2", "<i8", (6,))])
 MEASURE_MAX_DIM = 32768  # RTO_MEASURE_MAX_DIM: the largest dimension rto_measure_components takes
+# struct rto_part (64 bytes), rto_neck (32), rto_parts_summary (32): part segmentation (rto_segment_parts, rto_edit_parts)
+PART_DTYPE = np.dtype([("root", "<i8"), ("voxels", "<i8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("touches", "<i4"), ("basins", "<i4"),
+                       ("peak", "<i8"), ("peak_h", "<i4"), ("reserved", "<i4")])
+NECK_DTYPE = np.dtype([("part_lo", "<i4"), ("part_hi", "<i4"), ("h", "<i4"), ("reserved", "<i4"), ("at", "<i8"), ("pairs", "<i8")])
+PARTS_SUMMARY_DTYPE = np.dtype([("parts", "<i8"), ("basins", "<i8"), ("necks", "<i8"), ("pairs", "<i8")])
+PARTS_RATIO_MAX = 1001   # RTO_PARTS_RATIO_MAX: joins nothing, the parts are the basins
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -530,6 +538,15 @@ def load():
     L.rto_download_measures.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.rto_measures_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.rto_last_measure_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_segment_parts.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.rto_download_part_labels.argtypes = [vp, vp, C.c_int64]
+    L.rto_download_parts.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_download_necks.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rto_parts_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_edit_parts.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    L.rto_last_parts_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_parts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.rto_debug_parts_capacity.argtypes = [vp, C.c_int64]
     _lib = L
     return L
 
@@ -1103,6 +1120,63 @@ class Context:
         changed = C.c_int64()
         self._check(self._L.rto_edit_components(self._h, int(set), int(connectivity), int(select), int(arg), C.byref(changed)))
         return changed.value
+
+    # -- part segmentation ---------------------------------------------------------
+    def segment_parts(self, set: int = SET_SOLID, connectivity: int = CONN_FACE, ratio: int = 800):
+        """rto_segment_parts: the watershed of the squared distance field of SET_SOLID or SET_EMPTY under CONN_FACE or CONN_FULL,
+        basins merged where 1,000,000 s >= ratio^2 min(P, P') (0: the components, PARTS_RATIO_MAX: the basins); the summary as a
+        PARTS_SUMMARY_DTYPE scalar.  Labels and both tables stay resident until the grid changes."""
+        summary = np.zeros((), PARTS_SUMMARY_DTYPE)
+        self._check(self._L.rto_segment_parts(self._h, int(set), int(connectivity), int(ratio), summary.ctypes.data))
+        return summary
+
+    def _parts_table(self, symbol: str, dtype) -> np.ndarray:
+        n = C.c_int64()
+        self._check(getattr(self._L, symbol)(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype)
+        if n.value:
+            self._check(getattr(self._L, symbol)(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def part_labels(self) -> np.ndarray:
+        """The resident part labels as int32 (dimZ, dimY, dimX): the part's number, -1 outside the set."""
+        return self._resident_field("rto_parts_device", "rto_download_part_labels", outputs=5)
+
+    def parts(self) -> np.ndarray:
+        """The resident part table as a PART_DTYPE array, in ascending order of the parts' smallest voxel."""
+        return self._parts_table("rto_download_parts", PART_DTYPE)
+
+    def necks(self) -> np.ndarray:
+        """The resident neck table as a NECK_DTYPE array, sorted by (part_lo, part_hi)."""
+        return self._parts_table("rto_download_necks", NECK_DTYPE)
+
+    def parts_device(self):
+        """(device pointer of the int32 label volume, of the 64-byte part records, parts, of the 32-byte neck records, necks)."""
+        l, p, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n, m = C.c_int64(), C.c_int64()
+        self._check(self._L.rto_parts_device(self._h, C.byref(l), C.byref(p), C.byref(n), C.byref(q), C.byref(m)))
+        return l.value or 0, p.value or 0, n.value, q.value or 0, m.value
+
+    def edit_parts(self, set: int = SET_SOLID, connectivity: int = CONN_FACE, ratio: int = 800) -> int:
+        """rto_edit_parts: segment afresh, flip every voxel of the set that has a neighbour of a larger part number, rebuild as
+        edit_voxels does; the number of voxels flipped."""
+        changed = C.c_int64()
+        self._check(self._L.rto_edit_parts(self._h, int(set), int(connectivity), int(ratio), C.byref(changed)))
+        return changed.value
+
+    def last_parts_ms(self):
+        """ms of the last segment_parts: (transform, ascent + flatten, ranking + basin table, edges, host merge + relabel); -1: not run."""
+        return self._last_ms("rto_last_parts_ms", 5)
+
+    def debug_parts(self):
+        """(basins, basin edges downloaded, flatten rounds, edge-table slots) of the last segment_parts."""
+        b, e, cap, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+        self._check(self._L.rto_debug_parts(self._h, C.byref(b), C.byref(e), C.byref(r), C.byref(cap)))
+        return b.value, e.value, r.value, cap.value
+
+    def debug_parts_capacity(self, first_capacity: int):
+        """The first capacity of the basin-edge table from now on (0: sized from the basin count); changes no value."""
+        self._check(self._L.rto_debug_parts_capacity(self._h, int(first_capacity)))
 
     # -- component measures -------------------------------------------------------
     def measure_components(self):

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NODE_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
@@ -194,6 +194,26 @@ def load():
     L.rtoh_rt_exposure.restype = C.c_int
     L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
     L.rtoh_rt_geodesic_field.restype = C.c_int
+    L.rtoh_parts_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int]
+    L.rtoh_parts_cpu.restype = _vp
+    L.rtoh_parts_counts.argtypes = [_vp, _vp]
+    L.rtoh_parts_counts.restype = None
+    L.rtoh_parts_copy.argtypes = [_vp, _vp, _vp, _vp, _vp]
+    L.rtoh_parts_copy.restype = None
+    L.rtoh_parts_free.argtypes = [_vp]
+    L.rtoh_parts_free.restype = None
+    L.rtoh_parts_split_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int]
+    L.rtoh_parts_split_cpu.restype = C.c_int64
+    L.rtoh_rt_segment_parts.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]
+    L.rtoh_rt_segment_parts.restype = C.c_int
+    L.rtoh_rt_parts.argtypes = [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rtoh_rt_parts.restype = C.c_int
+    L.rtoh_rt_necks.argtypes = [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rtoh_rt_necks.restype = C.c_int
+    L.rtoh_rt_part_labels.argtypes = [_vp, _vp, C.c_int64]
+    L.rtoh_rt_part_labels.restype = C.c_int
+    L.rtoh_rt_split_at_necks.argtypes = [_vp, C.c_int, C.c_int, C.c_int]
+    L.rtoh_rt_split_at_necks.restype = C.c_int64
     L.rtoh_thickness_cpu.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]
     L.rtoh_thickness_cpu.restype = C.c_int
     L.rtoh_rt_thickness_field.argtypes = [_vp, C.c_int, C.c_float, _vp, C.c_int64, _vp]
@@ -336,6 +356,30 @@ class VoxelGrid:
         """Addition: applyMorphologyCPU -- rto_edit_morphology's DILATE / ERODE / OPEN / CLOSE on this grid for rq quanta, on the
         CPU; the number of voxels changed (-1: refused, the grid untouched)."""
         return int(load().rtoh_morphology_cpu(self._h, int(op), int(rq)))
+
+    def segmentParts(self, set: int = 1, connectivity: int = 6, ratio: int = 800):
+        """Addition: segmentPartsCPU (host/Parts.h) -- the rule of rto_segment_parts as plain loops on the CPU: (labels int32 (dimZ,
+        dimY, dimX), parts as hip.PART_DTYPE, necks as hip.NECK_DTYPE, summary as a hip.PARTS_SUMMARY_DTYPE scalar)."""
+        dx, dy, dz = self.dims
+        L = load()
+        h = L.rtoh_parts_cpu(self._h, int(set), int(connectivity), int(ratio))      # the segmentation runs once; the rest are copies
+        if not h:
+            raise ValueError("segmentParts: unknown set, connectivity or ratio, or a grid the 32-bit field cannot serve")
+        try:
+            counts = (C.c_int64 * 2)()
+            L.rtoh_parts_counts(h, counts)
+            labels = np.empty((dz, dy, dx), np.int32)
+            parts, necks = np.zeros(counts[0], PART_DTYPE), np.zeros(counts[1], NECK_DTYPE)
+            summary = np.zeros((), PARTS_SUMMARY_DTYPE)
+            L.rtoh_parts_copy(h, labels.ctypes.data, parts.ctypes.data, necks.ctypes.data, summary.ctypes.data)
+        finally:
+            L.rtoh_parts_free(h)
+        return labels, parts, necks, summary
+
+    def splitAtNecks(self, set: int = 1, connectivity: int = 6, ratio: int = 800) -> int:
+        """Addition: splitAtNecksCPU -- rto_edit_parts' cut on this grid, on the CPU; the number of voxels flipped (-1: refused,
+        the grid untouched)."""
+        return int(load().rtoh_parts_split_cpu(self._h, int(set), int(connectivity), int(ratio)))
 
     def thicknessField(self, medium: int = 1, mq: int = 64):
         """Addition: thicknessFieldCPU (host/Thickness.h) -- the rule of rto_thickness_field on the CPU for a radius of mq quanta:
@@ -813,6 +857,47 @@ class RayTracerBVH:
         if rc != 0 or not out[0]:
             return rc, None
         return rc, ((int(out[1]), int(out[2]), int(out[3])), int(out[4]), float(dist.value))
+
+    def segmentParts(self, set: int = 1, connectivity: int = 6, ratio: int = 800):
+        """Addition: RayTracerBVH::segmentParts -- (code, labels int32 (dimZ, dimY, dimX), summary as a hip.PARTS_SUMMARY_DTYPE
+        scalar); code is RTO_OK or the refusal's (lastError), and labels is then None."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        labels = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        summary = np.zeros((), PARTS_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_segment_parts(self._h, int(set), int(connectivity), int(ratio), labels.ctypes.data, labels.size, summary.ctypes.data))
+        return rc, (labels if rc == 0 else None), summary
+
+    def _partsTable(self, entry, dtype):
+        n = C.c_int64()
+        rc = int(entry(self._h, None, 0, C.byref(n)))
+        if rc != 0:
+            return rc, None
+        table = np.zeros(n.value, dtype)
+        if n.value:
+            rc = int(entry(self._h, table.ctypes.data, n.value, C.byref(n)))
+        return rc, (table if rc == 0 else None)
+
+    def parts(self):
+        """Addition: RayTracerBVH::parts -- (code, the last segmentParts' part table as hip.PART_DTYPE, or None)."""
+        return self._partsTable(load().rtoh_rt_parts, PART_DTYPE)
+
+    def necks(self):
+        """Addition: RayTracerBVH::necks -- (code, the last segmentParts' neck table as hip.NECK_DTYPE, or None)."""
+        return self._partsTable(load().rtoh_rt_necks, NECK_DTYPE)
+
+    def partLabels(self):
+        """Addition: RayTracerBVH::partLabels -- (code, the resident part labels int32 (dimZ, dimY, dimX), or None)."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        out = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        rc = int(load().rtoh_rt_part_labels(self._h, out.ctypes.data, out.size))
+        return rc, (out if rc == 0 else None)
+
+    def splitAtNecks(self, set: int = 1, connectivity: int = 6, ratio: int = 800) -> int:
+        """Addition: RayTracerBVH::splitAtNecks -- segments afresh and cuts the grid at the necks; voxels flipped, or the refusal's
+        code (negative)."""
+        return int(load().rtoh_rt_split_at_necks(self._h, int(set), int(connectivity), int(ratio)))
 
     def thicknessField(self, medium: int = 1, maxRadius: float = 0.0):
         """Addition: RayTracerBVH::thicknessField -- (code, t2 int32 (dimZ, dimY, dimX), summary as a hip.THICK_SUMMARY_DTYPE

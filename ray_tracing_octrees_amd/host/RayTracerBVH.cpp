@@ -76,6 +76,11 @@ struct HipApi {
     decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
     decltype(&rto_measure_components) measure_components = nullptr;
     decltype(&rto_download_measures) download_measures = nullptr;
+    decltype(&rto_segment_parts) segment_parts = nullptr;
+    decltype(&rto_download_part_labels) download_part_labels = nullptr;
+    decltype(&rto_download_parts) download_parts = nullptr;
+    decltype(&rto_download_necks) download_necks = nullptr;
+    decltype(&rto_edit_parts) edit_parts = nullptr;
     std::string error;
 
     bool load() {
@@ -162,6 +167,11 @@ struct HipApi {
         thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
         measure_components = reinterpret_cast<decltype(measure_components)>(sym("rto_measure_components"));
         download_measures = reinterpret_cast<decltype(download_measures)>(sym("rto_download_measures"));
+        segment_parts = reinterpret_cast<decltype(segment_parts)>(sym("rto_segment_parts"));
+        download_part_labels = reinterpret_cast<decltype(download_part_labels)>(sym("rto_download_part_labels"));
+        download_parts = reinterpret_cast<decltype(download_parts)>(sym("rto_download_parts"));
+        download_necks = reinterpret_cast<decltype(download_necks)>(sym("rto_download_necks"));
+        edit_parts = reinterpret_cast<decltype(edit_parts)>(sym("rto_edit_parts"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -1072,6 +1082,71 @@ int RayTracerBVH::exposure(std::vector<int32_t>& e) {
     const int rc = api().download_exposure(m_ctx, e.data(), (int64_t)e.size());
     if (rc != RTO_OK) { e.clear(); return regionFailed(rc, "exposure"); }
     return RTO_OK;
+}
+
+// The part segmentation of the first GPU's resident grid (rto_segment_parts); the code is RTO_OK or the refusal's.
+int RayTracerBVH::segmentParts(int set, int connectivity, int ratio, std::vector<int32_t>* labels, rto_parts_summary* summary) {
+    return fieldInto("segmentParts", "part segmentation", labels, [&] { return api().segment_parts(m_ctx, set, connectivity, ratio, summary); },
+                     api().download_part_labels);
+}
+
+// A resident table of the last segmentParts, downloaded: the count first, then the records.
+template <class Record>
+static int downloadPartsTable(rto_context* ctx, int (*download)(rto_context*, Record*, int64_t, int64_t*), std::vector<Record>& table) {
+    int64_t count = 0;
+    int rc = download(ctx, nullptr, 0, &count);
+    if (rc == RTO_OK && count > 0) {
+        table.resize((size_t)count);
+        rc = download(ctx, table.data(), count, &count);
+    }
+    if (rc != RTO_OK) table.clear();
+    return rc;
+}
+
+int RayTracerBVH::parts(std::vector<rto_part>& table) {
+    table.clear();
+    if (!computeUsable("parts")) return RTO_E_INVALID;
+    const int rc = downloadPartsTable(m_ctx, api().download_parts, table);
+    return rc == RTO_OK ? RTO_OK : regionFailed(rc, "parts");
+}
+
+int RayTracerBVH::necks(std::vector<rto_neck>& table) {
+    table.clear();
+    if (!computeUsable("necks")) return RTO_E_INVALID;
+    const int rc = downloadPartsTable(m_ctx, api().download_necks, table);
+    return rc == RTO_OK ? RTO_OK : regionFailed(rc, "necks");
+}
+
+int RayTracerBVH::partLabels(std::vector<int32_t>& labels) {
+    labels.clear();
+    if (!computeUsable("partLabels")) return RTO_E_INVALID;
+    labels.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+    const int rc = api().download_part_labels(m_ctx, labels.data(), (int64_t)labels.size());
+    if (rc != RTO_OK) { labels.clear(); return regionFailed(rc, "partLabels"); }
+    return RTO_OK;
+}
+
+// rto_edit_parts on every GPU: the number of voxels flipped, or the refusal's code (negative).
+int64_t RayTracerBVH::splitAtNecks(int set, int connectivity, int ratio) {
+    m_lastEditChanged = -1;
+    if (!computeUsable("splitAtNecks")) return RTO_E_INVALID;
+    if (m_numNodes > 0 && !makeGridResident("splitAtNecks")) return RTO_E_HIP;
+    int64_t changed = 0;
+    for (rto_context* c : m_ctxs) {
+        const int rc = api().edit_parts(c, set, connectivity, ratio, c == m_ctx ? &changed : nullptr);
+        if (rc != RTO_OK) {
+            m_lastError = api().last_error(c);
+            std::cerr << "[RayTracerBVH] splitAtNecks failed: " << m_lastError << std::endl;
+            return rc;
+        }
+    }
+    m_lastEditChanged = changed;
+    if (changed > 0) {
+        rto_octree_info info;
+        if (api().octree_info(m_ctx, &info) == RTO_OK) m_numNodes = static_cast<int>(info.num_nodes);
+        m_gridStale = true;
+    }
+    return changed;
 }
 
 // The local thickness field of the first GPU's resident grid (rto_thickness_field); the code is RTO_OK or the refusal's.

@@ -276,6 +276,19 @@ public:
     int exposureField(const std::vector<int32_t>& dirs, const std::vector<int32_t>& weights, int mode = RTO_EXPO_SKIN, int reach = RTO_EXPO_NO_LIMIT,
                       rto_expo_summary* summary = nullptr);
     int exposure(std::vector<int32_t>& e);
+    // Part segmentation of the resident grid (rto_segment_parts / rto_edit_parts).  segmentParts runs the
+    // watershed of the squared distance field of `set` on the first GPU under `connectivity` and merges basins with `ratio` in
+    // [0, RTO_PARTS_RATIO_MAX] (0: the components, 1001: the basins): one int32 per voxel, x fastest, the part's number, -1 outside
+    // the set; labels and summary may be null.  parts / necks / partLabels download what the last segmentParts left resident.
+    // splitAtNecks segments afresh on every GPU, clears (or fills, for RTO_SET_EMPTY) the voxels of the set that touch a part of a
+    // larger number, and rebuilds as editVoxels does: the number of voxels flipped (lastEditChanged() too).  Each returns RTO_OK
+    // (splitAtNecks: the count) or the refusal's code, which is negative (lastError).  They need the compute pipeline; the CPU form
+    // of the same rule for a VoxelGrid is host/Parts.h.
+    int segmentParts(int set, int connectivity, int ratio, std::vector<int32_t>* labels, rto_parts_summary* summary = nullptr);
+    int parts(std::vector<rto_part>& table);
+    int necks(std::vector<rto_neck>& table);
+    int partLabels(std::vector<int32_t>& labels);
+    int64_t splitAtNecks(int set = RTO_SET_SOLID, int connectivity = RTO_CONN_FACE, int ratio = 800);
     // Component measures of the resident grid (rto_measure_components).  measureComponents labels `set` under
     // `connectivity` on the first GPU and measures every component: one rto_measure per component in the table's order (exposed
     // faces by direction, cell counts, Euler number, first and second moments of the voxel indices) and their sum; table and total

@@ -16,6 +16,7 @@
 #include "Skeleton.h"
 #include "Exposure.h"
 #include "Thickness.h"
+#include "Parts.h"
 #include "Measure.h"
 #include "Camera.h"
 #include "Frustum.h"
@@ -418,6 +419,64 @@ int rtoh_rt_thickness_histogram(RayTracerBVH* rt, int64_t* bins, int64_t capacit
     if (count) *count = (int64_t)b.size();
     return RTO_OK;
 }
+// Part segmentation.  rtoh_parts_cpu runs the CPU form of the rule (Parts.h) on a grid ONCE and keeps the answer: the handle (NULL
+// for a refusal) gives the counts (rtoh_parts_counts: parts, necks) and then the copies (rtoh_parts_copy: labels of dims product
+// int32, parts and necks of the counted sizes, the summary; any may be NULL); rtoh_parts_free ends it.  rtoh_parts_split_cpu edits
+// the grid in place (the number flipped, -1: refused).
+struct RtohParts {
+    std::vector<int32_t> labels;
+    std::vector<rto_part> parts;
+    std::vector<rto_neck> necks;
+    rto_parts_summary summary;
+};
+RtohParts* rtoh_parts_cpu(const VoxelGrid* g, int set, int connectivity, int ratio) {
+    RtohParts* r = new RtohParts();
+    if (segmentPartsCPU(*g, set, connectivity, ratio, r->labels, r->parts, r->necks, &r->summary) < 0) { delete r; return nullptr; }
+    return r;
+}
+void rtoh_parts_counts(const RtohParts* r, int64_t counts[2]) { counts[0] = (int64_t)r->parts.size(); counts[1] = (int64_t)r->necks.size(); }
+void rtoh_parts_copy(const RtohParts* r, int32_t* labels, rto_part* parts, rto_neck* necks, rto_parts_summary* summary) {
+    if (labels) std::copy(r->labels.begin(), r->labels.end(), labels);
+    if (parts) std::copy(r->parts.begin(), r->parts.end(), parts);
+    if (necks) std::copy(r->necks.begin(), r->necks.end(), necks);
+    if (summary) *summary = r->summary;
+}
+void rtoh_parts_free(RtohParts* r) { delete r; }
+int64_t rtoh_parts_split_cpu(VoxelGrid* g, int set, int connectivity, int ratio) { return splitAtNecksCPU(*g, set, connectivity, ratio); }
+// RayTracerBVH::segmentParts / parts / necks / partLabels / splitAtNecks: the class's codes; the tables are filled up to capacity and
+// *count = the records there are.
+int rtoh_rt_segment_parts(RayTracerBVH* rt, int set, int connectivity, int ratio, int32_t* labels, int64_t capacity, rto_parts_summary* summary) {
+    std::vector<int32_t> l;
+    const int rc = rt->segmentParts(set, connectivity, ratio, labels ? &l : nullptr, summary);
+    if (rc != RTO_OK) return rc;
+    if (labels) std::copy(l.begin(), l.begin() + (size_t)std::min<int64_t>((int64_t)l.size(), capacity), labels);
+    return RTO_OK;
+}
+int rtoh_rt_parts(RayTracerBVH* rt, rto_part* out, int64_t capacity, int64_t* count) {
+    std::vector<rto_part> t;
+    const int rc = rt->parts(t);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), out);
+    if (count) *count = (int64_t)t.size();
+    return RTO_OK;
+}
+int rtoh_rt_necks(RayTracerBVH* rt, rto_neck* out, int64_t capacity, int64_t* count) {
+    std::vector<rto_neck> t;
+    const int rc = rt->necks(t);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), out);
+    if (count) *count = (int64_t)t.size();
+    return RTO_OK;
+}
+int rtoh_rt_part_labels(RayTracerBVH* rt, int32_t* out, int64_t capacity) {
+    std::vector<int32_t> l;
+    const int rc = rt->partLabels(l);
+    if (rc != RTO_OK) return rc;
+    if ((int64_t)l.size() > capacity) return RTO_E_INVALID;
+    std::copy(l.begin(), l.end(), out);
+    return RTO_OK;
+}
+int64_t rtoh_rt_split_at_necks(RayTracerBVH* rt, int set, int connectivity, int ratio) { return rt->splitAtNecks(set, connectivity, ratio); }
 // Component measures.  rtoh_measure_cpu: the CPU form of the rule (Measure.h) on a label volume of dims[3]: out (capacity records)
 // and total may be NULL; the code of rto_measure_components.
 int rtoh_measure_cpu(const int* dims, const int32_t* labels, int64_t count, int connectivity, rto_measure* out, int64_t capacity,
