@@ -1328,6 +1328,108 @@ int  rto_debug_parts(const rto_context* ctx, int64_t* basins, int64_t* edges, in
  * fills up is discarded and made again with twice the slots, at most 8 times: no value depends on the capacity. */
 int  rto_debug_parts_capacity(rto_context* ctx, int64_t first_capacity);
 
+/* ---- field views ------------------------------------------------------------
+ * A frame of the octree, from the renders' camera, coloured by an int32 volume of the resident grid: a resident field, the
+ * component labels or a caller's own volume; and per pixel the value under it.  The reference shows per-voxel
+ * data with its second renderer (VolumeRaycastRenderer, a GL path); this is the exact-integer form of that need.  All float
+ * arithmetic is float32, one IEEE operation per operator, in the order written.  Rule:
+ *   ray       the frame's pixel ray (generate_ray_tab: rto_render_device's).  Like the queries, the view ignores rto_update_frustum.
+ *   window    without a clip box (0, largest float below 1e30).  With one (clip != 0): the planes of axis a are
+ *             gridMin[a] + (float)i * voxelSize for i = clip_lo[a] and clip_hi[a]; t1 = (lo plane - o) * (1 / d), t2 = (hi plane - o) *
+ *             (1 / d) per axis, tNear = max(max(min(t1x, t2x), min(t1y, t2y)), min(t1z, t2z)), tFar likewise with min and max
+ *             exchanged (glm's min and max, the queries' slab formula); a ray that fails tNear <= tFar && tFar > 0 is a miss;
+ *             t_lo = max(0, tNear), t_hi = min(below 1e30, tFar).
+ *   hit       the box query of `mode` (RTO_QUERY_FIRST or RTO_QUERY_CLOSEST) in [t_lo, t_hi]: leaf, tHit and face exactly as
+ *             rto_query_* define them.  FIRST without a clip box hits the pixels rto_render_device and rto_render_lit_* hit.
+ *   voxel     p = o + d * tHit per component.  On every axis c: q = floor((p[c] - gridMin[c]) / voxelSize), clamped (as a float; a
+ *             NaN goes to the lower end) into the leaf's [lo, lo + size - 1], converted to int and, with a clip box, clamped into
+ *             [clip_lo[c], clip_hi[c] - 1].  Then, when face >= 0, the face's axis a = face >> 1 drops its q and takes the leaf's
+ *             own boundary voxel: lo + size - 1 for an odd face, lo for an even one.  Leaves of one voxel are therefore exact
+ *             whatever the floats do; larger leaves, and leaves the clip box cuts, follow the float statement.
+ *   sample    RTO_SAMPLE_HIT: that voxel.  RTO_SAMPLE_FRONT: that voxel moved by one along the entry face's outward normal (+1 on
+ *             axis a for an odd face, -1 for an even one): the EMPTY voxel in front of the surface, where exposure SKIN fields and
+ *             distance-to-SOLID fields live.  FRONT has no voxel when face == -1, and none when the neighbour lies outside the
+ *             grid's dims.
+ *   value     what d_values holds: RTO_FIELD_PIXEL_MISS for a miss; RTO_FIELD_PIXEL_NONE when there is no voxel or the volume's
+ *             value there lies outside [valid_lo, valid_hi]; otherwise that value.  The defaults valid_lo = 0 and valid_hi =
+ *             0x7ffffffe leave out -1 ("outside the set") and RTO_DIST_NONE.
+ *   summary   hits (pixels that are no miss), valued, vmin and vmax over the valued pixels (0 and 0 when there are none), and the
+ *             range (lo, hi) the colours used: (range_lo, range_hi), or (vmin, vmax) when range_lo == range_hi (auto range).  It is
+ *             made on the device and the colour pass reads it there: no frame has a host step or a synchronisation.
+ *   index     of a valued pixel of value v, in int64: w = clamp(v, lo, hi) - lo, s = hi - lo.  CATEGORY: mix32((uint32)v) & 255
+ *             with the lit render's mix32, whatever the range.  Otherwise s == 0 gives 0; LINEAR floor(w * 255 / s); SQRT the
+ *             largest k in 0..255 with k * k * s <= w * 65025 (squared distances and thicknesses then read linearly).
+ *   bins      bins[k] = valued pixels of index k: the legend.  Their sum is `valued`.
+ *   colour    a LUT entry is the bytes r, g, b, a in memory order; each channel is (float)byte / 255.0f.  With shade != 0 r, g
+ *             and b are each multiplied by (0.25f + 0.75f * ndotl), ndotl = shade_term's Lambert term of the hit leaf against
+ *             the renders' light (computed from the leaf's own box: its tHit is max(0, tNear) of that box, also when a clip box
+ *             cut the leaf); alpha is untouched.  Miss pixels are miss_rgba, pixels without a value none_rgba, both unshaded.
+ * The volume is int32, dimZ x dimY x dimX, x fastest.  RTO_FIELD_DISTANCE .. RTO_FIELD_PARTS are the resident fields
+ * (rto_distance_field .. rto_segment_parts), RTO_FIELD_LABELS the component labels, RTO_FIELD_CALLER the caller's
+ * volume (for the other sources it must be NULL).  Needs a canonical tree and a resident grid: what rto_build_octree,
+ * rto_voxelize_mesh and the edits leave.  A tree that is one leaf is rendered (its box is the walk).  rto_set_kernel does not apply.
+ * A whole-grid clip box gives the frame without one when the grid's planes are computed without rounding (both forms of a plane
+ * are then the same float).
+ * Errors, each leaving the context untouched, checked in this order: RTO_E_INVALID: a NULL frame, view, LUT or rgba; a misaligned
+ * buffer (d_rgba 16 bytes, d_summary and d_bins 8, d_lut, d_volume and d_values 4); an unknown source, sample, mode (ANY is
+ * invalid) or scale; reserved != 0; valid_lo > valid_hi or valid_lo <= INT32_MIN + 1; range_lo > range_hi; a width or height
+ * below 1; a frame beyond the lit render's limits (width * height + 128 and 64 * (8x8 tiles) + 256 below 2^32); CALLER without a
+ * volume, or a volume with another source.  RTO_E_NO_OCTREE: nothing uploaded.  RTO_E_UNSUPPORTED: no resident grid
+ * (rto_upload_octree), then a non-canonical array.  RTO_E_INVALID: a clip box with clip_lo[a] < 0, clip_hi[a] > dim[a] or
+ * clip_lo[a] >= clip_hi[a]; last, a named source that is not resident, in its readers' words ("... not made yet, or the grid has
+ * changed since").
+ * The device form is asynchronous on hip_stream.  Its work buffers (the summary block, and a value buffer when d_values is NULL)
+ * live on the context under the lit render's rules: a frame larger than any before allocates, and then must not be stream-
+ * captured; one set per context, so field views on different streams of one context must not run at the same time.  With
+ * shade != 0 the first pass parks ndotl in the red channel of d_rgba before the second pass overwrites the pixel. */
+#define RTO_FIELD_DISTANCE  0
+#define RTO_FIELD_GEODESIC  1
+#define RTO_FIELD_THICKNESS 2
+#define RTO_FIELD_SKELETON  3
+#define RTO_FIELD_EXPOSURE  4
+#define RTO_FIELD_PARTS     5
+#define RTO_FIELD_LABELS    6
+#define RTO_FIELD_CALLER    7
+#define RTO_SAMPLE_HIT      0
+#define RTO_SAMPLE_FRONT    1
+#define RTO_SCALE_LINEAR    0
+#define RTO_SCALE_SQRT      1
+#define RTO_SCALE_CATEGORY  2
+#define RTO_FIELD_PIXEL_MISS (-2147483647 - 1)   /* INT32_MIN */
+#define RTO_FIELD_PIXEL_NONE (-2147483647)       /* INT32_MIN + 1 */
+typedef struct rto_field_view {     /* 112 bytes */
+    int32_t  source;                /* RTO_FIELD_* */
+    int32_t  sample;                /* RTO_SAMPLE_* */
+    int32_t  mode;                  /* RTO_QUERY_FIRST or RTO_QUERY_CLOSEST */
+    int32_t  scale;                 /* RTO_SCALE_* */
+    int32_t  valid_lo, valid_hi;    /* values outside are "no value"; defaults 0 and 0x7ffffffe; valid_lo > INT32_MIN + 1 */
+    int32_t  range_lo, range_hi;    /* equal: auto range */
+    int32_t  clip;                  /* != 0: the section box below applies */
+    int32_t  clip_lo[3], clip_hi[3];   /* voxel indices, x y z: 0 <= clip_lo < clip_hi <= dim */
+    int32_t  shade;                 /* != 0: colours are multiplied by 0.25 + 0.75 ndotl */
+    float    miss_rgba[4];
+    float    none_rgba[4];
+    int32_t  reserved[4];           /* 0 */
+} rto_field_view;
+typedef struct rto_field_view_summary {   /* 32 bytes */
+    int64_t  hits;                  /* pixels that are no miss */
+    int64_t  valued;                /* pixels that hold a value */
+    int32_t  vmin, vmax;            /* over the valued pixels; 0, 0 when there are none */
+    int32_t  lo, hi;                /* the range the colours used */
+} rto_field_view_summary;
+
+int  rto_render_field_device(rto_context* ctx, const rto_frame* frame, const rto_field_view* view, const uint32_t* d_lut /* 256 */,
+                             const int32_t* d_volume /* RTO_FIELD_CALLER only */, void* d_rgba /* float4 per pixel, 16-byte aligned */,
+                             int32_t* d_values /* may be NULL */, rto_field_view_summary* d_summary /* may be NULL */,
+                             int64_t* d_bins /* 256, may be NULL */, void* hip_stream);
+/* The same with host buffers (the LUT and a caller's volume too); synchronous on the context's stream. */
+int  rto_render_field_host(rto_context* ctx, const rto_frame* frame, const rto_field_view* view, const uint32_t* lut /* 256 */,
+                           const int32_t* volume /* RTO_FIELD_CALLER only */, float* host_rgba, int32_t* host_values /* may be NULL */,
+                           rto_field_view_summary* host_summary /* may be NULL */, int64_t* host_bins /* 256, may be NULL */);
+/* Device time of the last field view's two kernels in ms (sample, shade); waits for that frame.  -1: not run, or the frame was
+ * stream-captured or launched after rto_timing_begin(ctx, -1). */
+int  rto_last_field_view_ms(const rto_context* ctx, float ms[2]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -165,6 +165,14 @@ struct rto_context {
     unsigned* d_litCount = nullptr;
     size_t litCap = 0;
 
+    // field views (rto_field_view.inc): the summary block of the frame in flight, the value buffer of callers that pass no d_values
+    // (frames of up to fvCap pixels) and the events around the two kernels of the last frame (fvTimed: they were recorded)
+    void* d_fvSum = nullptr;
+    int* d_fvValues = nullptr;
+    size_t fvCap = 0;
+    hipEvent_t fvEv[3] = { nullptr, nullptr, nullptr };
+    bool fvTimed = false;
+
     // mesh extraction (rto_mesh.inc): the last mesh (a snapshot the context owns) and the first node of every tree level
     float4* d_mesh = nullptr;
     int* d_meshNode = nullptr;
@@ -404,6 +412,9 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_litRec);
     (void)hipFree(c->d_litAcc);
     (void)hipFree(c->d_litCount);
+    (void)hipFree(c->d_fvSum);
+    (void)hipFree(c->d_fvValues);
+    for (hipEvent_t e : c->fvEv) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_mesh);
     (void)hipFree(c->d_meshNode);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
@@ -3024,6 +3035,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_edit.inc"
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"
+#include "rto_field_view.inc"
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
 #include "rto_region.inc"

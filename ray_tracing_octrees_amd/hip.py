@@ -60,6 +60,7 @@ SYMBOLS = (
     "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
     "rto_segment_parts", "rto_download_part_labels", "rto_download_parts", "rto_download_necks", "rto_parts_device", "rto_edit_parts",
     "rto_last_parts_ms", "rto_debug_parts", "rto_debug_parts_capacity",
+    "rto_render_field_device", "rto_render_field_host", "rto_last_field_view_ms",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -124,6 +125,12 @@ PART_DTYPE = np.dtype([("root", "<i8"), ("voxels", "<i8"), ("lo", "<i4", (3,)), 
 NECK_DTYPE = np.dtype([("part_lo", "<i4"), ("part_hi", "<i4"), ("h", "<i4"), ("reserved", "<i4"), ("at", "<i8"), ("pairs", "<i8")])
 PARTS_SUMMARY_DTYPE = np.dtype([("parts", "<i8"), ("basins", "<i8"), ("necks", "<i8"), ("pairs", "<i8")])
 PARTS_RATIO_MAX = 1001   # RTO_PARTS_RATIO_MAX: joins nothing, the parts are the basins
+# field views (rto_render_field_*): RTO_FIELD_*, RTO_SAMPLE_*, RTO_SCALE_* and the two pixel codes of the value buffer
+FIELD_DISTANCE, FIELD_GEODESIC, FIELD_THICKNESS, FIELD_SKELETON, FIELD_EXPOSURE, FIELD_PARTS, FIELD_LABELS, FIELD_CALLER = 0, 1, 2, 3, 4, 5, 6, 7
+SAMPLE_HIT, SAMPLE_FRONT = 0, 1
+SCALE_LINEAR, SCALE_SQRT, SCALE_CATEGORY = 0, 1, 2
+FIELD_PIXEL_MISS, FIELD_PIXEL_NONE = -2**31, -2**31 + 1
+FIELD_VIEW_SUMMARY_DTYPE = np.dtype([("hits", "<i8"), ("valued", "<i8"), ("vmin", "<i4"), ("vmax", "<i4"), ("lo", "<i4"), ("hi", "<i4")])
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -236,6 +243,52 @@ def ao_directions() -> np.ndarray:
     if rc != RTO_OK:
         raise RtoError(rc, "rto_ao_directions failed")
     return out
+
+
+# struct rto_field_view (112 bytes) and rto_field_view_summary (32): field views (rto_render_field_*)
+class FieldView(C.Structure):
+    _fields_ = [("source", C.c_int32), ("sample", C.c_int32), ("mode", C.c_int32), ("scale", C.c_int32),
+                ("valid_lo", C.c_int32), ("valid_hi", C.c_int32), ("range_lo", C.c_int32), ("range_hi", C.c_int32),
+                ("clip", C.c_int32), ("clip_lo", C.c_int32 * 3), ("clip_hi", C.c_int32 * 3), ("shade", C.c_int32),
+                ("miss_rgba", C.c_float * 4), ("none_rgba", C.c_float * 4), ("reserved", C.c_int32 * 4)]
+
+
+class FieldViewSummary(C.Structure):
+    _fields_ = [("hits", C.c_int64), ("valued", C.c_int64), ("vmin", C.c_int32), ("vmax", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32)]
+
+
+def make_field_view(source, sample=SAMPLE_HIT, mode=QUERY_FIRST, scale=SCALE_LINEAR, valid=(0, 0x7ffffffe), range=(0, 0), clip=None,
+                    shade=False, miss_rgba=(0.0, 0.0, 0.0, 1.0), none_rgba=(0.25, 0.25, 0.25, 1.0)) -> FieldView:
+    """An rto_field_view with the header's defaults.  range: (lo, hi), equal for auto range; clip: None or ((x0, y0, z0),
+    (x1, y1, z1)) in voxel indices."""
+    v = FieldView()
+    v.source, v.sample, v.mode, v.scale = int(source), int(sample), int(mode), int(scale)
+    v.valid_lo, v.valid_hi = int(valid[0]), int(valid[1])
+    v.range_lo, v.range_hi = int(range[0]), int(range[1])
+    v.clip = 0 if clip is None else 1
+    for a in (0, 1, 2):
+        v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
+        v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
+    v.shade = 1 if shade else 0
+    for k in (0, 1, 2, 3):
+        v.miss_rgba[k] = _f(miss_rgba[k])
+        v.none_rgba[k] = _f(none_rgba[k])
+    return v
+
+
+def ramp_lut(anchors) -> np.ndarray:
+    """256 LUT entries (uint32, bytes r, g, b, a in memory order) interpolated between n >= 1 RGBA anchor colours (bytes), in
+    integers: with p = i * (n - 1), j = p // 255 and f = p % 255, entry i is anchors[j] for f == 0, else per channel
+    (a[j] * (255 - f) + a[j + 1] * f + 127) // 255.  Entry 0 is the first anchor, entry 255 the last."""
+    a = np.asarray(anchors, np.int64).reshape(-1, 4)
+    if len(a) < 1 or a.min() < 0 or a.max() > 255:
+        raise ValueError("ramp_lut: anchors are RGBA bytes")
+    n = len(a)
+    p = np.arange(256, dtype=np.int64) * (n - 1)
+    j, f = p // 255, (p % 255)[:, None]
+    nxt = a[np.minimum(j + 1, n - 1)]
+    rgba = (a[j] * (255 - f) + nxt * f + 127) // 255
+    return np.ascontiguousarray(rgba.astype(np.uint8)).view("<u4").reshape(256)
 
 
 class Hit(C.Structure):
@@ -547,6 +600,9 @@ def load():
     L.rto_last_parts_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_parts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
     L.rto_debug_parts_capacity.argtypes = [vp, C.c_int64]
+    L.rto_render_field_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldView), vp, vp, vp, vp, vp, vp, vp]
+    L.rto_render_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldView), vp, vp, vp, vp, vp, vp]
+    L.rto_last_field_view_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -933,6 +989,40 @@ class Context:
     @staticmethod
     def ao_directions() -> np.ndarray:
         return ao_directions()
+
+    # -- field views ---------------------------------------------------------
+    def render_field_host(self, frame: Frame, view: FieldView, lut, volume=None):
+        """A frame coloured by an int32 volume of the resident grid (rto_render_field_host).  lut: 256 uint32 (ramp_lut);
+        volume: the (dimZ, dimY, dimX) int32 array of FIELD_CALLER, None for every other source.  Returns (rgba (H, W, 4)
+        float32, values (H, W) int32, summary (one FIELD_VIEW_SUMMARY_DTYPE record), bins (256,) int64)."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("render_field_host: the LUT has 256 entries")
+        if volume is not None:
+            volume = np.ascontiguousarray(volume, dtype=np.int32)
+            dims = (C.c_int * 3)()
+            if self._L.rto_download_voxels(self._h, None, 0, dims) == RTO_OK and volume.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"render_field_host: the volume must be {(dims[2], dims[1], dims[0])}, not {volume.shape}")
+        rgba = np.empty((frame.height, frame.width, 4), np.float32)
+        values = np.empty((frame.height, frame.width), np.int32)
+        summary = np.zeros(1, FIELD_VIEW_SUMMARY_DTYPE)
+        bins = np.zeros(256, np.int64)
+        self._check(self._L.rto_render_field_host(self._h, C.byref(frame), C.byref(view), lut.ctypes.data,
+                                                  volume.ctypes.data if volume is not None else None, rgba.ctypes.data,
+                                                  values.ctypes.data, summary.ctypes.data, bins.ctypes.data))
+        return rgba, values, summary[0], bins
+
+    def render_field_device(self, frame: Frame, view: FieldView, d_lut: int, d_rgba: int, d_volume: int = 0, d_values: int = 0,
+                            d_summary: int = 0, d_bins: int = 0, stream: int = 0):
+        """Asynchronous: the field view into d_rgba (W*H*16 bytes) and, where given, the values (W*H int32), the summary (32 bytes)
+        and the 256 int64 bins; d_lut: 256 uint32 on the device; d_volume: the device volume of FIELD_CALLER."""
+        p = lambda x: C.c_void_p(x) if x else None
+        self._check(self._L.rto_render_field_device(self._h, C.byref(frame), C.byref(view), p(d_lut), p(d_volume), p(d_rgba),
+                                                    p(d_values), p(d_summary), p(d_bins), p(stream)))
+
+    def last_field_view_ms(self):
+        """(sample kernel, shade kernel) of the last field view in ms; -1: not run."""
+        return self._last_ms("rto_last_field_view_ms", 2)
 
     # -- triangle queries (the resident leaf triangles) --------------------
     def query_triangles(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:

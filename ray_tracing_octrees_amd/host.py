@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, FIELD_VIEW_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
 
 _lib = None
@@ -124,6 +124,10 @@ def load():
     L.rtoh_rt_render_scene_lit.restype = None
     L.rtoh_rt_render_surface_lit.argtypes = L.rtoh_rt_render_scene_lit.argtypes
     L.rtoh_rt_render_surface_lit.restype = None
+    L.rtoh_rt_render_field.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp]
+    L.rtoh_rt_render_field.restype = C.c_int
+    L.rtoh_rt_field_values.argtypes = [_vp, _vp, C.c_int64, _vp]
+    L.rtoh_rt_field_values.restype = C.c_int64
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
     L.rtoh_rt_intersect_spans.argtypes = [_vp, _vp, C.c_int64, C.c_float, C.c_float, _vp]
@@ -714,6 +718,41 @@ class RayTracerBVH:
         ld = (C.c_float * 3)(*[_f(x) for x in lightDir])
         load().rtoh_rt_render_surface_lit(self._h, camera._h, width, height, _f(aspect), _f(fovDeg), ld, 1 if shadow else 0,
                                           int(aoSamples), _f(aoRadius), int(seed) & 0xFFFFFFFF)
+
+    def renderField(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, view, lut, volume=None) -> int:
+        """Addition: RayTracerBVH::renderField -- a frame coloured by a per-voxel int32 volume of the resident grid (DESIGN.md
+        section 27).  view: a hip.FieldView; lut: 256 uint32 (hip.ramp_lut); volume: the (dimZ, dimY, dimX) int32 array of
+        hip.FIELD_CALLER.  RTO_OK or the refusal's code (lastError); read the frame with framebuffer(), the values with
+        fieldValues(), the counts and range with fieldSummary()."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("renderField: the LUT has 256 entries")
+        vol = None if volume is None else np.ascontiguousarray(volume, dtype=np.int32)
+        if vol is not None:
+            dims = (C.c_int * 3)()
+            load().rtoh_rt_grid(self._h, dims, None)
+            if vol.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"renderField: the volume must be {(dims[2], dims[1], dims[0])}, not {vol.shape}")
+        return int(load().rtoh_rt_render_field(self._h, camera._h, int(width), int(height), _f(aspect), _f(fovDeg), C.addressof(view),
+                                               lut.ctypes.data, vol.ctypes.data if vol is not None else None))
+
+    def fieldValues(self) -> np.ndarray | None:
+        """Addition: RayTracerBVH::fieldValues -- the last renderField's value under every pixel, (H, W) int32
+        (hip.FIELD_PIXEL_MISS / FIELD_PIXEL_NONE where there is none); None when no field view has been rendered."""
+        w, h = C.c_int(), C.c_int()
+        n = int(load().rtoh_rt_field_values(self._h, None, 0, None))
+        if n == 0 or not load().rtoh_rt_framebuffer(self._h, None, 0, C.byref(w), C.byref(h)) or w.value * h.value != n:
+            return None
+        out = np.empty((h.value, w.value), np.int32)
+        load().rtoh_rt_field_values(self._h, out.ctypes.data, out.size, None)
+        return out
+
+    def fieldSummary(self):
+        """Addition: RayTracerBVH::fieldSummary -- the last renderField's hits, valued, vmin, vmax and the range used, as a
+        hip.FIELD_VIEW_SUMMARY_DTYPE record."""
+        s = np.zeros(1, FIELD_VIEW_SUMMARY_DTYPE)
+        load().rtoh_rt_field_values(self._h, None, 0, s.ctypes.data)
+        return s[0]
 
     def framebuffer(self) -> np.ndarray | None:
         w, h = C.c_int(), C.c_int()

@@ -81,6 +81,7 @@ struct HipApi {
     decltype(&rto_download_parts) download_parts = nullptr;
     decltype(&rto_download_necks) download_necks = nullptr;
     decltype(&rto_edit_parts) edit_parts = nullptr;
+    decltype(&rto_render_field_host) render_field_host = nullptr;
     std::string error;
 
     bool load() {
@@ -172,6 +173,7 @@ struct HipApi {
         download_parts = reinterpret_cast<decltype(download_parts)>(sym("rto_download_parts"));
         download_necks = reinterpret_cast<decltype(download_necks)>(sym("rto_download_necks"));
         edit_parts = reinterpret_cast<decltype(edit_parts)>(sym("rto_edit_parts"));
+        render_field_host = reinterpret_cast<decltype(render_field_host)>(sym("rto_render_field_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -431,6 +433,34 @@ void RayTracerBVH::renderLit(const Camera& camera, int width, int height, float 
         return;
     }
     m_frameW = width; m_frameH = height;
+}
+
+// A field view of the first GPU's resident grid (rto_render_field_host): the frame goes to framebuffer(), the per-pixel values and
+// the summary to fieldValues() / fieldSummary().  A grid that came as a pointer tree is built on the GPU first, as the fields'
+// makers do; a refusal leaves no frame and no values.
+int RayTracerBVH::renderField(const Camera& camera, int width, int height, float aspect, float fovDeg, const rto_field_view& view,
+                              const uint32_t* lut, const int32_t* volume) {
+    m_fieldValues.clear();
+    m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
+    if (!computeUsable("renderField")) return RTO_E_INVALID;
+    if (m_numNodes > 0 && !makeGridResident("field view")) return RTO_E_HIP;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
+    m_frameW = m_frameH = 0; m_frameStale = false;
+    m_frame.clear();
+    if (width > 0 && height > 0) {
+        m_frame.resize(static_cast<size_t>(width) * height * 4);
+        m_fieldValues.resize(static_cast<size_t>(width) * height);
+    }
+    const int rc = api().render_field_host(m_ctx, &f, &view, lut, volume, m_frame.empty() ? nullptr : m_frame.data(),
+                                           m_fieldValues.empty() ? nullptr : m_fieldValues.data(), &m_fieldSummary, nullptr);
+    if (rc != RTO_OK) {
+        m_frame.clear();
+        m_fieldValues.clear();
+        m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
+        return regionFailed(rc, "renderField");
+    }
+    m_frameW = width; m_frameH = height;
+    return RTO_OK;
 }
 
 static RayHit to_ray_hit(const rto_hit& h) {

@@ -170,6 +170,14 @@ public:
     // renderSceneTriangles' frame (the leaf triangles' surface) lit the same way (rto_render_lit_triangles_host; DESIGN.md section
     // 14).  Needs buildLeafTriangles(); without triangles resident it fails as intersectTriangles / pickSurface do: no frame, lastError set.
     void renderSurfaceLit(const Camera& camera, int width, int height, float aspect, float fovDeg, const Lighting& lighting);
+    // A frame coloured by a per-voxel int32 volume of the resident grid (rto_render_field_host): a resident
+    // field, the component labels, or with RTO_FIELD_CALLER `volume` (dimZ x dimY x dimX, x fastest).  lut: 256 entries, bytes
+    // r g b a.  RTO_OK, or the refusal's code (lastError); framebuffer() holds the frame, fieldValues() the value under every
+    // pixel (RTO_FIELD_PIXEL_MISS / _NONE where there is none), fieldSummary() the frame's counts and range.
+    int renderField(const Camera& camera, int width, int height, float aspect, float fovDeg, const rto_field_view& view,
+                    const uint32_t* lut, const int32_t* volume = nullptr);
+    const std::vector<int32_t>& fieldValues() const { return m_fieldValues; }
+    const rto_field_view_summary& fieldSummary() const { return m_fieldSummary; }
     // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
@@ -380,6 +388,8 @@ private:
     int64_t editComponents(int set, int connectivity, int select, int64_t arg);
     int64_t editMorphology(int op, float radius);
     mutable std::string m_lastError;
+    std::vector<int32_t> m_fieldValues;                // the last renderField's value per pixel
+    rto_field_view_summary m_fieldSummary = { 0, 0, 0, 0, 0, 0 };
 
     mutable std::vector<float> m_frame;
     mutable bool m_frameStale = false;   // the GPU holds a newer frame than m_frame

@@ -229,6 +229,17 @@ void rtoh_rt_render_surface_lit(RayTracerBVH* rt, const Camera* cam, int w, int 
     L.seed = seed;
     rt->renderSurfaceLit(*cam, w, h, aspect, fovDeg, L);
 }
+int rtoh_rt_render_field(RayTracerBVH* rt, const Camera* cam, int w, int h, float aspect, float fovDeg, const rto_field_view* view,
+                         const uint32_t* lut, const int32_t* volume) {
+    return rt->renderField(*cam, w, h, aspect, fovDeg, *view, lut, volume);
+}
+// values: up to `capacity` int32 of the last renderField, row-major; returns how many there are.  summary may be NULL.
+int64_t rtoh_rt_field_values(const RayTracerBVH* rt, int32_t* values, int64_t capacity, rto_field_view_summary* summary) {
+    const std::vector<int32_t>& v = rt->fieldValues();
+    if (values) std::copy(v.begin(), v.begin() + (size_t)std::min<int64_t>((int64_t)v.size(), capacity), values);
+    if (summary) *summary = rt->fieldSummary();
+    return (int64_t)v.size();
+}
 int64_t rtoh_rt_num_nodes(const RayTracerBVH* rt) { return (int64_t)rt->numNodes(); }
 int rtoh_rt_framebuffer(const RayTracerBVH* rt, float* out, int64_t capacityFloats, int* w, int* h) {
     *w = rt->frameWidth(); *h = rt->frameHeight();

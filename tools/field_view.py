@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Makes a field on a scene, renders it from the scene's camera with rto_render_field_host and writes the frame as a binary PPM
+and the legend (range, the 256 bins, the LUT) as JSON beside it.  numpy only.
+
+    python3 tools/field_view.py --scene calgary --field sky --out calgary_sky.ppm
+    python3 tools/field_view.py --scene sphere128 --field thickness --clip 0.5 --out cut.ppm
+
+Scenes: sphereN (the test sphere of edge N, Camera(0.5, 0.7, 1.8)) and calgary (the shipped city grid, Camera(0.6, 0.5, 3500)).
+Fields: distance (to EMPTY, SQRT scale: how deep inside), thickness (SQRT), skeleton, labels and parts (CATEGORY), geodesic
+(through EMPTY from voxel 0, sampled in FRONT of the surface), sun (exposure along one direction) and sky (exposure over 64
+directions of the upper hemisphere: the sky view factor; both sampled in FRONT of the surface).  --clip F keeps the part of the
+grid below the fraction F of its x extent (a section through the solid)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+import ray_tracing_octrees_amd as rto
+from ray_tracing_octrees_amd import hip
+
+HEAT = [(12, 7, 60, 255), (90, 20, 140, 255), (200, 60, 90, 255), (250, 150, 40, 255), (252, 250, 180, 255)]
+
+
+def scene(name):
+    """(grid, camera, the index of the axis that points up)."""
+    if name == "calgary":
+        z = np.load(os.path.join(ROOT, "tests", "golden", "ref_scene_cache.npz"))
+        dims = tuple(int(x) for x in z["dims"])
+        data = np.unpackbits(z["packed"])[: dims[0] * dims[1] * dims[2]].reshape(dims[2], dims[1], dims[0])
+        return rto.VoxelGrid.from_array(data, z["min"].astype(np.float32), np.float32(z["voxel"])), rto.Camera(0.6, 0.5, 3500.0), 2
+    if name.startswith("sphere"):
+        return rto.VoxelGrid.test_sphere(int(name[6:])), rto.Camera(0.5, 0.7, 1.8), 1
+    raise SystemExit(f"unknown scene {name}")
+
+
+def sky_directions(n, up):
+    """n directions spread evenly in solid angle over the hemisphere around axis `up` (a golden-angle spiral), as integers."""
+    i = np.arange(n)
+    h = 1.0 - (i + 0.5) / n
+    r = np.sqrt(1.0 - h * h)
+    phi = i * np.pi * (3.0 - np.sqrt(5.0))
+    d = np.zeros((n, 3))
+    d[:, up] = h
+    d[:, (up + 1) % 3] = r * np.cos(phi)
+    d[:, (up + 2) % 3] = r * np.sin(phi)
+    return hip.quantize_directions(d, 31)
+
+
+def make_field(ctx, field, up, voxel):
+    """Makes the field resident; returns make_field_view's keywords for it."""
+    if field == "distance":
+        ctx.distance_field(hip.SET_EMPTY)
+        return dict(source=hip.FIELD_DISTANCE, scale=hip.SCALE_SQRT)
+    if field == "thickness":
+        ctx.thickness_field(hip.SET_SOLID, 8 * float(voxel))
+        return dict(source=hip.FIELD_THICKNESS, scale=hip.SCALE_SQRT)
+    if field == "skeleton":
+        ctx.skeleton_field()
+        return dict(source=hip.FIELD_SKELETON, scale=hip.SCALE_CATEGORY)
+    if field == "labels":
+        ctx.label_components(hip.SET_SOLID, hip.CONN_FACE)
+        return dict(source=hip.FIELD_LABELS, scale=hip.SCALE_CATEGORY)
+    if field == "parts":
+        ctx.segment_parts(hip.SET_SOLID, hip.CONN_FACE, 800)
+        return dict(source=hip.FIELD_PARTS, scale=hip.SCALE_CATEGORY)
+    if field == "geodesic":
+        ctx.geodesic_field([0], hip.SET_EMPTY, hip.CONN_FACE)
+        return dict(source=hip.FIELD_GEODESIC, sample=hip.SAMPLE_FRONT)
+    if field in ("sun", "sky"):
+        dirs = sky_directions(64, up) if field == "sky" else sky_directions(8, up)[2:3]
+        ctx.exposure_field(dirs, None, hip.EXPO_SKIN, None)
+        return dict(source=hip.FIELD_EXPOSURE, sample=hip.SAMPLE_FRONT, range=(0, len(dirs)))
+    raise SystemExit(f"unknown field {field}")
+
+
+def write_ppm(path, rgba):
+    """Binary PPM of the frame's r, g, b (clamped to [0, 1], 8 bits)."""
+    rgb = np.clip(np.rint(rgba[..., :3] * 255.0), 0, 255).astype(np.uint8)
+    with open(path, "wb") as fh:
+        fh.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        fh.write(np.ascontiguousarray(rgb).tobytes())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="calgary")
+    ap.add_argument("--field", default="sky")
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--mode", choices=("first", "closest"), default="closest")
+    ap.add_argument("--clip", type=float, default=None, help="keep the grid below this fraction of its x extent")
+    ap.add_argument("--flat", action="store_true", help="no Lambert shading")
+    ap.add_argument("--out", default="field_view.ppm")
+    a = ap.parse_args()
+    grid, cam, up = scene(a.scene)
+    ctx = rto.Context(0)
+    ctx.build_octree(grid.data, grid.min, grid.voxelSize)
+    kw = make_field(ctx, a.field, up, grid.voxelSize)
+    dx, dy, dz = grid.dims
+    if a.clip is not None:
+        kw["clip"] = ((0, 0, 0), (max(1, min(dx, int(round(a.clip * dx)))), dy, dz))
+    kw["mode"] = hip.QUERY_FIRST if a.mode == "first" else hip.QUERY_CLOSEST
+    view = hip.make_field_view(shade=not a.flat, miss_rgba=(0.55, 0.7, 0.9, 1.0), none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
+    lut = hip.ramp_lut(HEAT)
+    W, H = a.width, a.height
+    f = rto.make_frame(cam.getView(), cam.getPos(), W / H, 45.0, W, H)
+    rgba, values, summary, bins = ctx.render_field_host(f, view, lut)
+    write_ppm(a.out, rgba)
+    legend = {"scene": a.scene, "field": a.field, "frame": [W, H], "hits": int(summary["hits"]), "valued": int(summary["valued"]),
+              "vmin": int(summary["vmin"]), "vmax": int(summary["vmax"]), "range": [int(summary["lo"]), int(summary["hi"])],
+              "scale": int(view.scale), "bins": bins.tolist(), "lut_rgba": lut.view(np.uint8).reshape(256, 4).tolist(),
+              "ms": list(ctx.last_field_view_ms())}
+    with open(os.path.splitext(a.out)[0] + ".legend.json", "w") as fh:
+        json.dump(legend, fh)
+    print(f"{a.out}: {W}x{H}, {legend['hits']} hit pixels, {legend['valued']} with a value in [{legend['vmin']}, {legend['vmax']}], "
+          f"{int((bins > 0).sum())} of 256 legend bins in use")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
