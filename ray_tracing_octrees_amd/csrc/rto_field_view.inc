@@ -1,6 +1,7 @@
 // rto_field_view.inc -- field views (include/rto_hip.h, rto_render_field_*): a frame of the octree coloured by an int32 volume of the
 // resident grid (a resident field, the component labels or a caller's volume).  Included at the end of rto_api.hip, after
-// rto_lit.inc (lit_mix32) and rto_query.inc (box_walk, query_face).
+// rto_lit.inc (lit_mix32, and of its frame pass tile_pixel, rooted_box_walk, kLargestBelow1e30, frame_bound_check and
+// frame_tree_check) and rto_query.inc (query_face).
 //
 // Rule (DESIGN.md section 27).  The hit is the box query of view.mode on the frame's pixel ray in the window the clip box leaves;
 // the voxel of the hit is floor((p - gridMin) / voxelSize) of p = o + d tHit, clamped into the leaf (and the clip box), with the
@@ -47,23 +48,6 @@ struct FieldArgs {
     FieldSumRaw* sum;
 };
 
-// box_walk in the window [tlo, thi], or for a tree that is one leaf the root's own test (lit_walk with a window).
-template <int QMODE>
-__device__ __forceinline__ DescHit field_walk(const RenderParams& P, const Geo& G, const Ray r, float tlo, float thi, bool valid,
-                                              const FieldArgs& A, const uint2* __restrict__ desc, uint2* stk, unsigned* stkNode) {
-    if (!A.rootLeaf) return box_walk<QMODE>(P, G, r, tlo, thi, valid, desc, stk, stkNode);
-    DescHit w;
-    w.hit = false; w.t = 1e30f; w.x = w.y = w.z = 0; w.size = P.rootSize; w.j = 0; w.node = 0;
-    if (valid && A.nodes[0].isSolid == 1) {
-        float tNear, tFar, a0, a1, a2, a3, a4, a5;
-        bool pass = slab_exact(G, r, 0, 0, 0, P.rootSize, tNear, tFar, a0, a1, a2, a3, a4, a5) && !(tNear >= 1e30f);
-        if (QMODE != kQueryFirst) pass = pass && !(tNear > thi);
-        const float tHit = gmax(tlo, tNear);
-        if (pass && tHit <= tFar && tHit <= thi) { w.hit = true; w.t = tHit; }
-    }
-    return w;
-}
-
 // One axis of the voxel of the hit: floor((p - g) / vs) clamped in float into [lo, hi] (a NaN goes to lo), then into the clip box.
 __device__ __forceinline__ int field_axis(float p, float g, float vs, int lo, int hi, bool clip, int clo, int chi) {
     float q = __builtin_floorf((p - g) / vs);
@@ -83,15 +67,11 @@ __global__ __launch_bounds__(kBlock) void k_field_sample(RenderParams P, FieldAr
     desc_stacks(lds_stack, P.depth, stk, stkNode);
     const Geo G = geo_of(P);
     const int lane = threadIdx.x & 63;
-    const int tile = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    const int tx = tile % P.tilesX, ty = tile / P.tilesX;
-    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
-    const bool inFrame = ty < P.tilesY && px < P.W && py < P.H;
-    Ray r;
-    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
-    if (inFrame) r = generate_ray_tab(P, px, py);
+    const TilePixel t = tile_pixel(P);
+    const Ray r = t.r;
+    const bool inFrame = t.in;
     // the window: (0, below 1e30), or what the clip box leaves of it
-    float tlo = 0.0f, thi = __uint_as_float(0x7149f2c9u);
+    float tlo = 0.0f, thi = kLargestBelow1e30;
     bool valid = inFrame;
     if (A.clip && inFrame) {
         const float t1x = (A.planeLo[0] - r.ox) * r.ix, t2x = (A.planeHi[0] - r.ox) * r.ix;
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_field_sample(RenderParams P, FieldAr
         tlo = gmax(0.0f, tNear);
         thi = gmin(thi, tFar);
     }
-    const DescHit w = field_walk<QMODE>(P, G, r, tlo, thi, valid, A, desc, stk, stkNode);
+    const DescHit w = rooted_box_walk<QMODE>(P, G, r, tlo, thi, valid, A.rootLeaf, A.nodes, desc, stk, stkNode);
 
     int value = kFieldMiss;
     float ndotl = 0.0f;
@@ -135,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_field_sample(RenderParams P, FieldAr
         }
     }
     if (inFrame) {
-        const unsigned pix = (unsigned)py * (unsigned)P.W + (unsigned)px;   // < 2^32 (field_check)
+        const unsigned pix = (unsigned)t.py * (unsigned)P.W + (unsigned)t.px;   // < 2^32 (field_check)
         A.values[pix] = value;
         if (A.shade) A.ndotl[4 * (size_t)pix] = ndotl;
     }
@@ -282,17 +262,11 @@ static int field_check(rto_context* c, const char* fn, const rto_frame* f, const
     if (v->valid_lo > v->valid_hi || v->valid_lo <= RTO_FIELD_PIXEL_NONE)
         return fail(c, RTO_E_INVALID, name + ": valid_lo must be above INT32_MIN + 1 and at most valid_hi");
     if (v->range_lo > v->range_hi) return fail(c, RTO_E_INVALID, name + ": range_lo > range_hi");
-    if (f->width <= 0 || f->height <= 0) return fail(c, RTO_E_INVALID, name + ": width/height must be positive");
-    const uint64_t pixels = (uint64_t)f->width * (uint64_t)f->height;
-    const uint64_t tileLanes = 64u * (uint64_t)((f->width + 7) / 8) * (uint64_t)((f->height + 7) / 8);
-    if (pixels + 128u >= ((uint64_t)1 << 32) || tileLanes + 256u >= ((uint64_t)1 << 32))
-        return fail(c, RTO_E_INVALID, name + ": the frame is too large: width * height + 128 and 64 lanes per 8x8 tile must stay below 2^32");
+    int rc = frame_bound_check(c, name, f, 1);
+    if (rc != RTO_OK) return rc;
     if (v->source == RTO_FIELD_CALLER && !d_volume) return fail(c, RTO_E_INVALID, name + ": RTO_FIELD_CALLER needs a volume");
     if (v->source != RTO_FIELD_CALLER && d_volume) return fail(c, RTO_E_INVALID, name + ": a volume goes with RTO_FIELD_CALLER only");
-    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, name + ": no octree uploaded");
-    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, name + ": the octree came from rto_upload_octree: no voxel grid is resident");
-    if (c->numNodes > 1 && !(c->canonical && c->numInternal > 0))
-        return fail(c, RTO_E_UNSUPPORTED, name + ": a field view needs a canonical octree (descriptor tree)");
+    if ((rc = frame_tree_check(c, name, true, ": a field view needs a canonical octree (descriptor tree)")) != RTO_OK) return rc;
     if (v->clip)
         for (int a = 0; a < 3; a++)
             if (v->clip_lo[a] < 0 || v->clip_hi[a] > c->voxDim[a] || v->clip_lo[a] >= v->clip_hi[a])

@@ -252,6 +252,32 @@ def test_frames_match_the_statement(ctx, orc, scenes, scene, cam):
 
 
 @gpu
+def test_a_frame_smaller_than_one_tile(ctx, orc, scenes):
+    """sphere64 at 5 x 3, every (shadow, K) setting bit for bit against lit_ref: the frame is part of one 8x8 tile, so three of
+    its workgroup's four waves lie behind the last tile, and with at most 15 hits the shadow rays fill part of one wave and the
+    AO rays start at the padding alone (ray 64, or 0 without the shadow term)."""
+    rto = _rto()
+    s = scenes("sphere64")
+    ctx.set_kernel(rto.KERNEL_AUTO)
+    ctx.upload_octree(s.nodes, s.min, s.voxel)
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    view, pos = make_camera(orc, 0.6, 0.45, 1.0)                    # nine of the fifteen pixels hit
+    W, H = 5, 3
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    rd = _rays(orc, view, pos, W, H)
+    radius = float(np.float32(4 * float(s.voxel)))
+    hits = occluded = 0
+    for sh, K in SETTINGS:
+        img, vis = ctx.render_lit_host(f, _light(LIGHTS[1], sh, K, radius, 0x9E3779B9), vis=True)
+        want, wvis = lr.lit_frame(T, s.voxel, pos, rd, W, H, _table(), light_dir=LIGHTS[1], shadow=sh, K=K, radius=radius, seed=0x9E3779B9)
+        _equal(img, want, f"5x3 shadow {sh} K {K}")
+        assert (vis == wvis).all(), f"5x3 shadow {sh} K {K}: visibility differs at {int((vis != wvis).sum())} pixels"
+        hits += int((vis >= 0).sum())
+        occluded += int((vis > 0).sum())
+    assert hits == 9 * len(SETTINGS) and occluded > 0
+
+
+@gpu
 @pytest.mark.parametrize("scene,cams", [("sphere256", [SPHERE_CAM]), ("calgary", ["calgary_default", "calgary_oblique"])])
 def test_no_terms_is_the_box_render_at_1080p(ctx, orc, scenes, camera, scene, cams):
     """Configs 2 and 4 at 1920x1080: shadow off, K = 0 and the default light give rto_render_device's frame bit for bit."""

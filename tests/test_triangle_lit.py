@@ -333,6 +333,29 @@ def test_frames_match_the_statement(ctx, orc, scenes, scene, cam):
     assert hits > 0 and occluded > 0
 
 
+@gpu
+def test_a_frame_smaller_than_one_tile(ctx, orc, scenes):
+    """sphere64 at 5 x 3, every (shadow, K) setting bit for bit against tri_lit_ref: the frame is part of one 8x8 tile, so three
+    of its workgroup's four waves lie behind the last tile, and with at most 15 hits the shadow rays fill part of one wave and the
+    AO rays start at the padding alone (ray 64, or 0 without the shadow term)."""
+    rto = _rto()
+    s = scenes("sphere64")
+    tris, off = _resident(ctx, s)
+    T = q.Tree32(s.nodes, s.min, s.voxel)
+    view, pos = make_camera(orc, 0.6, 0.45, 1.0)                    # nine of the fifteen pixels hit
+    W, H = 5, 3
+    f = rto.make_frame(view, pos, W / H, FOV, W, H)
+    rd = _rays(orc, view, pos, W, H)
+    first = tq.query_tri32(T, tris, off, pos, rd)[tq.FIRST]
+    radius = float(np.float32(4 * float(s.voxel)))
+    hits = occluded = 0
+    for sh, K in SETTINGS:
+        vis = _check(ctx, T, tris, off, s.voxel, f, pos, rd, W, H, LIGHTS[1], sh, K, radius, 0x9E3779B9, f"5x3 shadow {sh} K {K}", first)
+        hits += int((vis >= 0).sum())
+        occluded += int((vis > 0).sum())
+    assert hits == 9 * len(SETTINGS) and occluded > 0
+
+
 def _identity_case(ctx, orc, g, view, pos, W, H, sample):
     """(0, 0) is rto_render_triangles(shadow = 0) on the whole frame; (1, 0) is its shadowed frame on the sampled pixels whose shadow
     ray has one verdict under FIRST and ANY in tri_query_ref.  Returns (excluded, casting) of the sample."""
