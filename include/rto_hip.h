@@ -1430,6 +1430,89 @@ int  rto_render_field_host(rto_context* ctx, const rto_frame* frame, const rto_f
  * stream-captured or launched after rto_timing_begin(ctx, -1). */
 int  rto_last_field_view_ms(const rto_context* ctx, float ms[2]);
 
+/* ---- field projections ------------------------------------------------------
+ * A frame from the renders' camera whose pixel value is a reduction of an int32 volume of the resident grid over the voxels the
+ * pixel ray crosses in the grid, or in a section box: maximum, minimum, mean, count or the first value inside [valid_lo, valid_hi];
+ * coloured as a field view is.  The reference marches its dense volume per pixel in VolumeRaycastRenderer;
+ * this is the exact-integer form of that march.  The octree is not walked.  "Valued": a voxel whose value lies in [valid_lo,
+ * valid_hi].  All float arithmetic is float32, one IEEE operation per operator, in the order written; the only floats are the plane
+ * parameters T below, so floats decide which voxels a ray visits and nothing else.  Rule:
+ *   ray       the frame's pixel ray o, d, inv = 1.0f / d (generate_ray_tab: rto_render_device's).  rto_update_frustum is ignored.  A
+ *             ray with a non-finite component of o, or with all three axes still, is a miss.
+ *   planes    P_a(j) = gridMin[a] + (float)j * voxelSize for j = 0 .. dim[a] (the field views' clip-plane formula), and T_a(j) =
+ *             (P_a(j) - o[a]) * inv[a].  Float rounding is monotone, so T_a is non-decreasing in j when inv[a] > 0 and
+ *             non-increasing otherwise.
+ *   still     axis a is still when inv[a] is not finite (d[a] is 0, -0.0, or so small that 1 / d overflows).  Its coordinate is
+ *             floor((o[a] - gridMin[a]) / voxelSize) for the whole ray, and no plane of it is an event.
+ *   events    a pair (moving axis a, plane j) with T_a(j) > 0.  Events are ordered by (T, a), x before y before z; events of one
+ *             axis with equal T in its direction of travel.  Planes with T_a(j) <= 0 are crossed at the start.
+ *   states    the coordinate of a moving axis is crossed - 1 when inv[a] > 0 and dim[a] - crossed otherwise, `crossed` being the
+ *             number of its planes crossed so far: it runs from -1 (or dim) outside the grid, through it, to the other outside.
+ *             The walk is the start state and then the state after every event, in order.
+ *   visited   the states with lo[a] <= c[a] < hi[a] on all three axes, in walk order; [lo, hi) is the clip box, or [0, dim) without
+ *             one.  There is no slab test and no t window: a section box filters the whole-grid walk, so boxes that partition the
+ *             grid partition every ray's visited voxels, and counts and sums add up exactly.
+ *   value     RTO_FIELD_PIXEL_MISS when no voxel is visited; RTO_FIELD_PIXEL_NONE when none of the visited is valued (under
+ *             COUNT too); else MAX the largest and MIN the smallest valued value, MEAN floor(sum / count) in int64 towards minus
+ *             infinity, COUNT the number of valued voxels, FIRST the value of the first valued voxel in walk order.
+ *   voxel     d_voxels: the linear index (z * dimY + y) * dimX + x of the deciding voxel, -1 without one: under MAX and MIN the
+ *             first voxel in walk order that holds the pixel's value, under MEAN, COUNT and FIRST the first valued voxel.
+ *   totals    d_sums (int64) and d_counts: the sum and the number of the valued voxels visited, under every op; 0 and 0 for a
+ *             miss or NONE.
+ *   colours   d_rgba, d_summary and d_bins come from the pixel values by the field views' summary, index, bins and colour rules,
+ *             unchanged and unshaded: a projection has no surface.
+ * The march skips 8 x 8 x 8 bricks through a table of each brick's largest and smallest valued value, rebuilt by every call (it
+ * depends on the window, and a caller's volume may have changed).  The table changes no output (rto_debug_set_projection_table).
+ * Sources are the field views'.  Needs a resident grid (rto_build_octree, rto_voxelize_mesh, the edits) of fewer than 2^31
+ * voxels; the tree need not be canonical.
+ * Errors, each leaving the context untouched, checked in this order: RTO_E_INVALID: a NULL frame, projection, LUT or rgba; a
+ * misaligned buffer (d_rgba 16 bytes, d_sums, d_summary and d_bins 8, d_lut, d_volume, d_values, d_voxels and d_counts 4); an
+ * unknown source, op or scale; reserved != 0; valid_lo > valid_hi or valid_lo <= INT32_MIN + 1; range_lo > range_hi; a width or
+ * height below 1; a frame beyond the lit render's limits; CALLER without a volume, or a volume with another source.
+ * RTO_E_NO_OCTREE: nothing uploaded.  RTO_E_UNSUPPORTED: no resident grid (rto_upload_octree), then a grid of 2^31 voxels or more.
+ * RTO_E_INVALID: a clip box with clip_lo[a] < 0, clip_hi[a] > dim[a] or clip_lo[a] >= clip_hi[a]; last, a named source that is not
+ * resident, in its readers' words.
+ * The device form is asynchronous on hip_stream.  Its work buffers (the brick table, the field views' summary block and, when
+ * d_values is NULL, their value buffer) live on the context under the field views' rules: a larger grid or frame than any before
+ * allocates, and then must not be stream-captured; one set per context, so projections and field views on different streams of
+ * one context must not run at the same time. */
+#define RTO_PROJECT_MAX    0
+#define RTO_PROJECT_MIN    1
+#define RTO_PROJECT_MEAN   2
+#define RTO_PROJECT_COUNT  3
+#define RTO_PROJECT_FIRST  4
+typedef struct rto_field_projection {   /* 112 bytes */
+    int32_t  source;                /* RTO_FIELD_* */
+    int32_t  op;                    /* RTO_PROJECT_* */
+    int32_t  scale;                 /* RTO_SCALE_* */
+    int32_t  valid_lo, valid_hi;    /* the window of valued voxels; defaults 0 and 0x7ffffffe; valid_lo > INT32_MIN + 1 */
+    int32_t  range_lo, range_hi;    /* equal: auto range */
+    int32_t  clip;                  /* != 0: the section box below applies */
+    int32_t  clip_lo[3], clip_hi[3];   /* voxel indices, x y z: 0 <= clip_lo < clip_hi <= dim */
+    float    miss_rgba[4];
+    float    none_rgba[4];
+    int32_t  reserved[6];           /* 0 */
+} rto_field_projection;
+
+int  rto_project_field_device(rto_context* ctx, const rto_frame* frame, const rto_field_projection* projection,
+                              const uint32_t* d_lut /* 256 */, const int32_t* d_volume /* RTO_FIELD_CALLER only */,
+                              void* d_rgba /* float4 per pixel, 16-byte aligned */, int32_t* d_values /* may be NULL */,
+                              int32_t* d_voxels /* may be NULL */, int64_t* d_sums /* may be NULL */, int32_t* d_counts /* may be NULL */,
+                              rto_field_view_summary* d_summary /* may be NULL */, int64_t* d_bins /* 256, may be NULL */,
+                              void* hip_stream);
+/* The same with host buffers (the LUT and a caller's volume too); synchronous on the context's stream. */
+int  rto_project_field_host(rto_context* ctx, const rto_frame* frame, const rto_field_projection* projection, const uint32_t* lut /* 256 */,
+                            const int32_t* volume /* RTO_FIELD_CALLER only */, float* host_rgba, int32_t* host_values /* may be NULL */,
+                            int32_t* host_voxels /* may be NULL */, int64_t* host_sums /* may be NULL */,
+                            int32_t* host_counts /* may be NULL */, rto_field_view_summary* host_summary /* may be NULL */,
+                            int64_t* host_bins /* 256, may be NULL */);
+/* Device time of the last projection's three kernels in ms (bricks, march, shade); waits for that frame.  -1: not run, or the
+ * frame was stream-captured or launched after rto_timing_begin(ctx, -1).  Without the table the first is the empty interval. */
+int  rto_last_projection_ms(const rto_context* ctx, float ms[3]);
+/* Developer aid in the style of RTO_KERNEL_GENERIC: 0 = the march consults no brick table (and none is built), 1 = it does
+ * (default).  The same loop runs either way and no output depends on it: for A/B timing and for the test that says so. */
+int  rto_debug_set_projection_table(rto_context* ctx, int enabled);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -173,6 +173,14 @@ struct rto_context {
     hipEvent_t fvEv[3] = { nullptr, nullptr, nullptr };
     bool fvTimed = false;
 
+    // field projections (rto_project.inc): the brick table of the call in flight (pjBrickCap records), the events around the three
+    // kernels of the last frame (pjTimed: they were recorded) and whether the march consults the table (rto_debug_set_projection_table)
+    uint2* d_pjBricks = nullptr;
+    size_t pjBrickCap = 0;
+    hipEvent_t pjEv[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool pjTimed = false;
+    bool pjTable = true;
+
     // mesh extraction (rto_mesh.inc): the last mesh (a snapshot the context owns) and the first node of every tree level
     float4* d_mesh = nullptr;
     int* d_meshNode = nullptr;
@@ -415,6 +423,8 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_fvSum);
     (void)hipFree(c->d_fvValues);
     for (hipEvent_t e : c->fvEv) if (e) (void)hipEventDestroy(e);
+    (void)hipFree(c->d_pjBricks);
+    for (hipEvent_t e : c->pjEv) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_mesh);
     (void)hipFree(c->d_meshNode);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
@@ -3036,6 +3046,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"
 #include "rto_field_view.inc"
+#include "rto_project.inc"
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
 #include "rto_region.inc"

@@ -61,6 +61,7 @@ SYMBOLS = (
     "rto_segment_parts", "rto_download_part_labels", "rto_download_parts", "rto_download_necks", "rto_parts_device", "rto_edit_parts",
     "rto_last_parts_ms", "rto_debug_parts", "rto_debug_parts_capacity",
     "rto_render_field_device", "rto_render_field_host", "rto_last_field_view_ms",
+    "rto_project_field_device", "rto_project_field_host", "rto_last_projection_ms", "rto_debug_set_projection_table",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -131,6 +132,8 @@ SAMPLE_HIT, SAMPLE_FRONT = 0, 1
 SCALE_LINEAR, SCALE_SQRT, SCALE_CATEGORY = 0, 1, 2
 FIELD_PIXEL_MISS, FIELD_PIXEL_NONE = -2**31, -2**31 + 1
 FIELD_VIEW_SUMMARY_DTYPE = np.dtype([("hits", "<i8"), ("valued", "<i8"), ("vmin", "<i4"), ("vmax", "<i4"), ("lo", "<i4"), ("hi", "<i4")])
+# field projections (rto_project_field_*): RTO_PROJECT_*
+PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN, PROJECT_COUNT, PROJECT_FIRST = 0, 1, 2, 3, 4
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -270,6 +273,31 @@ def make_field_view(source, sample=SAMPLE_HIT, mode=QUERY_FIRST, scale=SCALE_LIN
         v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
         v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
     v.shade = 1 if shade else 0
+    for k in (0, 1, 2, 3):
+        v.miss_rgba[k] = _f(miss_rgba[k])
+        v.none_rgba[k] = _f(none_rgba[k])
+    return v
+
+
+# struct rto_field_projection (112 bytes): field projections (rto_project_field_*)
+class FieldProjection(C.Structure):
+    _fields_ = [("source", C.c_int32), ("op", C.c_int32), ("scale", C.c_int32), ("valid_lo", C.c_int32), ("valid_hi", C.c_int32),
+                ("range_lo", C.c_int32), ("range_hi", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_int32 * 3),
+                ("clip_hi", C.c_int32 * 3), ("miss_rgba", C.c_float * 4), ("none_rgba", C.c_float * 4), ("reserved", C.c_int32 * 6)]
+
+
+def make_field_projection(source, op=PROJECT_MAX, scale=SCALE_LINEAR, valid=(0, 0x7ffffffe), range=(0, 0), clip=None,
+                          miss_rgba=(0.0, 0.0, 0.0, 1.0), none_rgba=(0.25, 0.25, 0.25, 1.0)) -> FieldProjection:
+    """An rto_field_projection with the header's defaults.  range: (lo, hi), equal for auto range; clip: None or ((x0, y0, z0),
+    (x1, y1, z1)) in voxel indices."""
+    v = FieldProjection()
+    v.source, v.op, v.scale = int(source), int(op), int(scale)
+    v.valid_lo, v.valid_hi = int(valid[0]), int(valid[1])
+    v.range_lo, v.range_hi = int(range[0]), int(range[1])
+    v.clip = 0 if clip is None else 1
+    for a in (0, 1, 2):
+        v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
+        v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
     for k in (0, 1, 2, 3):
         v.miss_rgba[k] = _f(miss_rgba[k])
         v.none_rgba[k] = _f(none_rgba[k])
@@ -603,6 +631,10 @@ def load():
     L.rto_render_field_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldView), vp, vp, vp, vp, vp, vp, vp]
     L.rto_render_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldView), vp, vp, vp, vp, vp, vp]
     L.rto_last_field_view_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_project_field_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldProjection), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rto_project_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldProjection), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rto_last_projection_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_debug_set_projection_table.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -1023,6 +1055,53 @@ class Context:
     def last_field_view_ms(self):
         """(sample kernel, shade kernel) of the last field view in ms; -1: not run."""
         return self._last_ms("rto_last_field_view_ms", 2)
+
+    # -- field projections -----------------------------------------------------
+    def project_field_host(self, frame: Frame, projection: FieldProjection, lut, volume=None, totals: bool = True):
+        """A frame whose pixels reduce an int32 volume of the resident grid along their rays (rto_project_field_host).  lut: 256
+        uint32 (ramp_lut); volume: the (dimZ, dimY, dimX) int32 array of FIELD_CALLER, None for every other source.  Returns (rgba
+        (H, W, 4) float32, values (H, W) int32, voxels (H, W) int32, sums (H, W) int64, counts (H, W) int32, summary (one
+        FIELD_VIEW_SUMMARY_DTYPE record), bins (256,) int64); totals=False asks for neither sums nor counts (both None), which lets
+        MAX, MIN and FIRST skip or stop on more than empty bricks."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("project_field_host: the LUT has 256 entries")
+        if volume is not None:
+            volume = np.ascontiguousarray(volume, dtype=np.int32)
+            dims = (C.c_int * 3)()
+            if self._L.rto_download_voxels(self._h, None, 0, dims) == RTO_OK and volume.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"project_field_host: the volume must be {(dims[2], dims[1], dims[0])}, not {volume.shape}")
+        shape = (frame.height, frame.width)
+        rgba = np.empty(shape + (4,), np.float32)
+        values, voxels = np.empty(shape, np.int32), np.empty(shape, np.int32)
+        sums = np.empty(shape, np.int64) if totals else None
+        counts = np.empty(shape, np.int32) if totals else None
+        summary = np.zeros(1, FIELD_VIEW_SUMMARY_DTYPE)
+        bins = np.zeros(256, np.int64)
+        self._check(self._L.rto_project_field_host(self._h, C.byref(frame), C.byref(projection), lut.ctypes.data,
+                                                   volume.ctypes.data if volume is not None else None, rgba.ctypes.data,
+                                                   values.ctypes.data, voxels.ctypes.data, sums.ctypes.data if totals else None,
+                                                   counts.ctypes.data if totals else None, summary.ctypes.data, bins.ctypes.data))
+        return rgba, values, voxels, sums, counts, summary[0], bins
+
+    def project_field_device(self, frame: Frame, projection: FieldProjection, d_lut: int, d_rgba: int, d_volume: int = 0,
+                             d_values: int = 0, d_voxels: int = 0, d_sums: int = 0, d_counts: int = 0, d_summary: int = 0,
+                             d_bins: int = 0, stream: int = 0):
+        """Asynchronous: the projection into d_rgba (W*H*16 bytes) and, where given, the values, voxels and counts (W*H int32
+        each), the sums (W*H int64), the summary (32 bytes) and the 256 int64 bins; d_lut: 256 uint32 on the device; d_volume: the
+        device volume of FIELD_CALLER."""
+        p = lambda x: C.c_void_p(x) if x else None
+        self._check(self._L.rto_project_field_device(self._h, C.byref(frame), C.byref(projection), p(d_lut), p(d_volume), p(d_rgba),
+                                                     p(d_values), p(d_voxels), p(d_sums), p(d_counts), p(d_summary), p(d_bins),
+                                                     p(stream)))
+
+    def last_projection_ms(self):
+        """(brick table, march, shade kernel) of the last projection in ms; -1: not run."""
+        return self._last_ms("rto_last_projection_ms", 3)
+
+    def debug_set_projection_table(self, enabled: bool):
+        """rto_debug_set_projection_table: whether the march consults the brick table (default) or walks every voxel."""
+        self._check(self._L.rto_debug_set_projection_table(self._h, 1 if enabled else 0))
 
     # -- triangle queries (the resident leaf triangles) --------------------
     def query_triangles(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:

@@ -128,6 +128,14 @@ def load():
     L.rtoh_rt_render_field.restype = C.c_int
     L.rtoh_rt_field_values.argtypes = [_vp, _vp, C.c_int64, _vp]
     L.rtoh_rt_field_values.restype = C.c_int64
+    L.rtoh_rt_project_field.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp]
+    L.rtoh_rt_project_field.restype = C.c_int
+    L.rtoh_rt_projection_values.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int64]
+    L.rtoh_rt_projection_values.restype = C.c_int64
+    L.rtoh_projection_walk.argtypes = [_vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64]
+    L.rtoh_projection_walk.restype = C.c_int64
+    L.rtoh_projection_reduce.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.c_int32, _vp]
+    L.rtoh_projection_reduce.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
     L.rtoh_rt_intersect_spans.argtypes = [_vp, _vp, C.c_int64, C.c_float, C.c_float, _vp]
@@ -753,6 +761,36 @@ class RayTracerBVH:
         s = np.zeros(1, FIELD_VIEW_SUMMARY_DTYPE)
         load().rtoh_rt_field_values(self._h, None, 0, s.ctypes.data)
         return s[0]
+
+    def projectField(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, projection, lut, volume=None) -> int:
+        """Addition: RayTracerBVH::projectField -- a frame whose pixels reduce a per-voxel int32 volume of the resident grid over
+        the voxels their rays cross.  projection: a hip.FieldProjection; lut and volume as renderField's.
+        RTO_OK or the refusal's code (lastError); read the frame with framebuffer(), the per-pixel outputs with
+        projectionValues(), the counts and range with fieldSummary()."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("projectField: the LUT has 256 entries")
+        vol = None if volume is None else np.ascontiguousarray(volume, dtype=np.int32)
+        if vol is not None:
+            dims = (C.c_int * 3)()
+            load().rtoh_rt_grid(self._h, dims, None)
+            if vol.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"projectField: the volume must be {(dims[2], dims[1], dims[0])}, not {vol.shape}")
+        return int(load().rtoh_rt_project_field(self._h, camera._h, int(width), int(height), _f(aspect), _f(fovDeg),
+                                                C.addressof(projection), lut.ctypes.data, vol.ctypes.data if vol is not None else None))
+
+    def projectionValues(self):
+        """Addition: RayTracerBVH::projectionValues -- the last projectField's (values, voxels, sums, counts), (H, W) each; None
+        when no projection has been rendered."""
+        w, h = C.c_int(), C.c_int()
+        n = int(load().rtoh_rt_projection_values(self._h, None, None, None, None, 0))
+        if n == 0 or not load().rtoh_rt_framebuffer(self._h, None, 0, C.byref(w), C.byref(h)) or w.value * h.value != n:
+            return None
+        shape = (h.value, w.value)
+        values, voxels, counts = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.int32)
+        sums = np.empty(shape, np.int64)
+        load().rtoh_rt_projection_values(self._h, values.ctypes.data, voxels.ctypes.data, sums.ctypes.data, counts.ctypes.data, n)
+        return values, voxels, sums, counts
 
     def framebuffer(self) -> np.ndarray | None:
         w, h = C.c_int(), C.c_int()

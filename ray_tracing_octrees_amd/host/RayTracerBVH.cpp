@@ -82,6 +82,7 @@ struct HipApi {
     decltype(&rto_download_necks) download_necks = nullptr;
     decltype(&rto_edit_parts) edit_parts = nullptr;
     decltype(&rto_render_field_host) render_field_host = nullptr;
+    decltype(&rto_project_field_host) project_field_host = nullptr;
     std::string error;
 
     bool load() {
@@ -174,6 +175,7 @@ struct HipApi {
         download_necks = reinterpret_cast<decltype(download_necks)>(sym("rto_download_necks"));
         edit_parts = reinterpret_cast<decltype(edit_parts)>(sym("rto_edit_parts"));
         render_field_host = reinterpret_cast<decltype(render_field_host)>(sym("rto_render_field_host"));
+        project_field_host = reinterpret_cast<decltype(project_field_host)>(sym("rto_project_field_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -458,6 +460,37 @@ int RayTracerBVH::renderField(const Camera& camera, int width, int height, float
         m_fieldValues.clear();
         m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
         return regionFailed(rc, "renderField");
+    }
+    m_frameW = width; m_frameH = height;
+    return RTO_OK;
+}
+
+// A projection of the first GPU's resident grid (rto_project_field_host): the frame goes to framebuffer(), the per-pixel outputs
+// to projectionValues(), the summary to fieldSummary().  A refusal leaves no frame and no values.
+int RayTracerBVH::projectField(const Camera& camera, int width, int height, float aspect, float fovDeg,
+                               const rto_field_projection& projection, const uint32_t* lut, const int32_t* volume) {
+    m_projection = ProjectionValues();
+    m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
+    if (!computeUsable("projectField")) return RTO_E_INVALID;
+    if (m_numNodes > 0 && !makeGridResident("field projection")) return RTO_E_HIP;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
+    m_frameW = m_frameH = 0; m_frameStale = false;
+    m_frame.clear();
+    if (width > 0 && height > 0) {
+        const size_t n = static_cast<size_t>(width) * height;
+        m_frame.resize(n * 4);
+        m_projection.values.resize(n); m_projection.voxels.resize(n); m_projection.counts.resize(n); m_projection.sums.resize(n);
+    }
+    ProjectionValues& p = m_projection;
+    const bool have = !m_frame.empty();
+    const int rc = api().project_field_host(m_ctx, &f, &projection, lut, volume, have ? m_frame.data() : nullptr,
+                                            have ? p.values.data() : nullptr, have ? p.voxels.data() : nullptr,
+                                            have ? p.sums.data() : nullptr, have ? p.counts.data() : nullptr, &m_fieldSummary, nullptr);
+    if (rc != RTO_OK) {
+        m_frame.clear();
+        m_projection = ProjectionValues();
+        m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
+        return regionFailed(rc, "projectField");
     }
     m_frameW = width; m_frameH = height;
     return RTO_OK;

@@ -178,6 +178,17 @@ public:
                     const uint32_t* lut, const int32_t* volume = nullptr);
     const std::vector<int32_t>& fieldValues() const { return m_fieldValues; }
     const rto_field_view_summary& fieldSummary() const { return m_fieldSummary; }
+    // A frame whose pixels reduce such a volume over the voxels their rays cross in the grid or in the projection's section box
+    // (rto_project_field_host): maximum, minimum, mean, count or first value in the window.  Sources, LUT
+    // and return value as renderField's; the octree is not walked.  framebuffer() holds the frame, projectionValues() the value,
+    // the deciding voxel, the sum and the count under every pixel, fieldSummary() the frame's counts and range.
+    struct ProjectionValues {
+        std::vector<int32_t> values, voxels, counts;
+        std::vector<int64_t> sums;
+    };
+    int projectField(const Camera& camera, int width, int height, float aspect, float fovDeg, const rto_field_projection& projection,
+                     const uint32_t* lut, const int32_t* volume = nullptr);
+    const ProjectionValues& projectionValues() const { return m_projection; }
     // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
@@ -390,6 +401,7 @@ private:
     mutable std::string m_lastError;
     std::vector<int32_t> m_fieldValues;                // the last renderField's value per pixel
     rto_field_view_summary m_fieldSummary = { 0, 0, 0, 0, 0, 0 };
+    ProjectionValues m_projection;                     // the last projectField's outputs per pixel
 
     mutable std::vector<float> m_frame;
     mutable bool m_frameStale = false;   // the GPU holds a newer frame than m_frame

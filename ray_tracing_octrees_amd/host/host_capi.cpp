@@ -18,6 +18,7 @@
 #include "Thickness.h"
 #include "Parts.h"
 #include "Measure.h"
+#include "Projection.h"
 #include "Camera.h"
 #include "Frustum.h"
 #include "OctreeVoxel.h"
@@ -239,6 +240,35 @@ int64_t rtoh_rt_field_values(const RayTracerBVH* rt, int32_t* values, int64_t ca
     if (values) std::copy(v.begin(), v.begin() + (size_t)std::min<int64_t>((int64_t)v.size(), capacity), values);
     if (summary) *summary = rt->fieldSummary();
     return (int64_t)v.size();
+}
+int rtoh_rt_project_field(RayTracerBVH* rt, const Camera* cam, int w, int h, float aspect, float fovDeg, const rto_field_projection* proj,
+                          const uint32_t* lut, const int32_t* volume) {
+    return rt->projectField(*cam, w, h, aspect, fovDeg, *proj, lut, volume);
+}
+// Up to `capacity` entries each of the last projectField's values, voxels, sums and counts, row-major; returns how many there are.
+int64_t rtoh_rt_projection_values(const RayTracerBVH* rt, int32_t* values, int32_t* voxels, int64_t* sums, int32_t* counts, int64_t capacity) {
+    const RayTracerBVH::ProjectionValues& p = rt->projectionValues();
+    const size_t n = (size_t)std::min<int64_t>((int64_t)p.values.size(), capacity);
+    if (values) std::copy(p.values.begin(), p.values.begin() + n, values);
+    if (voxels) std::copy(p.voxels.begin(), p.voxels.begin() + n, voxels);
+    if (sums) std::copy(p.sums.begin(), p.sums.begin() + n, sums);
+    if (counts) std::copy(p.counts.begin(), p.counts.begin() + n, counts);
+    return (int64_t)p.values.size();
+}
+// The CPU form of a projection (host/Projection.h): one ray's visited voxels (x, y, z per voxel, up to `capacity` of them; returns
+// how many there are) and the reduction of a volume over such a walk (result: value, voxel, sum, count).
+int64_t rtoh_projection_walk(const float gridMin[3], float voxelSize, const int32_t dim[3], const float o[3], const float d[3],
+                             const int32_t lo[3], const int32_t hi[3], int32_t* cells, int64_t capacity) {
+    const std::vector<rto_host::ProjectionVoxel> w = rto_host::projectionWalk(gridMin, voxelSize, dim, o, d, lo, hi);
+    for (size_t i = 0; i < w.size() && (int64_t)i < capacity; i++) { cells[3 * i] = w[i].x; cells[3 * i + 1] = w[i].y; cells[3 * i + 2] = w[i].z; }
+    return (int64_t)w.size();
+}
+void rtoh_projection_reduce(const int32_t* volume, const int32_t dim[3], const int32_t* cells, int64_t n, int op, int32_t validLo,
+                            int32_t validHi, int64_t result[4]) {
+    static_assert(sizeof(rto_host::ProjectionVoxel) == 12, "x, y, z");
+    const rto_host::ProjectionResult r = rto_host::projectionReduce(volume, dim, reinterpret_cast<const rto_host::ProjectionVoxel*>(cells), n,
+                                                                    op, validLo, validHi);
+    result[0] = r.value; result[1] = r.voxel; result[2] = r.sum; result[3] = r.count;
 }
 int64_t rtoh_rt_num_nodes(const RayTracerBVH* rt) { return (int64_t)rt->numNodes(); }
 int rtoh_rt_framebuffer(const RayTracerBVH* rt, float* out, int64_t capacityFloats, int* w, int* h) {

@@ -4,12 +4,15 @@ and the legend (range, the 256 bins, the LUT) as JSON beside it.  numpy only.
 
     python3 tools/field_view.py --scene calgary --field sky --out calgary_sky.ppm
     python3 tools/field_view.py --scene sphere128 --field thickness --clip 0.5 --out cut.ppm
+    python3 tools/field_view.py --scene sphere128 --field distance --project max --out xray.ppm
 
 Scenes: sphereN (the test sphere of edge N, Camera(0.5, 0.7, 1.8)) and calgary (the shipped city grid, Camera(0.6, 0.5, 3500)).
 Fields: distance (to EMPTY, SQRT scale: how deep inside), thickness (SQRT), skeleton, labels and parts (CATEGORY), geodesic
 (through EMPTY from voxel 0, sampled in FRONT of the surface), sun (exposure along one direction) and sky (exposure over 64
 directions of the upper hemisphere: the sky view factor; both sampled in FRONT of the surface).  --clip F keeps the part of the
-grid below the fraction F of its x extent (a section through the solid)."""
+grid below the fraction F of its x extent (a section through the solid).  --project OP (max, min, mean, count, first) renders a
+projection instead (rto_project_field_host): the reduction of the field along every pixel ray through the grid, or through the
+--clip box; --window LO HI sets the values that count (for first: the threshold of an isosurface seen through walls)."""
 import argparse
 import json
 import os
@@ -94,6 +97,9 @@ def main():
     ap.add_argument("--mode", choices=("first", "closest"), default="closest")
     ap.add_argument("--clip", type=float, default=None, help="keep the grid below this fraction of its x extent")
     ap.add_argument("--flat", action="store_true", help="no Lambert shading")
+    ap.add_argument("--project", choices=("max", "min", "mean", "count", "first"), default=None,
+                    help="a projection along the pixel rays instead of a view of the surface")
+    ap.add_argument("--window", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="with --project: the values that count")
     ap.add_argument("--out", default="field_view.ppm")
     a = ap.parse_args()
     grid, cam, up = scene(a.scene)
@@ -103,17 +109,29 @@ def main():
     dx, dy, dz = grid.dims
     if a.clip is not None:
         kw["clip"] = ((0, 0, 0), (max(1, min(dx, int(round(a.clip * dx)))), dy, dz))
-    kw["mode"] = hip.QUERY_FIRST if a.mode == "first" else hip.QUERY_CLOSEST
-    view = hip.make_field_view(shade=not a.flat, miss_rgba=(0.55, 0.7, 0.9, 1.0), none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
     lut = hip.ramp_lut(HEAT)
     W, H = a.width, a.height
     f = rto.make_frame(cam.getView(), cam.getPos(), W / H, 45.0, W, H)
-    rgba, values, summary, bins = ctx.render_field_host(f, view, lut)
+    if a.project:
+        kw.pop("sample", None)
+        if a.window:
+            kw["valid"] = tuple(a.window)
+        op = {"max": hip.PROJECT_MAX, "min": hip.PROJECT_MIN, "mean": hip.PROJECT_MEAN, "count": hip.PROJECT_COUNT, "first": hip.PROJECT_FIRST}[a.project]
+        if op == hip.PROJECT_COUNT:
+            kw.update(scale=hip.SCALE_LINEAR, range=(0, 0))
+        view = hip.make_field_projection(op=op, miss_rgba=(0.55, 0.7, 0.9, 1.0), none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
+        rgba, values, _, _, _, summary, bins = ctx.project_field_host(f, view, lut, totals=False)
+        ms = list(ctx.last_projection_ms())
+    else:
+        kw["mode"] = hip.QUERY_FIRST if a.mode == "first" else hip.QUERY_CLOSEST
+        view = hip.make_field_view(shade=not a.flat, miss_rgba=(0.55, 0.7, 0.9, 1.0), none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
+        rgba, values, summary, bins = ctx.render_field_host(f, view, lut)
+        ms = list(ctx.last_field_view_ms())
     write_ppm(a.out, rgba)
     legend = {"scene": a.scene, "field": a.field, "frame": [W, H], "hits": int(summary["hits"]), "valued": int(summary["valued"]),
               "vmin": int(summary["vmin"]), "vmax": int(summary["vmax"]), "range": [int(summary["lo"]), int(summary["hi"])],
               "scale": int(view.scale), "bins": bins.tolist(), "lut_rgba": lut.view(np.uint8).reshape(256, 4).tolist(),
-              "ms": list(ctx.last_field_view_ms())}
+              "project": a.project, "ms": ms}
     with open(os.path.splitext(a.out)[0] + ".legend.json", "w") as fh:
         json.dump(legend, fh)
     print(f"{a.out}: {W}x{H}, {legend['hits']} hit pixels, {legend['valued']} with a value in [{legend['vmin']}, {legend['vmax']}], "
