@@ -336,7 +336,13 @@ int  rto_split_row_source(const rto_split_plan* plan, int row, int* part, int* l
  * tri_offset[i]..tri_offset[i+1] (numNodes+1 entries) is node i's range.  Rendering follows the reference's
  * traversal order and 512-pop cap; a leaf is hit when one of its triangles is (Moeller-Trumbore, nearest
  * t > 0 in the leaf); shading = the reference's Lambert term on the ray-facing face normal; shadow != 0 adds one
- * ray towards the light (any hit => ambient only).  stats may be NULL (pops counts both traversals). */
+ * ray towards the light (any hit => ambient only).  stats may be NULL (pops counts both traversals).
+ * Frustum state: the triangle render walks the whole array's triangle records, which a compacted array does not have.  While
+ * an rto_update_frustum(enable=1) is in force every rto_render_triangles_* entry, and rto_render_resident in its two triangle
+ * modes, fails with
+ * RTO_E_UNSUPPORTED ("render_triangles: not available while frustum culling is active")
+ * and changes nothing; after rto_update_frustum(enable=0) it renders again, bit for bit.  The triangle queries and the lit
+ * triangle render below ignore the update instead. */
 int  rto_upload_leaf_triangles(rto_context* ctx, const float* tris, int64_t num_tris, const int32_t* tri_offset);
 /* The same buffer built in HBM (replaces the CPU loop MarchingCubesRenderer::render -> localMC per leaf,
  * S/Renderer.cpp:14-36, S/OctreeVoxel.cpp:780-879): identical triangles in identical order, for the resident octree.

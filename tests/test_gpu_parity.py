@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import frustum_states as fs
 import ray_tracing_octrees_amd as rto
 from ray_tracing_octrees_amd import hip
 from conftest import Scene, assert_bit_exact, partition_row_map
@@ -576,35 +577,14 @@ def test_culled_root_with_surviving_descendants_follows_the_reference(ctx, orc, 
     kernel choice must then render what the oracle renders from the compacted array: the default kernel starts its traversal at
     the node the update recorded on the device (StartState: a leaf -> one pop; an internal node -> its descriptor), the A/B
     kernels hand the frame to the generic kernel over the compacted array."""
-    rng = np.random.default_rng(4)
-    found = None
-    for _ in range(4000):
-        dim = 16
-        gmin = rng.uniform(-60, 60, 3).astype(np.float32)
-        vs = np.float32(rng.choice([0.7, 3.3, 0.37, 1.9])) if first_survivor == "solid leaf" else np.float32(rng.uniform(0.2, 4.0))
-        for a in range(3):
-            root_mx = np.float32(np.float32(gmin[a] + np.float32(0) * vs) + np.float32(dim) * vs)
-            child_mx = np.float32(np.float32(gmin[a] + np.float32(dim // 2) * vs) + np.float32(dim // 2) * vs)
-            # the internal-node variant also needs the far quarter (x = 12, size 4) to stick out of the root: its solid leaves must survive too
-            quarter_mx = np.float32(np.float32(gmin[a] + np.float32(12) * vs) + np.float32(4) * vs)
-            if child_mx > root_mx and (first_survivor == "solid leaf" or quarter_mx > root_mx):
-                found = (gmin, vs, a, root_mx, child_mx if first_survivor == "solid leaf" else min(child_mx, quarter_mx))
-                break
-        if found:
-            break
+    rng = np.random.default_rng(fs.SEARCH_SEED)
+    found = fs.search_origin(np, rng, 16, first_survivor)
     assert found, "no grid origin / voxel size with the rounding difference found"
     gmin, vs, a, root_mx, child_mx = found
-    data = (rng.random((16, 16, 16)) < 0.35).astype(np.uint8)
     # the survivors are the root's children on the far side of `a`; the first of them in BFS order (octant 1 << a) becomes
-    # index 0 of the compacted array, where the reference's traversal starts: make it a solid leaf so that there is something to see
-    sl = [slice(0, 8)] * 3                               # data is [z][y][x]
-    sl[2 - a] = slice(8, 16)
-    if first_survivor == "solid leaf":
-        data[tuple(sl)] = 1
-    else:                                                # ... or a mixed cell (near half noise, far half solid): the traversal starts at an internal node
-        data[tuple(sl)] = (rng.random((8, 8, 8)) < 0.5).astype(np.uint8)
-        sl[2 - a] = slice(12, 16)
-        data[tuple(sl)] = 1
+    # index 0 of the compacted array, where the reference's traversal starts: a solid leaf, so that there is something to see,
+    # or a mixed cell (near half noise, far half solid): the traversal starts at an internal node
+    data = fs.rootless16_data(np, rng, a, first_survivor)
     g = orc.Grid((16, 16, 16), gmin, vs, data)
     nodes = orc.build_flat_octree(g)
     s = Scene(g, nodes)
