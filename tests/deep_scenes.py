@@ -11,6 +11,14 @@ Scenes:
     the far corner whose corner voxel is carved out, so the corner's cells are mixed down to size 2.  A ray that meets that
     cell descends through child 7 at every level and holds 7 d + 1 stack entries there: 134 at d = 19, 141 at d = 20.
   * "thin": a dense grid of 3 * 2^(d-2) x 3 x 2 voxels with small blobs along x: depth d, a few MB, for the builders.
+  * "bar": a grid of X x c x c voxels, X = 3 * 2^(d-2), c = 16 up to depth 16 and 4 from depth 17 on (at most 12.6 M voxels),
+    that holds four cell-aligned solid c-cubes over its whole cross-section, at x = 0, N/2 - c, N/2 + 2c and X - c (N = 2^d),
+    and six single voxels one empty voxel away from their -x and +x faces, so that the cells next to the cubes are mixed down to
+    size 1.
+    The cubes are leaves of size c: the only deep scenes where a ray ends inside a solid leaf larger than 2 voxels, at x up
+    to 2^20.  The tree is built from the solid coordinates; the dense array `data` is made when first asked for.  Two
+    cameras, each orbiting one cube (the second, which has grid on both sides along x, and the last, whose +x face is the
+    grid's) at 2.5 c voxels.
 Grid kinds: "frac" (origin -0.5, voxel 2^-d: every node plane exact), "far" (voxel 1, origin of sceneCache.bin: exact,
 planes up to 2^20 from the origin), "tenth" (voxel 0.1, origin 0.3: the general child test).
 """
@@ -82,6 +90,24 @@ def _block(corner, size):
     return np.asarray(corner, np.int64) + g
 
 
+def bar_edge(d):
+    """The edge c of a bar scene's cubes and cross-section."""
+    return 16 if d <= 16 else 4
+
+
+def bar_solid(d):
+    """(solid voxels (n, 3), the four cubes' low corners, c) of the bar geometry at depth d."""
+    N, c = 1 << d, bar_edge(d)
+    X = 3 * N // 4
+    xs = (0, N // 2 - c, N // 2 + 2 * c, X - c)
+    singles = np.array([[c + 1, 1, 1], [N // 2 + 1, 1, 2], [N // 2 - c - 2, 2, 1], [N // 2 + 2 * c - 2, 2, 2], [N // 2 + 3 * c + 1, 0, 3],
+                        [X - c - 2, 1, 1]], np.int64)
+    return np.concatenate([_block((x, 0, 0), c) for x in xs] + [singles]), xs, c
+
+
+_bar_data = {}
+
+
 def grid_frame(kind, d):
     """(grid_min float32[3], voxel float32) of a grid kind at depth d."""
     if kind == "frac":
@@ -97,6 +123,7 @@ class DeepScene:
     def __init__(self, kind, d, geometry="spine"):
         self.kind, self.depth, self.geometry = kind, d, geometry
         self.min, self.voxel = grid_frame(kind, d)
+        self._data = None
         N = 1 << d
         if geometry == "spine":
             self.dims = (N, N, N)
@@ -109,7 +136,13 @@ class DeepScene:
             solid = np.unique(np.concatenate([corner] + balls), axis=0)
             big = ((N // 4, 0, 0, N // 4), (N // 2, N // 2, 0, N // 8))    # cell-aligned solid cubes (x, y, z, edge)
             self.nodes = build_octree(np.unique(np.concatenate([solid] + list(blocks)), axis=0), self.dims, big)
-        else:
+        elif geometry == "bar":
+            solid, xs, c = bar_solid(d)
+            self.dims = (3 * N // 4, c, c)
+            self.edge, self.blocks = c, xs
+            self.blobs = [np.array([[x + (c - 1) / 2, (c - 1) / 2, (c - 1) / 2]]) for x in xs]       # + 0.5: the cubes' centres
+            self.nodes = build_octree(solid, self.dims)
+        elif geometry == "thin":
             self.dims = (3 * N // 4, 3, 2)
             data = np.zeros(self.dims[::-1], np.uint8)                                 # (z, y, x)
             xs = [3, N // 2 - 1, N // 2 + 5, 3 * N // 4 - 2]
@@ -121,15 +154,40 @@ class DeepScene:
             z, y, x = np.nonzero(data)
             self.blobs = [np.array([[x0, 1, 1]]) for x0 in xs]
             self.nodes = build_octree(np.stack([x, y, z], 1), self.dims)
+        else:
+            raise KeyError(geometry)
+
+    @property
+    def data(self):
+        """The dense (z, y, x) uint8 array; a bar scene's is made on first use and shared by the grid kinds of a depth."""
+        if self._data is None and self.geometry == "bar":
+            if self.depth not in _bar_data:
+                data = np.zeros(self.dims[::-1], np.uint8)
+                solid = bar_solid(self.depth)[0]
+                data[solid[:, 2], solid[:, 1], solid[:, 0]] = 1
+                _bar_data[self.depth] = data
+            return _bar_data[self.depth]
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        self._data = value
 
     def world(self, p):
         return self.min.astype(np.float64) + np.asarray(p, np.float64) * float(self.voxel)
 
     def cameras(self, orc):
         """(name, view, pos) triples: 9 voxels from the first blob (the corner one of a spine scene), 16 from the second (rays
-        reach level d in both), and one far away that sees the whole root box."""
+        reach level d in both), and one far away that sees the whole root box.  A bar scene: "block1" and "block3", each 2.5 c
+        voxels from the centre of one cube."""
         N = 1 << self.depth
         out = []
+        if self.geometry == "bar":
+            for i in (1, 3):
+                cam = orc.Camera(0.7, 0.5, float(np.float32(2.5 * self.edge * float(self.voxel))))
+                cam.set_target(*[float(v) for v in self.world(self.blobs[i][0] + 0.5).astype(np.float32)])
+                out.append((f"block{i}", cam.get_view(), cam.get_pos()))
+            return out
         for i, (th, ph, r) in enumerate(((0.7, 0.5, 9.0), (2.4, -0.35, 16.0))):
             centre = self.blobs[i].mean(0) + 0.5
             cam = orc.Camera(th, ph, float(np.float32(r * float(self.voxel))))

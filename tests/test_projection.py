@@ -6,7 +6,8 @@ against the statement, bit for bit and with no pixel excluded; the brick table o
 device form; the lifecycle; every refusal; a full sphere without the statement; the drop-in class.
 
 Grids: the lifecycle suite's 40 x 12 x 12, a 13 x 9 x 5 grid (no dim a multiple of 8, z below one brick), a 32^3 grid with a 16^3
-block, and an 8^3 grid (one brick)."""
+block, and an 8^3 grid (one brick); and, for k_project_bricks' runs of 64 voxels along x, seven grids of 65 to 200 voxels a
+row (LONG below) with cameras of their own."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +17,7 @@ import re
 import numpy as np
 import pytest
 
+import distance_ref as dr
 import projection_model as pm
 import projection_ref as pr
 from conftest import SPHERE_CAM, make_camera
@@ -435,6 +437,163 @@ def test_projection_kernels_keep_their_budgets():
     assert re.search(r"k_project_bricks[^.]*\b%d VGPRs" % BRICK_VGPRS, sec) and re.search(r"k_project_march[^.]*\b%d VGPRs" % MARCH_VGPRS, sec)
 
 
+# ---------------------------------------------------------------- long rows: more than one run of 8 bricks along x
+TENTH = (np.full(3, 0.3, np.float32), np.float32(0.1))
+# name: (dimX, dimY, dimZ, (gridMin, voxelSize)).  k_project_bricks gives one wave to a run of 8 bricks (64 voxels) along x:
+# "long65" the second run holds one column, "long72" exactly one brick (nbx = 9), "long100" five bricks, the last of four
+# columns (nbx = 13; 6 waves, so the last workgroup is half empty), "long128" two whole runs (nbx = 16), "long130" three runs,
+# the last of two columns (nbx = 17), "long200" four runs over one row of bricks (nbx = 25); "long130-tenth" is long130 at
+# voxel 0.1, origin 0.3.
+LONG = {"long65": (65, 9, 5, (GMIN, VOX)), "long72": (72, 12, 9, (GMIN, VOX)), "long100": (100, 5, 17, (GMIN, VOX)),
+        "long128": (128, 9, 5, (GMIN, VOX)), "long130": (130, 9, 9, (GMIN, VOX)), "long200": (200, 5, 3, (GMIN, VOX)),
+        "long130-tenth": (130, 9, 9, TENTH)}
+LONG_OPS = (pr.MAX, pr.MIN, pr.COUNT, pr.FIRST)     # the table's two keys; its "no valued voxel" skip
+LW, LH = 24, 16
+_LONG = {}
+
+
+def _long_grid(name):
+    """All solid but for the plane x = 0, a tunnel along x through the boundary of the first two runs and one voxel at the far
+    end: the distance to EMPTY changes along the whole row, up to 29^2 in the 130-voxel grids."""
+    dx, dy, dz, _ = LONG[name]
+    g = np.ones((dz, dy, dx), np.uint8)
+    g[:, :, 0] = 0
+    g[dz // 2, dy // 2, 58:min(70, dx)] = 0
+    g[0, 0, dx - 1] = 0
+    return g
+
+
+def _long_volume(name):
+    """A caller's volume whose valued voxels all lie at x >= 64: a frame changes when a table entry of a later run is wrong."""
+    dx, dy, dz, _ = LONG[name]
+    idx = np.arange(dx * dy * dz, dtype=np.int64).reshape(dz, dy, dx)
+    return np.where((idx % dx >= 64) & ((idx * 7 + idx // dx) % 5 != 0), (idx * 37) % 101, -1).astype(np.int32)
+
+
+def _x_view(pos, sign):
+    """A view that looks along +x or -x with y to the right and the world's -z or z up; _diag_view's construction."""
+    f = np.array([sign, 0, 0], np.float32)
+    r = np.array([0, 1, 0], np.float32)
+    R = np.stack([r, np.cross(r, f).astype(np.float32), -f]).astype(np.float32)
+    V = np.eye(4, dtype=np.float32)
+    V[:3, :3] = R
+    V[:3, 3] = -(R @ pos)
+    return V.T.reshape(16).copy()
+
+
+def _long_frames(orc, name):
+    """[(camera, view, pos, rays, the statement's walks)] of a long grid, made once.  "end": 6 voxels beyond the +x face, looking
+    along -x.  "inside": in the grid at (60.5, 0.3, 0.2), looking along +x: the central ray that leans towards +y and +z
+    stays in a cross-section of 5 x 3 voxels for 100 voxels.  "plane": on the grid plane x = 64, looking along +x (every
+    plane T of that axis up to 64 is <= 0).  "orbit": the suite's oblique camera 12 voxels from the point (max(64, dimX / 2), dimY /
+    2, dimZ / 2); at the suite's usual radius it sees next to nothing of such a grid."""
+    if name not in _LONG:
+        dx, dy, dz, (gmin, vox) = LONG[name]
+        at = lambda x, y, z: (gmin + (np.array([x, y, z], np.float32) * vox).astype(np.float32)).astype(np.float32)
+        cams = []
+        pos = at(dx + 6, dy / 2 + 0.3, dz / 2 + 0.2)
+        cams.append(("end", _x_view(pos, -1), pos))
+        pos = at(60.5, 0.3, 0.2)
+        cams.append(("inside", _x_view(pos, 1), pos))
+        pos = at(64, dy / 2 - 0.3, dz / 2 + 0.2)
+        cams.append(("plane", _x_view(pos, 1), pos))
+        cam = orc.Camera(0.6, 0.45, float(np.float32(12 * float(vox))))
+        cam.set_target(*[float(v) for v in at(max(64, dx / 2), dy / 2, dz / 2)])
+        cams.append(("orbit", cam.get_view(), cam.get_pos()))
+        out = []
+        for cname, view, pos in cams:
+            rd = _rays(orc, view, pos, LW, LH)
+            out.append((cname, view, pos, rd, pr.walks(gmin, vox, (dx, dy, dz), pos, rd)))
+        _LONG[name] = out
+    return _LONG[name]
+
+
+def _long_runs(hip, cname, cells, vol, field):
+    """[(projection, caller volume or None, the statement's frame)] of a long grid's frame: MAX, MIN, COUNT and FIRST of the x >=
+    64 volume, MAX of the distance to EMPTY.  Each has at least 50 valued pixels and, but for FIRST (one value may lead every
+    walk) and the distance from the "inside" camera (its own voxel holds the maximum of every walk), two LUT indices."""
+    runs = [(_proj(hip, hip.FIELD_CALLER, op, scale=hip.SCALE_SQRT if op == pr.COUNT else hip.SCALE_LINEAR), vol) for op in LONG_OPS]
+    runs.append((_proj(hip, hip.FIELD_DISTANCE, pr.MAX, scale=hip.SCALE_SQRT, valid=(1, 0x7ffffffe)), None))
+    out = []
+    for v, volume in runs:
+        want = pr.frame_of(cells, LW, LH, field if volume is None else volume, v, _lut())
+        assert want[5]["valued"] >= 50, (cname, v.source, v.op, want[5])
+        if not (v.op == pr.FIRST or (volume is None and cname == "inside")):
+            assert not pr.degenerate(want[1], v), (cname, v.source, v.op, want[5])
+        out.append((v, volume, want))
+    return out
+
+
+def _crosses_63_64(c):
+    return any({a[0], b[0]} == {63, 64} for a, b in zip(c, c[1:]))
+
+
+@pytest.mark.parametrize("name", list(LONG))
+def test_long_row_frames_bite_and_feel_the_later_runs(orc, name):
+    """On the statement alone.  Every frame of a long grid: at least 100 pixels visit something and at least 50 walks hold a
+    voxel with x >= 64 (what a later run's table entries cover).  Over the grid's four frames: at least 50 walks cross x = 63 |
+    64 and one is at least dimX / 2 voxels long.  (No single camera can do all four on every grid: a walk from the plane x =
+    64 never crosses it, and in a 9 x 5 cross-section a walk that starts before x = 32 meets column 64 on a pixel or two.)  The
+    "plane" camera stands on the plane, the "inside" camera in the grid.
+    Sensitivity: tests/projection_model.py's march with a table that calls every brick of the runs >= 1 empty (skip = bx >= 8)
+    gives another frame than the statement under every op, on at least 50 pixels of every frame."""
+    dx, dy, dz, (gmin, vox) = LONG[name]
+    dim = (dx, dy, dz)
+    vol = _long_volume(name)
+    field = dr.field(_long_grid(name), dr.SET_EMPTY)
+    hip = _hip()
+    frames = _long_frames(orc, name)
+    for cname, view, pos, rd, cells in frames:
+        assert sum(bool(c) for c in cells) >= 100, (name, cname)
+        later = [any(x >= 64 for x, _, _ in c) for c in cells]
+        assert sum(later) >= 50, (name, cname, sum(later))
+        q = (pos - gmin) / vox
+        if cname in ("inside", "plane"):
+            assert all(0 <= q[a] < dim[a] for a in range(3)), (name, cname)
+        if cname == "plane":
+            assert pos[0] == np.float32(gmin[0] + np.float32(np.float32(64) * vox))
+            assert {c[0][0] for c in cells if c} == {64}
+        skipped = [pm.march(gmin, vox, dim, pos, d, skip=lambda b: b[0] >= 8)[0] if far else c for d, c, far in zip(rd, cells, later)]
+        assert all(s == [v for v in c if v[0] < 64] for s, c in zip(skipped, cells))
+        for v, volume, want in _long_runs(hip, cname, cells, vol, field):
+            if volume is None:                     # the distance's maximum may lie in the first run: no promise
+                continue
+            blind = pr.frame_of(skipped, LW, LH, volume, v, _lut())
+            assert (want[1] != blind[1]).sum() >= 50 and want[0].tobytes() != blind[0].tobytes(), (name, cname, v.source, v.op)
+    assert sum(_crosses_63_64(c) for _, _, _, _, cells in frames for c in cells) >= 50
+    assert max(len(c) for _, _, _, _, cells in frames for c in cells) >= dx / 2
+    assert ((dx + 7) // 8 + 7) // 8 >= 2                                      # the kernel's runsX
+
+
+@pytest.mark.parametrize("name", list(LONG))
+def test_long_row_frames_against_the_host_form(orc, name):
+    """host/Projection through host_capi on every pixel ray of the long grids' frames: the statement's voxels in the statement's
+    order, and its value, voxel, sum and count under every op on the x >= 64 volume."""
+    from ray_tracing_octrees_amd import host
+    L = host.load()
+    dx, dy, dz, (gmin, vox) = LONG[name]
+    vol = np.ascontiguousarray(_long_volume(name))
+    dims = np.array([dx, dy, dz], np.int32)
+    gm = np.ascontiguousarray(gmin, np.float32)
+    blo, bhi = np.zeros(3, np.int32), dims.copy()
+    cap = dx + dy + dz + 4
+    out = np.zeros((cap, 3), np.int32)
+    res = np.zeros(4, np.int64)
+    valued = 0
+    for cname, view, pos, rd, cells in _long_frames(orc, name):
+        oo = np.ascontiguousarray(pos, np.float32)
+        for d, want in zip(rd, cells):
+            dd = np.ascontiguousarray(d, np.float32)
+            n = L.rtoh_projection_walk(gm.ctypes.data, C.c_float(float(vox)), dims.ctypes.data, oo.ctypes.data, dd.ctypes.data, blo.ctypes.data,
+                                       bhi.ctypes.data, out.ctypes.data, cap)
+            assert n == len(want) and [tuple(r) for r in out[:n].tolist()] == want, (name, cname, d)
+            for op in pr.OPS:
+                L.rtoh_projection_reduce(vol.ctypes.data, dims.ctypes.data, out.ctypes.data, n, op, 0, 0x7ffffffe, res.ctypes.data)
+                assert tuple(res.tolist()) == pr.reduce(want, vol, op, 0, 0x7ffffffe), (name, cname, op)
+            valued += res[3] > 0
+    assert valued >= 200
+
+
 # ================================================================ GPU
 _WALKS = {}
 
@@ -593,6 +752,36 @@ def test_gpu_caller_volumes(ctx, orc, name):
                 ctx.debug_set_projection_table(table)
                 for totals in (True, False):
                     _same(ctx.project_field_host(f, v, _lut(), vol, totals=totals), want, f"{name} op {op} table {table} totals {totals}")
+    finally:
+        ctx.debug_set_projection_table(True)
+
+
+@gpu
+@pytest.mark.parametrize("name", list(LONG))
+def test_gpu_long_rows_equal_the_statement(ctx, orc, name):
+    """Rows of more than 64 voxels, so that k_project_bricks runs a second, third and fourth wave along x, whole and partial, and
+    the march reads their records: every output against the statement, with the brick table and without it, with the totals and
+    without them.  A caller's volume valued only at x >= 64 (a missing or wrong record of a later run empties or dims the frame)
+    under MAX, MIN, COUNT and FIRST, and the resident distance to EMPTY under MAX; the four cameras of _long_frames, whose
+    statement frames test_long_row_frames_bite_and_feel_the_later_runs holds to their conditions."""
+    hip = _hip()
+    dx, dy, dz, (gmin, vox) = LONG[name]
+    g = _long_grid(name)
+    vol = _long_volume(name)
+    ctx.set_kernel(hip.KERNEL_AUTO)
+    ctx.build_octree(g, gmin, vox)
+    field = ctx.distance_field(hip.SET_EMPTY)[0]
+    assert np.array_equal(field, dr.field(g, dr.SET_EMPTY))
+    try:
+        for cname, view, pos, rd, cells in _long_frames(orc, name):
+            f = _frame(view, pos, LW, LH)
+            assert sum(any(x >= 64 for x, _, _ in c) for c in cells) >= 50
+            for v, volume, want in _long_runs(hip, cname, cells, vol, field):
+                for table in (True, False):
+                    ctx.debug_set_projection_table(table)
+                    for totals in (True, False):
+                        _same(ctx.project_field_host(f, v, _lut(), volume, totals=totals), want,
+                              f"{name} {cname} source {v.source} op {v.op} table {table} totals {totals}")
     finally:
         ctx.debug_set_projection_table(True)
 
