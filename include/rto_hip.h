@@ -1516,8 +1516,100 @@ int  rto_project_field_host(rto_context* ctx, const rto_frame* frame, const rto_
  * frame was stream-captured or launched after rto_timing_begin(ctx, -1).  Without the table the first is the empty interval. */
 int  rto_last_projection_ms(const rto_context* ctx, float ms[3]);
 /* Developer aid in the style of RTO_KERNEL_GENERIC: 0 = the march consults no brick table (and none is built), 1 = it does
- * (default).  The same loop runs either way and no output depends on it: for A/B timing and for the test that says so. */
+ * (default).  The same loop runs either way and no output depends on it: for A/B timing and for the test that says so.  The
+ * tables of rto_composite_field_* follow the same switch. */
 int  rto_debug_set_projection_table(rto_context* ctx, int enabled);
+
+/* ---- field compositing ------------------------------------------------------
+ * A frame from the renders' camera in which an int32 volume of the resident grid is seen through: every valued voxel a pixel ray
+ * crosses takes colour and opacity from a LUT entry, the entries are composited front to back, and the march can be stopped by
+ * the grid's solids.  This is the reference's VolumeRaycastRenderer -- a transfer function, front-to-back
+ * alpha compositing, termination -- in exact integers.  The octree is not walked.  Floats decide which voxels are visited and, at
+ * the very end, the output colour; everything in between is unsigned 32-bit integers.  All float arithmetic is float32, one IEEE
+ * operation per operator, in the order written.  Rule:
+ *   ray, planes, still, events, states, visited
+ *             the field projections', word for word; [lo, hi) is the clip box, or the grid without one.  rto_update_frustum is
+ *             ignored.
+ *   valued    a voxel whose value lies in [valid_lo, valid_hi].
+ *   index     the field views' index of the value v of a valued voxel under `scale` and the range (range_lo, range_hi), which
+ *             must be given: a composite has no auto range (every voxel's colour depends on it, so it has to be known before the
+ *             march).  LINEAR and SQRT need range_lo < range_hi; CATEGORY ignores the range.
+ *   entry     the LUT entry at that index is the bytes r, g, b, a in memory order; a' = a + (a >> 7) is 0 .. 256 (a byte of 255 is
+ *             fully opaque).  A voxel contributes when it is valued and a' != 0.
+ *   composite the state is T = 65536 (the transmittance, Q16), R = G = B = 0, count = 0.  For every contributing voxel in walk
+ *             order: c = (T * a') >> 8; R += c * r; G += c * g; B += c * b; T -= c; count += 1.  T * a' <= 2^24, and R, G and B
+ *             are at most 65536 * 255 = 16,711,680 < 2^24: their conversion to float32 is exact.
+ *   end       the walk ends at whichever comes first.  Occluded: with occlude != 0, at the first visited voxel whose byte in the
+ *             resident grid is 1 (FILLED), before that voxel can contribute.  Saturated: after the first contribution that leaves
+ *             T <= stop_q16 (0 .. 65535; with 0 the walk ends only when nothing more can be seen).  Through: when the visited voxels
+ *             run out.
+ *   outputs   d_transmittance (uint32): T, 65536 for a miss (a ray that visits no voxel).  d_first: the linear index (z * dimY +
+ *             y) * dimX + x of the first contributing voxel, -1 without one.  d_stops: the occluding or the saturating voxel, -1
+ *             when the walk went through or missed.  d_counts: the contributions.  Each may be NULL.
+ *   colour    bg is d_under[pix] (a float4 per pixel) when d_under is given, and the four formulas below then hold for every pixel,
+ *             a miss with its T = 65536 and R = G = B = 0 included.  d_under may be d_rgba itself: each pixel is read and then
+ *             written by its own lane.  Without d_under, bg is background_rgba for a pixel that visits a voxel, and a miss is
+ *             miss_rgba, unblended.  tf = (float)T / 65536.0f; out.r = (float)R / 16711680.0f + tf * bg.r, likewise g and b;
+ *             out.a = (float)(65536 - T) / 65536.0f + tf * bg.a.
+ *   summary   rto_composite_summary: the pixels that visit a voxel, that have a contribution, and whose walk ended saturated or
+ *             occluded.  It is made on the device, with no host step.
+ * With an all-opaque LUT (every a = 255) a pixel's colour is therefore the LUT colour of its first valued voxel, bit for bit the
+ * colour rto_project_field_* gives it under RTO_PROJECT_FIRST (65536 r / 16711680 and r / 255 are the same real number, both
+ * divisions round correctly, and T = 0 adds 0 * bg).  With a LUT whose alpha is nowhere 0 and never 255, stop_q16 = 0 and no
+ * occlusion, d_counts and d_first are the projections' d_counts and FIRST's d_voxels.
+ * The march skips 8 x 8 x 8 bricks through the projections' table of each brick's largest and smallest valued value (a brick with
+ * no valued voxel, or, under LINEAR and SQRT, with no LUT entry of a' != 0 between the indices of those two values) and, with
+ * occlude, a second table that says whether a brick holds a FILLED voxel; both are rebuilt by every call.  They change no output:
+ * rto_debug_set_projection_table(ctx, 0) switches off every table the composite consults too.
+ * Sources are the field views'.  Needs a resident grid of fewer than 2^31 voxels; the tree need not be canonical.
+ * Errors, each leaving the context untouched, checked in this order: RTO_E_INVALID: a NULL frame, composite, LUT or rgba; a
+ * misaligned buffer (d_under and d_rgba 16 bytes, d_summary 8, d_lut, d_volume, d_transmittance, d_first, d_stops and d_counts
+ * 4); an unknown source or scale; reserved != 0; valid_lo > valid_hi or valid_lo <= INT32_MIN + 1; LINEAR or SQRT with range_lo
+ * >= range_hi; stop_q16 outside 0 .. 65535; occlude other than 0 or 1; a width or height below 1; a frame beyond the lit render's
+ * limits; CALLER without a volume, or a volume with another source.  RTO_E_NO_OCTREE: nothing uploaded.  RTO_E_UNSUPPORTED: no
+ * resident grid (rto_upload_octree), then a grid of 2^31 voxels or more.  RTO_E_INVALID: a clip box with clip_lo[a] < 0,
+ * clip_hi[a] > dim[a] or clip_lo[a] >= clip_hi[a]; last, a named source that is not resident, in its readers' words.
+ * The device form is asynchronous on hip_stream.  Its work buffers (the projections' brick table, the solid table and the summary
+ * block) live on the context under the field views' rules: a larger grid than any before allocates, and then must not be stream-
+ * captured; one set per context, so composites, projections and field views on different streams of one context must not run at
+ * the same time. */
+typedef struct rto_field_composite {    /* 112 bytes */
+    int32_t  source;                /* RTO_FIELD_* */
+    int32_t  scale;                 /* RTO_SCALE_* */
+    int32_t  valid_lo, valid_hi;    /* the window of valued voxels; defaults 0 and 0x7ffffffe; valid_lo > INT32_MIN + 1 */
+    int32_t  range_lo, range_hi;    /* LINEAR and SQRT: range_lo < range_hi; there is no auto range */
+    int32_t  clip;                  /* != 0: the section box below applies */
+    int32_t  clip_lo[3], clip_hi[3];   /* voxel indices, x y z: 0 <= clip_lo < clip_hi <= dim */
+    int32_t  stop_q16;              /* 0 .. 65535: the walk ends once T <= stop_q16 */
+    int32_t  occlude;               /* 1: the walk ends at the first FILLED voxel; 0: the volume is seen through the solids */
+    float    background_rgba[4];    /* under a pixel that visits a voxel, when d_under is NULL */
+    float    miss_rgba[4];          /* a pixel that visits none, when d_under is NULL */
+    int32_t  reserved[5];           /* 0 */
+} rto_field_composite;
+typedef struct rto_composite_summary {  /* 32 bytes */
+    int64_t  visited;               /* pixels that visit a voxel */
+    int64_t  contributing;          /* pixels with at least one contribution */
+    int64_t  saturated;             /* pixels whose walk ended with T <= stop_q16 */
+    int64_t  occluded;              /* pixels whose walk ended at a FILLED voxel */
+} rto_composite_summary;
+
+int  rto_composite_field_device(rto_context* ctx, const rto_frame* frame, const rto_field_composite* composite,
+                                const uint32_t* d_lut /* 256 */, const int32_t* d_volume /* RTO_FIELD_CALLER only */,
+                                const void* d_under /* float4 per pixel, 16-byte aligned; may be NULL, may be d_rgba */,
+                                void* d_rgba /* float4 per pixel, 16-byte aligned */, uint32_t* d_transmittance /* may be NULL */,
+                                int32_t* d_first /* may be NULL */, int32_t* d_stops /* may be NULL */, int32_t* d_counts /* may be NULL */,
+                                rto_composite_summary* d_summary /* may be NULL */, void* hip_stream);
+/* The same with host buffers (the LUT and a caller's volume too); synchronous on the context's stream.  host_under may be
+ * host_rgba. */
+int  rto_composite_field_host(rto_context* ctx, const rto_frame* frame, const rto_field_composite* composite, const uint32_t* lut /* 256 */,
+                              const int32_t* volume /* RTO_FIELD_CALLER only */, const float* host_under /* may be NULL */,
+                              float* host_rgba, uint32_t* host_transmittance /* may be NULL */, int32_t* host_first /* may be NULL */,
+                              int32_t* host_stops /* may be NULL */, int32_t* host_counts /* may be NULL */,
+                              rto_composite_summary* host_summary /* may be NULL */);
+/* Device time of the last composite in ms (the tables, the march, the summary's fold); waits for that frame.  -1: not run, or the
+ * frame was stream-captured or launched after rto_timing_begin(ctx, -1).  Without tables, or without d_summary, the interval is
+ * empty. */
+int  rto_last_composite_ms(const rto_context* ctx, float ms[3]);
 
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */

@@ -181,6 +181,14 @@ struct rto_context {
     bool pjTimed = false;
     bool pjTable = true;
 
+    // field compositing (rto_composite.inc): the solid table of the call in flight (one byte per brick, cpSolidCap of them), the
+    // summary block, and the events around the tables, the march and the fold of the last frame (cpTimed: they were recorded)
+    unsigned char* d_cpSolid = nullptr;
+    size_t cpSolidCap = 0;
+    void* d_cpSum = nullptr;
+    hipEvent_t cpEv[4] = { nullptr, nullptr, nullptr, nullptr };
+    bool cpTimed = false;
+
     // mesh extraction (rto_mesh.inc): the last mesh (a snapshot the context owns) and the first node of every tree level
     float4* d_mesh = nullptr;
     int* d_meshNode = nullptr;
@@ -425,6 +433,9 @@ void rto_destroy(rto_context* c) {
     for (hipEvent_t e : c->fvEv) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_pjBricks);
     for (hipEvent_t e : c->pjEv) if (e) (void)hipEventDestroy(e);
+    (void)hipFree(c->d_cpSolid);
+    (void)hipFree(c->d_cpSum);
+    for (hipEvent_t e : c->cpEv) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_mesh);
     (void)hipFree(c->d_meshNode);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
@@ -3047,6 +3058,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_lit.inc"
 #include "rto_field_view.inc"
 #include "rto_project.inc"
+#include "rto_composite.inc"
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
 #include "rto_region.inc"

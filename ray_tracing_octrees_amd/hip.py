@@ -62,6 +62,7 @@ SYMBOLS = (
     "rto_last_parts_ms", "rto_debug_parts", "rto_debug_parts_capacity",
     "rto_render_field_device", "rto_render_field_host", "rto_last_field_view_ms",
     "rto_project_field_device", "rto_project_field_host", "rto_last_projection_ms", "rto_debug_set_projection_table",
+    "rto_composite_field_device", "rto_composite_field_host", "rto_last_composite_ms",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -134,6 +135,8 @@ FIELD_PIXEL_MISS, FIELD_PIXEL_NONE = -2**31, -2**31 + 1
 FIELD_VIEW_SUMMARY_DTYPE = np.dtype([("hits", "<i8"), ("valued", "<i8"), ("vmin", "<i4"), ("vmax", "<i4"), ("lo", "<i4"), ("hi", "<i4")])
 # field projections (rto_project_field_*): RTO_PROJECT_*
 PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN, PROJECT_COUNT, PROJECT_FIRST = 0, 1, 2, 3, 4
+# field compositing (rto_composite_field_*): struct rto_composite_summary
+COMPOSITE_SUMMARY_DTYPE = np.dtype([("visited", "<i8"), ("contributing", "<i8"), ("saturated", "<i8"), ("occluded", "<i8")])
 AO_MAX_SAMPLES = 64      # RTO_AO_MAX_SAMPLES: the lit render's AO rays per pixel at most
 COMM_ID_BYTES = 128
 RESIDENT_OCTREE, RESIDENT_TRIANGLES, RESIDENT_TRIANGLES_SHADOW = 0, 1, 2
@@ -301,6 +304,34 @@ def make_field_projection(source, op=PROJECT_MAX, scale=SCALE_LINEAR, valid=(0, 
     for k in (0, 1, 2, 3):
         v.miss_rgba[k] = _f(miss_rgba[k])
         v.none_rgba[k] = _f(none_rgba[k])
+    return v
+
+
+# struct rto_field_composite (112 bytes): field compositing (rto_composite_field_*)
+class FieldComposite(C.Structure):
+    _fields_ = [("source", C.c_int32), ("scale", C.c_int32), ("valid_lo", C.c_int32), ("valid_hi", C.c_int32),
+                ("range_lo", C.c_int32), ("range_hi", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_int32 * 3),
+                ("clip_hi", C.c_int32 * 3), ("stop_q16", C.c_int32), ("occlude", C.c_int32), ("background_rgba", C.c_float * 4),
+                ("miss_rgba", C.c_float * 4), ("reserved", C.c_int32 * 5)]
+
+
+def make_field_composite(source, scale=SCALE_LINEAR, valid=(0, 0x7ffffffe), range=(0, 1), clip=None, stop_q16=0, occlude=False,
+                         background_rgba=(0.0, 0.0, 0.0, 0.0), miss_rgba=(0.0, 0.0, 0.0, 0.0)) -> FieldComposite:
+    """An rto_field_composite.  range: (lo, hi) with lo < hi under LINEAR and SQRT (there is no auto range); clip: None or ((x0,
+    y0, z0), (x1, y1, z1)) in voxel indices; stop_q16: 0 .. 65535, the transmittance (of 65536) at which a ray ends; occlude: the
+    ray ends at the first FILLED voxel."""
+    v = FieldComposite()
+    v.source, v.scale = int(source), int(scale)
+    v.valid_lo, v.valid_hi = int(valid[0]), int(valid[1])
+    v.range_lo, v.range_hi = int(range[0]), int(range[1])
+    v.clip = 0 if clip is None else 1
+    for a in (0, 1, 2):
+        v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
+        v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
+    v.stop_q16, v.occlude = int(stop_q16), int(occlude)
+    for k in (0, 1, 2, 3):
+        v.background_rgba[k] = _f(background_rgba[k])
+        v.miss_rgba[k] = _f(miss_rgba[k])
     return v
 
 
@@ -635,6 +666,9 @@ def load():
     L.rto_project_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldProjection), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rto_last_projection_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_debug_set_projection_table.argtypes = [vp, C.c_int]
+    L.rto_composite_field_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldComposite), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rto_composite_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldComposite), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rto_last_composite_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1102,6 +1136,55 @@ class Context:
     def debug_set_projection_table(self, enabled: bool):
         """rto_debug_set_projection_table: whether the march consults the brick table (default) or walks every voxel."""
         self._check(self._L.rto_debug_set_projection_table(self._h, 1 if enabled else 0))
+
+    # -- field compositing -----------------------------------------------------
+    def composite_field_host(self, frame: Frame, composite: FieldComposite, lut, volume=None, under=None, in_place: bool = False):
+        """A frame in which an int32 volume of the resident grid is seen through: LUT colour and opacity per valued voxel,
+        composited front to back along the pixel rays (rto_composite_field_host).  lut: 256 uint32 (ramp_lut; the alpha byte is
+        the voxel's opacity); volume: the (dimZ, dimY, dimX) int32 array of FIELD_CALLER, None for every other source; under: an (H,
+        W, 4) float32 frame to composite over, None for the composite's background_rgba and miss_rgba; in_place: the frame is
+        composited over `under` in one buffer, on the host and on the device.  Returns (rgba (H, W, 4) float32, transmittance (H, W)
+        uint32, first (H, W) int32, stops (H, W) int32, counts (H, W) int32, summary (one COMPOSITE_SUMMARY_DTYPE record))."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("composite_field_host: the LUT has 256 entries")
+        if volume is not None:
+            volume = np.ascontiguousarray(volume, dtype=np.int32)
+            dims = (C.c_int * 3)()
+            if self._L.rto_download_voxels(self._h, None, 0, dims) == RTO_OK and volume.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"composite_field_host: the volume must be {(dims[2], dims[1], dims[0])}, not {volume.shape}")
+        shape = (frame.height, frame.width)
+        if under is not None:
+            under = np.array(under, dtype=np.float32, order="C") if in_place else np.ascontiguousarray(under, dtype=np.float32)
+            if under.shape != shape + (4,):
+                raise ValueError(f"composite_field_host: under must be {shape + (4,)}, not {under.shape}")
+        elif in_place:
+            raise ValueError("composite_field_host: in_place needs a frame to composite over")
+        rgba = under if in_place else np.empty(shape + (4,), np.float32)
+        trans = np.empty(shape, np.uint32)
+        first, stops, counts = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.int32)
+        summary = np.zeros(1, COMPOSITE_SUMMARY_DTYPE)
+        self._check(self._L.rto_composite_field_host(self._h, C.byref(frame), C.byref(composite), lut.ctypes.data,
+                                                     volume.ctypes.data if volume is not None else None,
+                                                     under.ctypes.data if under is not None else None, rgba.ctypes.data,
+                                                     trans.ctypes.data, first.ctypes.data, stops.ctypes.data, counts.ctypes.data,
+                                                     summary.ctypes.data))
+        return rgba, trans, first, stops, counts, summary[0]
+
+    def composite_field_device(self, frame: Frame, composite: FieldComposite, d_lut: int, d_rgba: int, d_volume: int = 0,
+                               d_under: int = 0, d_transmittance: int = 0, d_first: int = 0, d_stops: int = 0, d_counts: int = 0,
+                               d_summary: int = 0, stream: int = 0):
+        """Asynchronous: the composite into d_rgba (W*H*16 bytes), over d_under (the same size; it may be d_rgba) when given, and,
+        where given, the transmittance (W*H uint32), the first and the stopping voxel and the counts (W*H int32 each) and the
+        summary (32 bytes); d_lut: 256 uint32 on the device; d_volume: the device volume of FIELD_CALLER."""
+        p = lambda x: C.c_void_p(x) if x else None
+        self._check(self._L.rto_composite_field_device(self._h, C.byref(frame), C.byref(composite), p(d_lut), p(d_volume), p(d_under),
+                                                       p(d_rgba), p(d_transmittance), p(d_first), p(d_stops), p(d_counts), p(d_summary),
+                                                       p(stream)))
+
+    def last_composite_ms(self):
+        """(tables, march, summary fold) of the last composite in ms; -1: not run."""
+        return self._last_ms("rto_last_composite_ms", 3)
 
     # -- triangle queries (the resident leaf triangles) --------------------
     def query_triangles(self, origins, dirs, t_min=0.0, t_max=1e30, mode: int = QUERY_CLOSEST) -> np.ndarray:

@@ -136,6 +136,16 @@ def load():
     L.rtoh_projection_walk.restype = C.c_int64
     L.rtoh_projection_reduce.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.c_int32, _vp]
     L.rtoh_projection_reduce.restype = None
+    L.rtoh_rt_composite_field.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp, _vp]
+    L.rtoh_rt_composite_field.restype = C.c_int
+    L.rtoh_rt_composite_values.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]
+    L.rtoh_rt_composite_values.restype = C.c_int64
+    L.rtoh_composite_ray.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]
+    L.rtoh_composite_ray.restype = None
+    L.rtoh_composite_index.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int]
+    L.rtoh_composite_index.restype = C.c_int
+    L.rtoh_composite_thresholds.argtypes = [C.c_int, C.c_int32, C.c_int32, _vp]
+    L.rtoh_composite_thresholds.restype = None
     L.rtoh_rt_pick.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp]
     L.rtoh_rt_pick.restype = C.c_int
     L.rtoh_rt_intersect_spans.argtypes = [_vp, _vp, C.c_int64, C.c_float, C.c_float, _vp]
@@ -791,6 +801,49 @@ class RayTracerBVH:
         sums = np.empty(shape, np.int64)
         load().rtoh_rt_projection_values(self._h, values.ctypes.data, voxels.ctypes.data, sums.ctypes.data, counts.ctypes.data, n)
         return values, voxels, sums, counts
+
+    def compositeField(self, camera: Camera, width: int, height: int, aspect: float, fovDeg: float, composite, lut, volume=None,
+                       under=None) -> int:
+        """Addition: RayTracerBVH::compositeField -- a frame in which a per-voxel int32 volume of the resident grid is seen
+        through, LUT colour and opacity composited front to back.  composite: a hip.FieldComposite; lut and
+        volume as renderField's; under: None or an (H, W, 4) float32 frame to composite over.  RTO_OK or the refusal's code
+        (lastError); read the frame with framebuffer(), the per-pixel outputs with compositeValues(), the counts with
+        compositeSummary()."""
+        lut = np.ascontiguousarray(lut, dtype=np.uint32)
+        if lut.shape != (256,):
+            raise ValueError("compositeField: the LUT has 256 entries")
+        vol = None if volume is None else np.ascontiguousarray(volume, dtype=np.int32)
+        if vol is not None:
+            dims = (C.c_int * 3)()
+            load().rtoh_rt_grid(self._h, dims, None)
+            if vol.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError(f"compositeField: the volume must be {(dims[2], dims[1], dims[0])}, not {vol.shape}")
+        und = None if under is None else np.ascontiguousarray(under, dtype=np.float32)
+        if und is not None and und.shape != (int(height), int(width), 4):
+            raise ValueError(f"compositeField: under must be {(int(height), int(width), 4)}, not {und.shape}")
+        return int(load().rtoh_rt_composite_field(self._h, camera._h, int(width), int(height), _f(aspect), _f(fovDeg),
+                                                  C.addressof(composite), lut.ctypes.data, vol.ctypes.data if vol is not None else None,
+                                                  und.ctypes.data if und is not None else None))
+
+    def compositeValues(self):
+        """Addition: RayTracerBVH::compositeValues -- the last compositeField's (transmittance, first, stops, counts), (H, W) each;
+        None when no composite has been rendered."""
+        w, h = C.c_int(), C.c_int()
+        n = int(load().rtoh_rt_composite_values(self._h, None, None, None, None, 0, None))
+        if n == 0 or not load().rtoh_rt_framebuffer(self._h, None, 0, C.byref(w), C.byref(h)) or w.value * h.value != n:
+            return None
+        shape = (h.value, w.value)
+        trans = np.empty(shape, np.uint32)
+        first, stops, counts = np.empty(shape, np.int32), np.empty(shape, np.int32), np.empty(shape, np.int32)
+        load().rtoh_rt_composite_values(self._h, trans.ctypes.data, first.ctypes.data, stops.ctypes.data, counts.ctypes.data, n, None)
+        return trans, first, stops, counts
+
+    def compositeSummary(self):
+        """Addition: RayTracerBVH::compositeSummary -- the last compositeField's hip.COMPOSITE_SUMMARY_DTYPE record."""
+        from .hip import COMPOSITE_SUMMARY_DTYPE
+        s = np.zeros(1, COMPOSITE_SUMMARY_DTYPE)
+        load().rtoh_rt_composite_values(self._h, None, None, None, None, 0, s.ctypes.data)
+        return s[0]
 
     def framebuffer(self) -> np.ndarray | None:
         w, h = C.c_int(), C.c_int()

@@ -83,6 +83,7 @@ struct HipApi {
     decltype(&rto_edit_parts) edit_parts = nullptr;
     decltype(&rto_render_field_host) render_field_host = nullptr;
     decltype(&rto_project_field_host) project_field_host = nullptr;
+    decltype(&rto_composite_field_host) composite_field_host = nullptr;
     std::string error;
 
     bool load() {
@@ -176,6 +177,7 @@ struct HipApi {
         edit_parts = reinterpret_cast<decltype(edit_parts)>(sym("rto_edit_parts"));
         render_field_host = reinterpret_cast<decltype(render_field_host)>(sym("rto_render_field_host"));
         project_field_host = reinterpret_cast<decltype(project_field_host)>(sym("rto_project_field_host"));
+        composite_field_host = reinterpret_cast<decltype(composite_field_host)>(sym("rto_composite_field_host"));
         if (!ok) { dlclose(handle); handle = nullptr; }
         return ok;
     }
@@ -491,6 +493,37 @@ int RayTracerBVH::projectField(const Camera& camera, int width, int height, floa
         m_projection = ProjectionValues();
         m_fieldSummary = rto_field_view_summary{ 0, 0, 0, 0, 0, 0 };
         return regionFailed(rc, "projectField");
+    }
+    m_frameW = width; m_frameH = height;
+    return RTO_OK;
+}
+
+// A composite of the first GPU's resident grid (rto_composite_field_host): the frame goes to framebuffer(), the per-pixel outputs
+// to compositeValues(), the summary to compositeSummary().  A refusal leaves no frame and no values.
+int RayTracerBVH::compositeField(const Camera& camera, int width, int height, float aspect, float fovDeg,
+                                 const rto_field_composite& composite, const uint32_t* lut, const int32_t* volume, const float* under) {
+    m_composite = CompositeValues();
+    m_compositeSummary = rto_composite_summary{ 0, 0, 0, 0 };
+    if (!computeUsable("compositeField")) return RTO_E_INVALID;
+    if (m_numNodes > 0 && !makeGridResident("field composite")) return RTO_E_HIP;
+    const rto_frame f = frame_of(camera, width, height, aspect, fovDeg);
+    m_frameW = m_frameH = 0; m_frameStale = false;
+    m_frame.clear();
+    if (width > 0 && height > 0) {
+        const size_t n = static_cast<size_t>(width) * height;
+        m_frame.resize(n * 4);
+        m_composite.transmittance.resize(n); m_composite.first.resize(n); m_composite.stops.resize(n); m_composite.counts.resize(n);
+    }
+    CompositeValues& p = m_composite;
+    const bool have = !m_frame.empty();
+    const int rc = api().composite_field_host(m_ctx, &f, &composite, lut, volume, under, have ? m_frame.data() : nullptr,
+                                              have ? p.transmittance.data() : nullptr, have ? p.first.data() : nullptr,
+                                              have ? p.stops.data() : nullptr, have ? p.counts.data() : nullptr, &m_compositeSummary);
+    if (rc != RTO_OK) {
+        m_frame.clear();
+        m_composite = CompositeValues();
+        m_compositeSummary = rto_composite_summary{ 0, 0, 0, 0 };
+        return regionFailed(rc, "compositeField");
     }
     m_frameW = width; m_frameH = height;
     return RTO_OK;

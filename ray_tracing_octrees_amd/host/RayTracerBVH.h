@@ -189,6 +189,19 @@ public:
     int projectField(const Camera& camera, int width, int height, float aspect, float fovDeg, const rto_field_projection& projection,
                      const uint32_t* lut, const int32_t* volume = nullptr);
     const ProjectionValues& projectionValues() const { return m_projection; }
+    // A frame in which such a volume is seen through: LUT colour and opacity per valued voxel, composited front to back along the
+    // pixel rays and, with composite.occlude, stopped by the grid's solids (rto_composite_field_host).
+    // Sources, LUT and return value as renderField's.  under: null, or width * height * 4 floats to composite over.
+    // framebuffer() holds the frame, compositeValues() the transmittance, the first contributing voxel, the stopping voxel and
+    // the contributions under every pixel, compositeSummary() the frame's counts.
+    struct CompositeValues {
+        std::vector<uint32_t> transmittance;
+        std::vector<int32_t> first, stops, counts;
+    };
+    int compositeField(const Camera& camera, int width, int height, float aspect, float fovDeg, const rto_field_composite& composite,
+                       const uint32_t* lut, const int32_t* volume = nullptr, const float* under = nullptr);
+    const CompositeValues& compositeValues() const { return m_composite; }
+    const rto_composite_summary& compositeSummary() const { return m_compositeSummary; }
     // The leaf renderSceneCompute shows at pixel (px, py) (row 0 = top) of a width x height frame of that camera: the render's own
     // ray and its FIRST rule (rto_query_pixels_host).  Replaces the reference's intersectBuildingVoxel (main.cpp:209-) in its
     // click handler.  false (and out a miss) when nothing is hit.
@@ -402,6 +415,8 @@ private:
     std::vector<int32_t> m_fieldValues;                // the last renderField's value per pixel
     rto_field_view_summary m_fieldSummary = { 0, 0, 0, 0, 0, 0 };
     ProjectionValues m_projection;                     // the last projectField's outputs per pixel
+    CompositeValues m_composite;                       // the last compositeField's outputs per pixel
+    rto_composite_summary m_compositeSummary{ 0, 0, 0, 0 };
 
     mutable std::vector<float> m_frame;
     mutable bool m_frameStale = false;   // the GPU holds a newer frame than m_frame

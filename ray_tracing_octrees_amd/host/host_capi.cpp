@@ -18,6 +18,7 @@
 #include "Thickness.h"
 #include "Parts.h"
 #include "Measure.h"
+#include "Composite.h"
 #include "Projection.h"
 #include "Camera.h"
 #include "Frustum.h"
@@ -270,6 +271,36 @@ void rtoh_projection_reduce(const int32_t* volume, const int32_t dim[3], const i
                                                                     op, validLo, validHi);
     result[0] = r.value; result[1] = r.voxel; result[2] = r.sum; result[3] = r.count;
 }
+int rtoh_rt_composite_field(RayTracerBVH* rt, const Camera* cam, int w, int h, float aspect, float fovDeg, const rto_field_composite* comp,
+                            const uint32_t* lut, const int32_t* volume, const float* under) {
+    return rt->compositeField(*cam, w, h, aspect, fovDeg, *comp, lut, volume, under);
+}
+// Up to `capacity` entries each of the last compositeField's transmittance, first, stops and counts, row-major; returns how many
+// there are.  summary may be NULL.
+int64_t rtoh_rt_composite_values(const RayTracerBVH* rt, uint32_t* transmittance, int32_t* first, int32_t* stops, int32_t* counts,
+                                 int64_t capacity, rto_composite_summary* summary) {
+    const RayTracerBVH::CompositeValues& p = rt->compositeValues();
+    const size_t n = (size_t)std::min<int64_t>((int64_t)p.counts.size(), capacity);
+    if (transmittance) std::copy(p.transmittance.begin(), p.transmittance.begin() + n, transmittance);
+    if (first) std::copy(p.first.begin(), p.first.begin() + n, first);
+    if (stops) std::copy(p.stops.begin(), p.stops.begin() + n, stops);
+    if (counts) std::copy(p.counts.begin(), p.counts.begin() + n, counts);
+    if (summary) *summary = rt->compositeSummary();
+    return (int64_t)p.counts.size();
+}
+// The CPU form of a composite (host/Composite.h).  One ray: a walk of rtoh_projection_walk composited under comp; grid: the
+// resident bytes (read with comp->occlude), under: the pixel below or NULL; result: T, R, G, B, first, stop, count, end; rgba: the
+// pixel's colour (n == 0 is a miss).
+void rtoh_composite_ray(const int32_t* volume, const uint8_t* grid, const int32_t dim[3], const int32_t* cells, int64_t n,
+                        const rto_field_composite* comp, const uint32_t* lut, const float* under, int64_t result[8], float rgba[4]) {
+    const rto_host::CompositeResult r = rto_host::compositeRay(volume, grid, dim, reinterpret_cast<const rto_host::ProjectionVoxel*>(cells), n,
+                                                               *comp, lut);
+    result[0] = r.T; result[1] = r.R; result[2] = r.G; result[3] = r.B; result[4] = r.first; result[5] = r.stop; result[6] = r.count;
+    result[7] = r.end;
+    rto_host::compositeColour(r, n > 0, *comp, under, rgba);
+}
+int rtoh_composite_index(int32_t v, int32_t lo, int32_t hi, int scale) { return rto_host::compositeIndex(v, lo, hi, scale); }
+void rtoh_composite_thresholds(int scale, int32_t lo, int32_t hi, uint32_t thr[256]) { rto_host::compositeThresholds(scale, lo, hi, thr); }
 int64_t rtoh_rt_num_nodes(const RayTracerBVH* rt) { return (int64_t)rt->numNodes(); }
 int rtoh_rt_framebuffer(const RayTracerBVH* rt, float* out, int64_t capacityFloats, int* w, int* h) {
     *w = rt->frameWidth(); *h = rt->frameHeight();

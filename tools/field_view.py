@@ -5,6 +5,7 @@ and the legend (range, the 256 bins, the LUT) as JSON beside it.  numpy only.
     python3 tools/field_view.py --scene calgary --field sky --out calgary_sky.ppm
     python3 tools/field_view.py --scene sphere128 --field thickness --clip 0.5 --out cut.ppm
     python3 tools/field_view.py --scene sphere128 --field distance --project max --out xray.ppm
+    python3 tools/field_view.py --scene calgary --field air --composite --over-lit --out fog.ppm
 
 Scenes: sphereN (the test sphere of edge N, Camera(0.5, 0.7, 1.8)) and calgary (the shipped city grid, Camera(0.6, 0.5, 3500)).
 Fields: distance (to EMPTY, SQRT scale: how deep inside), thickness (SQRT), skeleton, labels and parts (CATEGORY), geodesic
@@ -12,7 +13,13 @@ Fields: distance (to EMPTY, SQRT scale: how deep inside), thickness (SQRT), skel
 directions of the upper hemisphere: the sky view factor; both sampled in FRONT of the surface).  --clip F keeps the part of the
 grid below the fraction F of its x extent (a section through the solid).  --project OP (max, min, mean, count, first) renders a
 projection instead (rto_project_field_host): the reduction of the field along every pixel ray through the grid, or through the
---clip box; --window LO HI sets the values that count (for first: the threshold of an isosurface seen through walls)."""
+--clip box; --window LO HI sets the values that count (for first: the threshold of an isosurface seen through walls).
+--composite renders the field as a volume seen through (rto_composite_field_*): the LUT's colours with an opacity that rises from
+--opacity / 4 to --opacity (alpha bytes), composited front to back; --see-through lets the rays pass the solids (by default they
+stop at the first one); --stop Q ends a ray once its transmittance (of 65536) is at most Q; --range LO HI is the range of the
+colours (by default the smallest and largest value a 160 x 90 projection from the same camera finds).  --over-lit renders the lit
+frame on the device and composites over it in place (needs torch for the device buffers); without it the background is the sky
+colour.  Field `air` is the distance to SOLID, which lives in the empty space."""
 import argparse
 import json
 import os
@@ -58,6 +65,9 @@ def make_field(ctx, field, up, voxel):
     if field == "distance":
         ctx.distance_field(hip.SET_EMPTY)
         return dict(source=hip.FIELD_DISTANCE, scale=hip.SCALE_SQRT)
+    if field == "air":
+        ctx.distance_field(hip.SET_SOLID)
+        return dict(source=hip.FIELD_DISTANCE, scale=hip.SCALE_SQRT, valid=(1, 0x7ffffffe))
     if field == "thickness":
         ctx.thickness_field(hip.SET_SOLID, 8 * float(voxel))
         return dict(source=hip.FIELD_THICKNESS, scale=hip.SCALE_SQRT)
@@ -88,6 +98,42 @@ def write_ppm(path, rgba):
         fh.write(np.ascontiguousarray(rgb).tobytes())
 
 
+def composite(ctx, f, kw, lut, a):
+    """The frame of --composite and its legend."""
+    kw = {k: v for k, v in kw.items() if k != "sample"}
+    if a.window:
+        kw["valid"] = tuple(a.window)
+    if a.range:
+        kw["range"] = tuple(a.range)
+    elif kw.get("scale") != hip.SCALE_CATEGORY and "range" not in kw:
+        small = rto.make_frame(np.array(f.view, np.float32), np.array(f.cam_pos, np.float32), f.aspect, f.fov_deg, 160, 90)
+        pk = {k: v for k, v in kw.items() if k in ("source", "scale", "valid", "clip")}
+        top = ctx.project_field_host(small, hip.make_field_projection(op=hip.PROJECT_MAX, **pk), lut, totals=False)[5]
+        low = ctx.project_field_host(small, hip.make_field_projection(op=hip.PROJECT_MIN, **pk), lut, totals=False)[5]
+        kw["range"] = (int(low["vmin"]), max(int(top["vmax"]), int(low["vmin"]) + 1))
+    alpha = np.clip(a.opacity // 4 + (np.arange(256) * (a.opacity - a.opacity // 4)) // 255, 0, 255).astype(np.uint32)
+    lut = (lut & np.uint32(0x00ffffff)) | (alpha << np.uint32(24))
+    sky = (0.55, 0.7, 0.9, 1.0)
+    comp = hip.make_field_composite(stop_q16=a.stop, occlude=not a.see_through, background_rgba=sky, miss_rgba=sky, **kw)
+    if a.over_lit:
+        import torch
+        n = f.width * f.height
+        d_rgba = torch.empty(n * 4, dtype=torch.float32, device="cuda")
+        d_lut = torch.from_numpy(lut.view(np.int32)).cuda()
+        d_summary = torch.zeros(4, dtype=torch.int64, device="cuda")
+        ctx.render_lit_device(f, hip.make_lighting(), d_rgba.data_ptr())
+        ctx.composite_field_device(f, comp, d_lut.data_ptr(), d_rgba.data_ptr(), d_under=d_rgba.data_ptr(), d_summary=d_summary.data_ptr())
+        torch.cuda.synchronize()
+        rgba = d_rgba.cpu().numpy().reshape(f.height, f.width, 4)
+        summary = d_summary.cpu().numpy().view(hip.COMPOSITE_SUMMARY_DTYPE)[0]
+    else:
+        rgba, _, _, _, _, summary = ctx.composite_field_host(f, comp, lut)
+    legend = {name: int(summary[name]) for name in hip.COMPOSITE_SUMMARY_DTYPE.names}
+    legend.update(range=[int(comp.range_lo), int(comp.range_hi)], scale=int(comp.scale), stop_q16=int(comp.stop_q16), occlude=int(comp.occlude),
+                  over_lit=bool(a.over_lit), lut_rgba=lut.view(np.uint8).reshape(256, 4).tolist(), ms=list(ctx.last_composite_ms()))
+    return rgba, legend
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="calgary")
@@ -100,6 +146,12 @@ def main():
     ap.add_argument("--project", choices=("max", "min", "mean", "count", "first"), default=None,
                     help="a projection along the pixel rays instead of a view of the surface")
     ap.add_argument("--window", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="with --project: the values that count")
+    ap.add_argument("--composite", action="store_true", help="the field as a volume seen through, composited front to back")
+    ap.add_argument("--over-lit", action="store_true", help="with --composite: over the lit frame, in place on the device")
+    ap.add_argument("--see-through", action="store_true", help="with --composite: the rays pass the solids")
+    ap.add_argument("--opacity", type=int, default=24, help="with --composite: the largest alpha byte of the LUT")
+    ap.add_argument("--stop", type=int, default=256, help="with --composite: stop_q16")
+    ap.add_argument("--range", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="with --composite: the colours' range")
     ap.add_argument("--out", default="field_view.ppm")
     a = ap.parse_args()
     grid, cam, up = scene(a.scene)
@@ -112,6 +164,16 @@ def main():
     lut = hip.ramp_lut(HEAT)
     W, H = a.width, a.height
     f = rto.make_frame(cam.getView(), cam.getPos(), W / H, 45.0, W, H)
+    if a.composite:
+        rgba, legend = composite(ctx, f, kw, lut, a)
+        write_ppm(a.out, rgba)
+        legend.update(scene=a.scene, field=a.field, frame=[W, H])
+        with open(os.path.splitext(a.out)[0] + ".legend.json", "w") as fh:
+            json.dump(legend, fh)
+        print(f"{a.out}: {W}x{H}, {legend['visited']} pixels visit the volume, {legend['contributing']} show it, {legend['saturated']} "
+              f"saturated, {legend['occluded']} stopped by a solid")
+        ctx.close()
+        return
     if a.project:
         kw.pop("sample", None)
         if a.window:
