@@ -1611,6 +1611,73 @@ int  rto_composite_field_host(rto_context* ctx, const rto_frame* frame, const rt
  * empty. */
 int  rto_last_composite_ms(const rto_context* ctx, float ms[3]);
 
+/* ---- field isosurfaces ------------------------------------------------------
+ * Marching cubes of an int32 volume of the resident grid at a float level, made on the GPU: the offset
+ * surface of a distance field, the boundary of "thinner than three voxels", the reach limit of a geodesic flood, as the same
+ * 12-float records rto_extract_mesh gives.  This is the reference's marchingCubesVolume (S/MarchingCubes.cpp:622-689) over the
+ * voxel centres, its marchingCubesCell / vertexInterp (:544-620) word for word.  All floats are float32, one IEEE operation per
+ * operator, in the order written, with no contraction.  rto_update_frustum is ignored.  Rule:
+ *   samples   one per voxel, at the voxel centre: origin[a] = gridMin[a] + 0.5f * voxelSize, P_a(i) = origin[a] + (float)i *
+ *             voxelSize (the reference's origin + vec3(x, y, z) * spacing with spacing = voxelSize).  i may be -1 or dim under pad.
+ *   value     a voxel inside the box [lo, hi) whose volume value v lies in [valid_lo, valid_hi] has the value (float)v; every other
+ *             sample -- an unvalued voxel, a voxel outside the box, the pad ring -- takes the float `outside`.  The box is the clip
+ *             box, or [0, dim) without one.  The defaults valid = (0, 0x7ffffffe) leave out -1 and RTO_DIST_NONE, as the views do.
+ *             Values above 2^24 round to nearest: that is part of the rule.
+ *   cells     without pad: cell (x, y, z) for lo[a] <= c < hi[a] - 1 on every axis.  With pad != 0: lo[a] - 1 <= c < hi[a], so a
+ *             ring of `outside` samples closes the surface at the box's faces.  A box of one sample along an axis has no cells
+ *             without pad: an empty list, not an error.
+ *   cell      corners 0..7 at (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1); bit i of the case is set when val_i <
+ *             level; the 12 edges join the reference's corner pairs; a vertex is p1 when fabsf(level - v1) < 1e-6f, else p2 when
+ *             fabsf(level - v2) < 1e-6f, else p1 when fabsf(v1 - v2) < 1e-6f, else p1 + ((level - v1) / (v2 - v1)) * (p2 - p1) per
+ *             component; the triangles are those of the case's triTable row, in row order (the leaf-triangle build's table).
+ *   normal    the reference writes a placeholder (0, 1, 0); this writes the face normal by localMC's formula: n = cross(v1 - v0,
+ *             v2 - v0), l2 = dot(n, n); when l2 > 0 and finite the normal is n * inversesqrt(l2), otherwise (+0, +0, +0): the
+ *             triangle stays in the list and counts as degenerate.  Snapped vertices make degenerate triangles whenever level
+ *             equals a sample value: use half-integer levels.
+ *   order     cells in the reference's loop order, z slowest, then y, then x; within a cell the table's.
+ *   record    12 floats per triangle: v0, v1, v2, normal (rto_extract_mesh's layout).  tri_cell[j] = ((z + 1) * (dimY + 1) + (y + 1))
+ *             * (dimX + 1) + (x + 1) of the owning cell, whatever the pad or clip.
+ * Both extraction calls are synchronous on the context's stream (one count is read back).  The result is a snapshot in a buffer of
+ * its own -- not rto_extract_mesh's: both stay downloadable side by side -- valid until the next isosurface extraction or
+ * rto_destroy, untouched by later edits or builds.  An empty result is RTO_OK with 0 triangles.  The refusals below leave the previous
+ * isosurface alone; a device failure (RTO_E_HIP) after the output buffer has been replaced by a larger one leaves none.
+ * The count pass skips tiles the level does not cross through a table of each 8 x 8 x 8 brick's smallest and largest substituted
+ * value, rebuilt by every call; it changes no output, and rto_debug_set_projection_table(ctx, 0) switches it off too.
+ * Sources are the field views'.  Errors, each leaving the previous isosurface and the context untouched, checked in this order:
+ * RTO_E_INVALID: NULL params; a misaligned volume (4 bytes); an unknown source; reserved != 0; valid_lo > valid_hi or valid_lo <=
+ * INT32_MIN + 1; a level or outside that is not finite; pad other than 0 or 1; CALLER without a volume, or a volume with another
+ * source.  RTO_E_NO_OCTREE: nothing uploaded.  RTO_E_UNSUPPORTED: no resident grid (rto_upload_octree), then (dimX + 1)(dimY + 1)
+ * (dimZ + 1) >= 2^31.  RTO_E_INVALID: a clip box with clip_lo[a] < 0, clip_hi[a] > dim[a] or clip_lo[a] >= clip_hi[a]; last, a
+ * named source that is not resident, in its readers' words.  RTO_E_UNSUPPORTED: more than 2^31 - 1 triangles (the count saturates). */
+typedef struct rto_iso_params {     /* 64 bytes */
+    int32_t  source;                /* RTO_FIELD_* */
+    int32_t  valid_lo, valid_hi;    /* the window of valued voxels; defaults 0 and 0x7ffffffe; valid_lo > INT32_MIN + 1 */
+    float    level, outside;        /* finite */
+    int32_t  pad;                   /* 0 or 1 */
+    int32_t  clip;                  /* != 0: the box below applies */
+    int32_t  clip_lo[3], clip_hi[3];   /* voxel indices, x y z: 0 <= clip_lo < clip_hi <= dim */
+    int32_t  reserved[3];           /* 0 */
+} rto_iso_params;
+typedef struct rto_iso_summary {    /* 32 bytes */
+    int64_t  triangles;
+    int64_t  active_cells;          /* cells with at least one triangle */
+    int64_t  degenerate;            /* triangles whose normal is (0, 0, 0) */
+    int64_t  reserved;
+} rto_iso_summary;
+
+int  rto_extract_isosurface_device(rto_context* ctx, const rto_iso_params* params, const int32_t* d_volume /* RTO_FIELD_CALLER only */,
+                                   rto_iso_summary* summary /* host; may be NULL */);
+/* The same with a caller's volume in host memory. */
+int  rto_extract_isosurface_host(rto_context* ctx, const rto_iso_params* params, const int32_t* volume /* RTO_FIELD_CALLER only */,
+                                 rto_iso_summary* summary /* may be NULL */);
+/* The last isosurface where it lies: num_tris records of 48 bytes and as many int32 (both may be NULL for the count alone). */
+int  rto_isosurface_device(rto_context* ctx, void** d_tris, int32_t** d_tri_cell, int64_t* num_tris);
+/* Copies it out; tris == NULL and tri_cell == NULL: the count alone.  RTO_E_INVALID: none extracted yet, capacity too small. */
+int  rto_download_isosurface(rto_context* ctx, float* tris, int64_t capacity, int32_t* tri_cell /* may be NULL */, int64_t* num_tris);
+/* Device time in ms of the last extraction: count (with the brick table), rank, emit (-1: not run, or the box had no cell and no
+ * kernel ran).  The read-back of the count and the growth of the output buffer lie between the last two and are in none of them. */
+int  rto_last_isosurface_ms(const rto_context* ctx, float ms[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -197,6 +197,12 @@ struct rto_context {
     int meshLevelStart[kMaxDepth + 2] = { 0 };
     int meshLevels = 0;                       // 0: not known for the resident array (made on first use, dropped with the arrays)
 
+    // field isosurfaces (rto_iso.inc): the last isosurface, a snapshot the context owns, apart from the mesh above
+    float4* d_iso = nullptr;
+    int* d_isoCell = nullptr;
+    int64_t isoTris = -1, isoCap = 0;         // -1: no isosurface extracted yet
+    float isoMs[3] = { -1.f, -1.f, -1.f };
+
     // connected components (rto_components.inc): the last labelling of the resident grid; dropped whenever the grid changes
     int* d_ccLabels = nullptr;                // nullptr: no labels resident
     rto::CcComp* d_ccComps = nullptr;
@@ -438,6 +444,8 @@ void rto_destroy(rto_context* c) {
     for (hipEvent_t e : c->cpEv) if (e) (void)hipEventDestroy(e);
     (void)hipFree(c->d_mesh);
     (void)hipFree(c->d_meshNode);
+    (void)hipFree(c->d_iso);
+    (void)hipFree(c->d_isoCell);
     for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ringStop) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3061,6 +3069,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_composite.inc"
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
+#include "rto_iso.inc"
 #include "rto_region.inc"
 #include "rto_components.inc"
 #include "rto_distance.inc"

@@ -63,6 +63,8 @@ SYMBOLS = (
     "rto_render_field_device", "rto_render_field_host", "rto_last_field_view_ms",
     "rto_project_field_device", "rto_project_field_host", "rto_last_projection_ms", "rto_debug_set_projection_table",
     "rto_composite_field_device", "rto_composite_field_host", "rto_last_composite_ms",
+    "rto_extract_isosurface_device", "rto_extract_isosurface_host", "rto_isosurface_device", "rto_download_isosurface",
+    "rto_last_isosurface_ms",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -332,6 +334,34 @@ def make_field_composite(source, scale=SCALE_LINEAR, valid=(0, 0x7ffffffe), rang
     for k in (0, 1, 2, 3):
         v.background_rgba[k] = _f(background_rgba[k])
         v.miss_rgba[k] = _f(miss_rgba[k])
+    return v
+
+
+# struct rto_iso_params (64 bytes) / rto_iso_summary (32 bytes): field isosurfaces (rto_extract_isosurface_*)
+class IsoParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("valid_lo", C.c_int32), ("valid_hi", C.c_int32), ("level", C.c_float), ("outside", C.c_float),
+                ("pad", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_int32 * 3), ("clip_hi", C.c_int32 * 3),
+                ("reserved", C.c_int32 * 3)]
+
+
+class IsoSummary(C.Structure):
+    _fields_ = [("triangles", C.c_int64), ("active_cells", C.c_int64), ("degenerate", C.c_int64), ("reserved", C.c_int64)]
+
+
+def make_iso_params(source, level, outside=0.0, valid=(0, 0x7ffffffe), pad=True, clip=None) -> IsoParams:
+    """An rto_iso_params.  level: the iso value; half-integer levels avoid degenerate triangles.  outside: the value of every
+    sample that is unvalued, outside the box or in the pad ring.  The default 0 closes the surface around what lies above the
+    level; a field that grows away from its object, such as the distance to the solids, wants a large value.  pad: True or False
+    (an integer is handed on as it is).  clip: None or ((x0, y0, z0), (x1, y1, z1)) in voxel indices."""
+    v = IsoParams()
+    v.source = int(source)
+    v.valid_lo, v.valid_hi = int(valid[0]), int(valid[1])
+    v.level, v.outside = _f(level), _f(outside)
+    v.pad = int(pad)
+    v.clip = 0 if clip is None else 1
+    for a in (0, 1, 2):
+        v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
+        v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
     return v
 
 
@@ -669,6 +699,11 @@ def load():
     L.rto_composite_field_device.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldComposite), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rto_composite_field_host.argtypes = [vp, C.POINTER(Frame), C.POINTER(FieldComposite), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rto_last_composite_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_extract_isosurface_device.argtypes = [vp, C.POINTER(IsoParams), vp, C.POINTER(IsoSummary)]
+    L.rto_extract_isosurface_host.argtypes = [vp, C.POINTER(IsoParams), vp, C.POINTER(IsoSummary)]
+    L.rto_isosurface_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_download_isosurface.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.rto_last_isosurface_ms.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1819,6 +1854,48 @@ class Context:
     def last_mesh_ms(self):
         """Device ms of the last extraction: (count + cull, ranking passes, emit); -1: not run."""
         return self._last_ms("rto_last_mesh_ms", 3)
+
+    # -- field isosurfaces -------------------------------------------------
+    def extract_isosurface_count(self, params: IsoParams, volume=None) -> IsoSummary:
+        """rto_extract_isosurface_*: the list stays on the device (isosurface_device / download_isosurface).  volume (source
+        FIELD_CALLER only): a host array of dimZ x dimY x dimX int32, or a device pointer (an int, or a device tensor)."""
+        summary = IsoSummary()
+        if volume is None or isinstance(volume, int):
+            rc = self._L.rto_extract_isosurface_device(self._h, C.byref(params) if params is not None else None, volume or None, C.byref(summary))
+        elif hasattr(volume, "data_ptr") and getattr(volume, "is_cuda", False):
+            rc = self._L.rto_extract_isosurface_device(self._h, C.byref(params) if params is not None else None, volume.data_ptr(), C.byref(summary))
+        else:
+            vol = np.ascontiguousarray(np.asarray(volume, dtype=np.int32))
+            rc = self._L.rto_extract_isosurface_host(self._h, C.byref(params) if params is not None else None, vol.ctypes.data, C.byref(summary))
+        self._check(rc)
+        return summary
+
+    def download_isosurface(self):
+        """The last isosurface: (tris float32 (n, 12): v0, v1, v2, normal; tri_cell int32 (n,): the owning cell)."""
+        n = C.c_int64()
+        self._check(self._L.rto_download_isosurface(self._h, None, 0, None, C.byref(n)))
+        tris = np.zeros((n.value, 12), np.float32)
+        cell = np.zeros(n.value, np.int32)
+        if n.value:
+            self._check(self._L.rto_download_isosurface(self._h, tris.ctypes.data, n.value, cell.ctypes.data, C.byref(n)))
+        return tris, cell
+
+    def extract_isosurface(self, params: IsoParams, volume=None):
+        """Marching cubes of a voxel field at params.level, in the reference's cell order.  Returns
+        (tris (n, 12), tri_cell (n,), summary)."""
+        summary = self.extract_isosurface_count(params, volume)
+        tris, cell = self.download_isosurface()
+        return tris, cell, summary
+
+    def isosurface_device(self):
+        """(device pointer of the 48-byte records, device pointer of tri_cell, count) of the last isosurface."""
+        t, cl, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._L.rto_isosurface_device(self._h, C.byref(t), C.byref(cl), C.byref(n)))
+        return t.value or 0, cl.value or 0, n.value
+
+    def last_isosurface_ms(self):
+        """Device ms of the last isosurface: (count, rank, emit); -1: not run."""
+        return self._last_ms("rto_last_isosurface_ms", 3)
 
     def scene_bounds(self) -> SceneBounds:
         b = SceneBounds()

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _build
 from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, FIELD_VIEW_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
-                  THICK_MAX_C, THICK_SUMMARY_DTYPE, RtoError, _f)
+                  THICK_MAX_C, THICK_SUMMARY_DTYPE, IsoParams, IsoSummary, RtoError, _f)
 
 _lib = None
 _vp = C.c_void_p
@@ -278,6 +278,17 @@ def load():
     L.rtoh_rt_extract_mesh.restype = _vp
     L.rtoh_tris_take.argtypes = [_vp, _vp]
     L.rtoh_tris_take.restype = None
+    L.rtoh_marching_cubes_volume.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.c_float, C.POINTER(C.c_int64)]
+    L.rtoh_marching_cubes_volume.restype = _vp
+    L.rtoh_iso_surface_volume.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.POINTER(IsoParams), C.POINTER(IsoSummary),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.rtoh_iso_surface_volume.restype = _vp
+    L.rtoh_iso_take.argtypes = [_vp, _vp, _vp]
+    L.rtoh_iso_take.restype = None
+    L.rtoh_iso_surface_volume_ms.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.POINTER(IsoParams), C.POINTER(C.c_int64)]
+    L.rtoh_iso_surface_volume_ms.restype = C.c_double
+    L.rtoh_rt_iso_surface.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_int, _vp, C.POINTER(C.c_int64)]
+    L.rtoh_rt_iso_surface.restype = _vp
     _lib = L
     return L
 
@@ -600,6 +611,46 @@ def renderOctreePlanesMs(root: OctreeNode, grid: VoxelGrid, renderer, planes, ex
     pl = None if planes is None else np.ascontiguousarray(np.asarray(planes, np.float32).reshape(24))
     n = C.c_int64(0)
     ms = load().rtoh_render_octree_planes_ms(root._h, grid._h, kind, None if pl is None else pl.ctypes.data, _f(extraMargin), C.byref(n))
+    return float(ms), int(n.value)
+
+
+def marchingCubesVolume(scalarField, origin, spacing: float, isoValue: float) -> np.ndarray:
+    """453-skeleton/MarchingCubes.cpp:622-689 on the CPU: whole-volume marching cubes of a float field (dimZ, dimY, dimX) whose
+    sample (0, 0, 0) lies at `origin`.  (n, 18) float32 as localMC returns them, the reference's placeholder normals included."""
+    f = np.ascontiguousarray(np.asarray(scalarField, np.float32))
+    dz, dy, dx = f.shape
+    o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+    n = C.c_int64(0)
+    lst = load().rtoh_marching_cubes_volume(f.ctypes.data, dx, dy, dz, o.ctypes.data, _f(spacing), _f(isoValue), C.byref(n))
+    out = np.zeros((n.value, 18), np.float32)
+    load().rtoh_tris_take(lst, out.ctypes.data)
+    return out
+
+
+def isoSurfaceVolume(volume, gridMin, voxelSize: float, params: IsoParams):
+    """Addition: the field isosurface rule on the CPU, a plain triple loop over the cells of an int32 volume
+    (dimZ, dimY, dimX).  Returns (tris (n, 18) float32, tri_cell (n,) int32, IsoSummary); RtoError where the C ABI refuses."""
+    v = np.ascontiguousarray(np.asarray(volume, np.int32))
+    dz, dy, dx = v.shape
+    g = np.ascontiguousarray(np.asarray(gridMin, np.float32).reshape(3))
+    n, rc, summary = C.c_int64(0), C.c_int(0), IsoSummary()
+    lst = load().rtoh_iso_surface_volume(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), C.byref(params), C.byref(summary),
+                                         C.byref(rc), C.byref(n))
+    out = np.zeros((n.value, 18), np.float32)
+    cell = np.zeros(n.value, np.int32)
+    load().rtoh_iso_take(lst, out.ctypes.data, cell.ctypes.data)                # one extraction: copied out and freed
+    if rc.value != 0:
+        raise RtoError(rc.value, "isoSurfaceVolume: invalid parameters")
+    return out, cell, summary
+
+
+def isoSurfaceVolumeMs(volume, gridMin, voxelSize: float, params: IsoParams):
+    """Addition: (milliseconds of one isoSurfaceVolume on one core, timed inside the library; triangles)."""
+    v = np.ascontiguousarray(np.asarray(volume, np.int32))
+    dz, dy, dx = v.shape
+    g = np.ascontiguousarray(np.asarray(gridMin, np.float32).reshape(3))
+    n = C.c_int64(0)
+    ms = load().rtoh_iso_surface_volume_ms(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), C.byref(params), C.byref(n))
     return float(ms), int(n.value)
 
 
@@ -1214,6 +1265,26 @@ class RayTracerBVH:
                                           None if pl is None else pl.ctypes.data, _f(extraMargin), C.byref(n))
         out = np.zeros((n.value, 18), np.float32)
         load().rtoh_tris_take(lst, out.ctypes.data)                # one extraction: copied out and freed
+        return out
+
+    def isoSurface(self, source: int, level: float, outside: float = 0.0, pad: bool = True, volume=None) -> np.ndarray:
+        """Addition: RayTracerBVH::isoSurface -- marching cubes of a voxel field at `level`, made on the GPU (DESIGN.md section
+        30); volume: the (dimZ, dimY, dimX) int32 array of FIELD_CALLER.  (n, 18) float32; empty with lastError set on an error."""
+        vol = None if volume is None else np.ascontiguousarray(np.asarray(volume, np.int32))
+        n = C.c_int64(0)
+        lst = load().rtoh_rt_iso_surface(self._h, int(source), _f(level), _f(outside), 1 if pad else 0,
+                                         None if vol is None else vol.ctypes.data, C.byref(n))
+        out = np.zeros((n.value, 18), np.float32)
+        load().rtoh_tris_take(lst, out.ctypes.data)
+        return out
+
+    def offsetSurface(self, distanceInVoxels: float) -> np.ndarray:
+        """Addition: RayTracerBVH::offsetSurface -- the surface at that distance from the solids (the distance field to the
+        solids contoured at its square).  (n, 18) float32."""
+        n = C.c_int64(0)
+        lst = load().rtoh_rt_iso_surface(self._h, -1, _f(distanceInVoxels), 0.0, 1, None, C.byref(n))
+        out = np.zeros((n.value, 18), np.float32)
+        load().rtoh_tris_take(lst, out.ctypes.data)
         return out
 
     def grid(self) -> np.ndarray:

@@ -51,6 +51,8 @@ struct HipApi {
     decltype(&rto_frustum_planes) frustum_planes = nullptr;
     decltype(&rto_extract_mesh) extract_mesh = nullptr;
     decltype(&rto_download_mesh) download_mesh = nullptr;
+    decltype(&rto_extract_isosurface_host) extract_isosurface_host = nullptr;
+    decltype(&rto_download_isosurface) download_isosurface = nullptr;
     decltype(&rto_query_points_host) query_points_host = nullptr;
     decltype(&rto_query_regions_host) query_regions_host = nullptr;
     decltype(&rto_query_nearest_host) query_nearest_host = nullptr;
@@ -145,6 +147,8 @@ struct HipApi {
         frustum_planes = reinterpret_cast<decltype(frustum_planes)>(sym("rto_frustum_planes"));
         extract_mesh = reinterpret_cast<decltype(extract_mesh)>(sym("rto_extract_mesh"));
         download_mesh = reinterpret_cast<decltype(download_mesh)>(sym("rto_download_mesh"));
+        extract_isosurface_host = reinterpret_cast<decltype(extract_isosurface_host)>(sym("rto_extract_isosurface_host"));
+        download_isosurface = reinterpret_cast<decltype(download_isosurface)>(sym("rto_download_isosurface"));
         query_points_host = reinterpret_cast<decltype(query_points_host)>(sym("rto_query_points_host"));
         query_regions_host = reinterpret_cast<decltype(query_regions_host)>(sym("rto_query_regions_host"));
         query_nearest_host = reinterpret_cast<decltype(query_nearest_host)>(sym("rto_query_nearest_host"));
@@ -653,6 +657,51 @@ std::vector<MCTriangle> RayTracerBVH::extractMeshPlanes(int kind, const float* p
         out[i].normal[0] = out[i].normal[1] = out[i].normal[2] = rto_host::vec3(r[9], r[10], r[11]);
     }
     return out;
+}
+
+std::vector<MCTriangle> RayTracerBVH::isoSurface(int source, float level, float outside, bool pad, const int32_t* volume,
+                                                 std::vector<int32_t>* triCell, rto_iso_summary* summary) {
+    std::vector<MCTriangle> out;
+    if (triCell) triCell->clear();
+    m_lastError.clear();                       // an empty list with lastError() empty is an empty surface, not a failure
+    if (!computeUsable("isoSurface")) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return out;
+    }
+    if (m_numNodes > 0 && !makeGridResident("isosurface")) return out;
+    rto_iso_params p;
+    std::memset(&p, 0, sizeof p);
+    p.source = source;
+    p.valid_lo = 0; p.valid_hi = 0x7ffffffe;
+    p.level = level; p.outside = outside;
+    p.pad = pad ? 1 : 0;
+    std::vector<float> rec;
+    int64_t n = 0;
+    if (api().extract_isosurface_host(m_ctx, &p, volume, summary) != RTO_OK || api().download_isosurface(m_ctx, nullptr, 0, nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] isoSurface failed: " << m_lastError << std::endl;
+        return out;
+    }
+    rec.resize((size_t)n * 12);
+    if (triCell) triCell->resize((size_t)n);
+    if (n > 0 && api().download_isosurface(m_ctx, rec.data(), n, triCell ? triCell->data() : nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] isoSurface failed: " << m_lastError << std::endl;
+        if (triCell) triCell->clear();
+        return out;
+    }
+    out.resize((size_t)n);
+    for (size_t i = 0; i < out.size(); i++) {
+        const float* r = rec.data() + 12 * i;
+        for (int v = 0; v < 3; v++) out[i].v[v] = rto_host::vec3(r[3 * v], r[3 * v + 1], r[3 * v + 2]);
+        out[i].normal[0] = out[i].normal[1] = out[i].normal[2] = rto_host::vec3(r[9], r[10], r[11]);
+    }
+    return out;
+}
+
+std::vector<MCTriangle> RayTracerBVH::offsetSurface(float distanceInVoxels) {
+    if (distanceField(RTO_SET_SOLID, INFINITY, nullptr) != RTO_OK) return {};
+    return isoSurface(RTO_FIELD_DISTANCE, distanceInVoxels * distanceInVoxels, 1.0e9f, true);
 }
 
 std::vector<MCTriangle> RayTracerBVH::extractMesh(int kind, const Camera& camera, float aspect, float extraMargin) {

@@ -360,6 +360,17 @@ public:
     enum MeshKind { MeshMC = RTO_MESH_MC, MeshCubes = RTO_MESH_CUBES };
     std::vector<MCTriangle> extractMesh(int kind, const Camera& camera, float aspect, float extraMargin = 50.0f);
     std::vector<MCTriangle> extractMeshPlanes(int kind, const float* planes, float extraMargin);
+    // The isosurface of a voxel field, made on the GPU (rto_extract_isosurface_host): marching cubes of the
+    // resident distance, geodesic, thickness, skeleton, exposure or part-label field, the component labels, or with
+    // RTO_FIELD_CALLER `volume` (dimZ x dimY x dimX, x fastest) at `level`, in the reference's marchingCubesVolume order, with
+    // face normals.  outside: the value of every sample without one (unvalued voxels, the pad ring); pad: close the surface at the
+    // grid's faces.  Empty, with lastError set, on an error.  offsetSurface: the surface at distanceInVoxels from the solids --
+    // the distance field to RTO_SET_SOLID contoured at its square (half-integer distances give no degenerate triangle only
+    // where their square is no field value: 2.5 -> 6.25 is none).  offsetSurface MAKES that distance field, so it replaces the
+    // resident one: a field to RTO_SET_EMPTY made before is gone afterwards and has to be made again.  The CPU form of the same rule is host/MarchingCubes.h.
+    std::vector<MCTriangle> isoSurface(int source, float level, float outside = 0.0f, bool pad = true, const int32_t* volume = nullptr,
+                                       std::vector<int32_t>* triCell = nullptr, rto_iso_summary* summary = nullptr);
+    std::vector<MCTriangle> offsetSurface(float distanceInVoxels);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

@@ -18,6 +18,7 @@
 #include "Thickness.h"
 #include "Parts.h"
 #include "Measure.h"
+#include "MarchingCubes.h"
 #include "Composite.h"
 #include "Projection.h"
 #include "Camera.h"
@@ -748,6 +749,48 @@ void rtoh_tris_take(void* list, float* out) {
     if (!tris) return;
     copy_tris(*tris, out, (int64_t)tris->size());
     delete tris;
+}
+// marchingCubesVolume (host/MarchingCubes.h), once: the list and its length; rtoh_tris_take copies it out and frees it
+void* rtoh_marching_cubes_volume(const float* field, int dimX, int dimY, int dimZ, const float origin[3], float spacing, float iso, int64_t* numTris) {
+    auto* list = new std::vector<MCTriangle>(marchingCubesVolume(field, dimX, dimY, dimZ, rto_host::vec3(origin[0], origin[1], origin[2]), spacing, iso));
+    *numTris = (int64_t)list->size();
+    return list;
+}
+// isoSurfaceVolume, once: a handle to the list and its tri_cell, their length in *numTris, RTO_OK or the refusal's code in *rc;
+// rtoh_iso_take copies both out (18 floats and one int32 per triangle; either may be NULL) and frees the handle
+struct IsoList {
+    std::vector<MCTriangle> tris;
+    std::vector<int32_t> cells;
+};
+void* rtoh_iso_surface_volume(const int32_t* volume, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize,
+                              const rto_iso_params* params, rto_iso_summary* summary, int* rc, int64_t* numTris) {
+    auto* list = new IsoList();
+    list->tris = isoSurfaceVolume(volume, dimX, dimY, dimZ, rto_host::vec3(gridMin[0], gridMin[1], gridMin[2]), voxelSize, *params, &list->cells,
+                                  summary, rc);
+    *numTris = (int64_t)list->tris.size();
+    return list;
+}
+void rtoh_iso_take(void* handle, float* tris, int32_t* cells) {
+    auto* list = static_cast<IsoList*>(handle);
+    if (!list) return;
+    copy_tris(list->tris, tris, (int64_t)list->tris.size());
+    if (cells && !list->cells.empty()) std::memcpy(cells, list->cells.data(), list->cells.size() * sizeof(int32_t));
+    delete list;
+}
+// the same, timed where it runs: the milliseconds of one extraction on one core; nothing is copied
+double rtoh_iso_surface_volume_ms(const int32_t* volume, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize,
+                                  const rto_iso_params* params, int64_t* numTris) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<MCTriangle> tris = isoSurfaceVolume(volume, dimX, dimY, dimZ, rto_host::vec3(gridMin[0], gridMin[1], gridMin[2]), voxelSize, *params);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (numTris) *numTris = (int64_t)tris.size();
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
+// RayTracerBVH::isoSurface / offsetSurface (source < 0: offsetSurface(level)), once, as rtoh_rt_extract_mesh
+void* rtoh_rt_iso_surface(RayTracerBVH* rt, int source, float level, float outside, int pad, const int32_t* volume, int64_t* numTris) {
+    auto* list = new std::vector<MCTriangle>(source < 0 ? rt->offsetSurface(level) : rt->isoSurface(source, level, outside, pad != 0, volume));
+    *numTris = (int64_t)list->size();
+    return list;
 }
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }

@@ -3,6 +3,12 @@
 
     python3 tools/mesh_export.py --sphere 128 --kind cubes out.stl
     python3 tools/mesh_export.py --cache sceneCache.bin --kind mc --camera 0.6 0.5 3500 --margin 50 out.stl
+    python3 tools/mesh_export.py --sphere 128 --iso distance 6.25 out.stl      # the offset surface 2.5 voxels off the solids
+
+--iso FIELD LEVEL contours a voxel field instead (Context.extract_isosurface): distance (squared, to the
+solids), interior (squared distance to the empty voxels) or thickness (squared, of the solids, balls up to 8 voxels), at LEVEL in
+the field's units; --no-pad leaves the surface open at the grid's faces.  Levels that are no field value (x.5, 6.25) give no
+degenerate triangle.
 
 Binary STL: an 80-byte header, a uint32 count, then 50 bytes per triangle -- normal, v0, v1, v2 as 12 float32 and a uint16 of
 zero: our (v0, v1, v2, normal) records reordered.  write_stl / read_stl are the round trip (read_stl returns our layout)."""
@@ -50,6 +56,8 @@ def main():
     ap.add_argument("--camera", type=float, nargs=3, metavar=("THETA", "PHI", "RADIUS"), help="cull with this orbit camera's frustum (fov 45)")
     ap.add_argument("--aspect", type=float, default=16.0 / 9.0)
     ap.add_argument("--margin", type=float, default=50.0)
+    ap.add_argument("--iso", nargs=2, metavar=("FIELD", "LEVEL"), help="the isosurface of distance, interior or thickness at LEVEL")
+    ap.add_argument("--no-pad", action="store_true", help="with --iso: no ring of outside samples around the grid")
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("out")
     args = ap.parse_args()
@@ -61,6 +69,24 @@ def main():
         sys.exit(f"cannot read {args.cache}")
     ctx = rto.Context(args.gpu)
     ctx.build_octree(grid.data, grid.min, grid.voxelSize)
+    if args.iso:
+        field, level = args.iso[0], float(args.iso[1])
+        if field == "distance":
+            ctx.distance_field(hip.SET_SOLID)
+            source, outside = hip.FIELD_DISTANCE, 1.0e9          # beyond the grid: far from every solid
+        elif field == "interior":
+            ctx.distance_field(hip.SET_EMPTY)
+            source, outside = hip.FIELD_DISTANCE, 0.0
+        elif field == "thickness":
+            ctx.thickness_field(hip.SET_SOLID, 8.0 * float(grid.voxelSize))
+            source, outside = hip.FIELD_THICKNESS, 0.0
+        else:
+            sys.exit(f"--iso: unknown field {field} (distance, interior, thickness)")
+        tris, _, summary = ctx.extract_isosurface(hip.make_iso_params(source, level, outside, pad=not args.no_pad))
+        write_stl(args.out, tris, b"ray_tracing_octrees_amd isosurface")
+        print(f"{args.out}: {len(tris)} triangles ({summary.degenerate} degenerate) in {summary.active_cells} cells, "
+              f"device ms (count, rank, emit) = {ctx.last_isosurface_ms()}")
+        return
     kind = hip.MESH_MC if args.kind == "mc" else hip.MESH_CUBES
     if kind == hip.MESH_MC:
         ctx.build_leaf_triangles()
