@@ -58,7 +58,7 @@ def triangles_of_samples(S, first, origin, spacing, level):
     cs = case[cz, cy, cx]
     n = TRI_COUNT[cs]
     rank = np.repeat(np.arange(len(cs)), n)                           # the cell of every triangle, in order
-    t = np.concatenate([np.arange(k) for k in n]) if len(n) else np.zeros(0, np.int64)
+    t = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)      # 0 .. k - 1 within each cell
     cell = np.stack([cx + first[0], cy + first[1], cz + first[2]], axis=1)[rank]
     local = np.stack([cx, cy, cz], axis=1)[rank]
     verts = np.zeros((len(rank), 9), F)
