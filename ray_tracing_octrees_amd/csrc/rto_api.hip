@@ -25,6 +25,38 @@ namespace rto { struct CcComp; }   // rto_components.inc
 enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldParts, kFieldCount };
 static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure", "part label" };
 
+// The stage timer of a frame family: the events around the N stages of its last frame, and whether that frame recorded them (not
+// under stream capture, not after rto_timing_begin(ctx, -1)).
+template <int N> struct StageEvents {
+    hipEvent_t ev[N + 1] = {};
+    bool timed = false;
+    bool ready() const { return ev[N] != nullptr; }
+    hipError_t ensure() {                                // creates the events once; the caller refuses it under capture
+        for (hipEvent_t& e : ev)
+            if (!e) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    // boundary k of the frame in flight; the last one settles what read() reports
+    hipError_t mark(int k, hipStream_t s, bool on) {
+        const hipError_t r = on ? hipEventRecord(ev[k], s) : hipSuccess;
+        if (k == N && r == hipSuccess) timed = on;
+        return r;
+    }
+    // the N intervals in ms; all -1 and RTO_OK when nothing was recorded, all -1 and RTO_E_HIP on any event error
+    int read(float* ms) const {
+        std::fill(ms, ms + N, -1.0f);
+        if (!timed) return RTO_OK;
+        if (hipEventSynchronize(ev[N]) != hipSuccess) return RTO_E_HIP;
+        for (int k = 0; k < N; k++)
+            if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess) {
+                std::fill(ms, ms + N, -1.0f);
+                return RTO_E_HIP;
+            }
+        return RTO_OK;
+    }
+    void destroy() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct rto_context {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -166,28 +198,25 @@ struct rto_context {
     size_t litCap = 0;
 
     // field views (rto_field_view.inc): the summary block of the frame in flight, the value buffer of callers that pass no d_values
-    // (frames of up to fvCap pixels) and the events around the two kernels of the last frame (fvTimed: they were recorded)
-    void* d_fvSum = nullptr;
+    // (frames of up to fvCap pixels) and the events around the two kernels of the last frame
+    unsigned char* d_fvSum = nullptr;
     int* d_fvValues = nullptr;
     size_t fvCap = 0;
-    hipEvent_t fvEv[3] = { nullptr, nullptr, nullptr };
-    bool fvTimed = false;
+    StageEvents<2> fvEv;
 
     // field projections (rto_project.inc): the brick table of the call in flight (pjBrickCap records), the events around the three
-    // kernels of the last frame (pjTimed: they were recorded) and whether the march consults the table (rto_debug_set_projection_table)
+    // kernels of the last frame and whether the march consults the table (rto_debug_set_projection_table)
     uint2* d_pjBricks = nullptr;
     size_t pjBrickCap = 0;
-    hipEvent_t pjEv[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool pjTimed = false;
+    StageEvents<3> pjEv;
     bool pjTable = true;
 
     // field compositing (rto_composite.inc): the solid table of the call in flight (one byte per brick, cpSolidCap of them), the
-    // summary block, and the events around the tables, the march and the fold of the last frame (cpTimed: they were recorded)
+    // summary block, and the events around the tables, the march and the fold of the last frame
     unsigned char* d_cpSolid = nullptr;
     size_t cpSolidCap = 0;
-    void* d_cpSum = nullptr;
-    hipEvent_t cpEv[4] = { nullptr, nullptr, nullptr, nullptr };
-    bool cpTimed = false;
+    unsigned char* d_cpSum = nullptr;
+    StageEvents<3> cpEv;
 
     // mesh extraction (rto_mesh.inc): the last mesh (a snapshot the context owns) and the first node of every tree level
     float4* d_mesh = nullptr;
@@ -436,12 +465,12 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_litCount);
     (void)hipFree(c->d_fvSum);
     (void)hipFree(c->d_fvValues);
-    for (hipEvent_t e : c->fvEv) if (e) (void)hipEventDestroy(e);
+    c->fvEv.destroy();
     (void)hipFree(c->d_pjBricks);
-    for (hipEvent_t e : c->pjEv) if (e) (void)hipEventDestroy(e);
+    c->pjEv.destroy();
     (void)hipFree(c->d_cpSolid);
     (void)hipFree(c->d_cpSum);
-    for (hipEvent_t e : c->cpEv) if (e) (void)hipEventDestroy(e);
+    c->cpEv.destroy();
     (void)hipFree(c->d_mesh);
     (void)hipFree(c->d_meshNode);
     (void)hipFree(c->d_iso);
@@ -3065,6 +3094,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_voxelize.inc"
 #include "rto_lit.inc"
 #include "rto_field_view.inc"
+#include "rto_voxel_walk.inc"
 #include "rto_project.inc"
 #include "rto_composite.inc"
 #include "rto_tri_lit.inc"

@@ -1,7 +1,9 @@
 // rto_field_view.inc -- field views (include/rto_hip.h, rto_render_field_*): a frame of the octree coloured by an int32 volume of the
 // resident grid (a resident field, the component labels or a caller's volume).  Included at the end of rto_api.hip, after
 // rto_lit.inc (lit_mix32, and of its frame pass tile_pixel, rooted_box_walk, kLargestBelow1e30, frame_bound_check and
-// frame_tree_check) and rto_query.inc (query_face).
+// frame_tree_check) and rto_query.inc (query_face).  Its host side also holds what the field projections and composites share
+// with it (field_frame_check and its pieces, work_buffer, stage_events, HostStage, misaligned); their voxel walk is
+// rto_voxel_walk.inc, the stage timer (StageEvents) rto_api.hip.
 //
 // Rule (DESIGN.md section 27).  The hit is the box query of view.mode on the frame's pixel ray in the window the clip box leaves;
 // the voxel of the hit is floor((p - gridMin) / voxelSize) of p = o + d tHit, clamped into the leaf (and the clip box), with the
@@ -248,52 +250,159 @@ static int field_view_volume(rto_context* c, const char* fn, int source, const i
     return rc;
 }
 
-// Every check of a field view, in the order the ABI promises; *volume: the int32 volume the frame samples.
+// ---- the refusals the volume entry points share (the field frames below; iso_check where its own promised order allows)
+static int check_valid_window(rto_context* c, const std::string& name, int lo, int hi) {
+    if (lo > hi || lo <= RTO_FIELD_PIXEL_NONE) return fail(c, RTO_E_INVALID, name + ": valid_lo must be above INT32_MIN + 1 and at most valid_hi");
+    return RTO_OK;
+}
+
+static int check_caller_volume(rto_context* c, const std::string& name, int source, const void* given) {
+    if (source == RTO_FIELD_CALLER && !given) return fail(c, RTO_E_INVALID, name + ": RTO_FIELD_CALLER needs a volume");
+    if (source != RTO_FIELD_CALLER && given) return fail(c, RTO_E_INVALID, name + ": a volume goes with RTO_FIELD_CALLER only");
+    return RTO_OK;
+}
+
+static int check_clip_box(rto_context* c, const std::string& name, int clip, const int* lo, const int* hi) {
+    if (clip)
+        for (int a = 0; a < 3; a++)
+            if (lo[a] < 0 || hi[a] > c->voxDim[a] || lo[a] >= hi[a])
+                return fail(c, RTO_E_INVALID, name + ": the clip box needs 0 <= clip_lo < clip_hi <= dim on every axis");
+    return RTO_OK;
+}
+
+// The range rule of views and projections.
+static int check_range_order(rto_context* c, const std::string& name, int lo, int hi) {
+    return lo > hi ? fail(c, RTO_E_INVALID, name + ": range_lo > range_hi") : RTO_OK;
+}
+
+// The preconditions of projections and composites: a resident grid whose voxel indices fit the int32 output `word` names.
+static int check_grid_index(rto_context* c, const std::string& name, const char* word) {
+    if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, name + ": no octree uploaded");
+    if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, name + ": the octree came from rto_upload_octree: no voxel grid is resident");
+    if (grid_voxels(c) > 0x7fffffffll)
+        return fail(c, RTO_E_UNSUPPORTED, name + ": the grid has 2^31 voxels or more: a voxel's index does not fit " + word);
+    return RTO_OK;
+}
+
+// Every check of a field frame, in the order the ABI promises to views, projections and composites alike; V is the family's struct
+// and `what` its name in the messages.  A family's own lines go into three slots: enums (after the source), range (after the valid
+// window) and pre (the tree and grid preconditions, after the caller's volume).  *volume: the int32 volume the frame reads.
+template <class V, class Enums, class Range, class Pre>
+static int field_frame_check(rto_context* c, const std::string& name, const char* what, const rto_frame* f, const V* v, const void* lut,
+                             const int32_t* d_volume, const void* rgba, const int** volume, Enums enums, Range range, Pre pre) {
+    if (!f || !v || !lut || !rgba) return fail(c, RTO_E_INVALID, name + ": NULL frame, " + what + ", LUT or output");
+    if (v->source < RTO_FIELD_DISTANCE || v->source > RTO_FIELD_CALLER) return fail(c, RTO_E_INVALID, name + ": unknown source " + std::to_string(v->source));
+    int rc = enums();
+    if (rc != RTO_OK) return rc;
+    if (v->scale < RTO_SCALE_LINEAR || v->scale > RTO_SCALE_CATEGORY) return fail(c, RTO_E_INVALID, name + ": unknown scale " + std::to_string(v->scale));
+    for (int r : v->reserved) if (r != 0) return fail(c, RTO_E_INVALID, name + ": " + what + ".reserved must be 0");
+    if ((rc = check_valid_window(c, name, v->valid_lo, v->valid_hi)) != RTO_OK || (rc = range()) != RTO_OK ||
+        (rc = frame_bound_check(c, name, f, 1)) != RTO_OK || (rc = check_caller_volume(c, name, v->source, d_volume)) != RTO_OK ||
+        (rc = pre()) != RTO_OK || (rc = check_clip_box(c, name, v->clip, v->clip_lo, v->clip_hi)) != RTO_OK)
+        return rc;
+    return field_view_volume(c, name.c_str(), v->source, d_volume, volume);
+}
+
 static int field_check(rto_context* c, const char* fn, const rto_frame* f, const rto_field_view* v, const void* lut, const int32_t* d_volume,
                        const void* rgba, const int** volume) {
     const std::string name(fn);
-    if (!f || !v || !lut || !rgba) return fail(c, RTO_E_INVALID, name + ": NULL frame, view, LUT or output");
-    if (v->source < RTO_FIELD_DISTANCE || v->source > RTO_FIELD_CALLER) return fail(c, RTO_E_INVALID, name + ": unknown source " + std::to_string(v->source));
-    if (v->sample != RTO_SAMPLE_HIT && v->sample != RTO_SAMPLE_FRONT) return fail(c, RTO_E_INVALID, name + ": unknown sample " + std::to_string(v->sample));
-    if (v->mode != RTO_QUERY_FIRST && v->mode != RTO_QUERY_CLOSEST)
-        return fail(c, RTO_E_INVALID, name + ": mode must be RTO_QUERY_FIRST or RTO_QUERY_CLOSEST");
-    if (v->scale < RTO_SCALE_LINEAR || v->scale > RTO_SCALE_CATEGORY) return fail(c, RTO_E_INVALID, name + ": unknown scale " + std::to_string(v->scale));
-    for (int r : v->reserved) if (r != 0) return fail(c, RTO_E_INVALID, name + ": view.reserved must be 0");
-    if (v->valid_lo > v->valid_hi || v->valid_lo <= RTO_FIELD_PIXEL_NONE)
-        return fail(c, RTO_E_INVALID, name + ": valid_lo must be above INT32_MIN + 1 and at most valid_hi");
-    if (v->range_lo > v->range_hi) return fail(c, RTO_E_INVALID, name + ": range_lo > range_hi");
-    int rc = frame_bound_check(c, name, f, 1);
-    if (rc != RTO_OK) return rc;
-    if (v->source == RTO_FIELD_CALLER && !d_volume) return fail(c, RTO_E_INVALID, name + ": RTO_FIELD_CALLER needs a volume");
-    if (v->source != RTO_FIELD_CALLER && d_volume) return fail(c, RTO_E_INVALID, name + ": a volume goes with RTO_FIELD_CALLER only");
-    if ((rc = frame_tree_check(c, name, true, ": a field view needs a canonical octree (descriptor tree)")) != RTO_OK) return rc;
-    if (v->clip)
-        for (int a = 0; a < 3; a++)
-            if (v->clip_lo[a] < 0 || v->clip_hi[a] > c->voxDim[a] || v->clip_lo[a] >= v->clip_hi[a])
-                return fail(c, RTO_E_INVALID, name + ": the clip box needs 0 <= clip_lo < clip_hi <= dim on every axis");
-    return field_view_volume(c, fn, v->source, d_volume, volume);
+    return field_frame_check(c, name, "view", f, v, lut, d_volume, rgba, volume,
+        [&] {
+            if (v->sample != RTO_SAMPLE_HIT && v->sample != RTO_SAMPLE_FRONT) return fail(c, RTO_E_INVALID, name + ": unknown sample " + std::to_string(v->sample));
+            if (v->mode != RTO_QUERY_FIRST && v->mode != RTO_QUERY_CLOSEST) return fail(c, RTO_E_INVALID, name + ": mode must be RTO_QUERY_FIRST or RTO_QUERY_CLOSEST");
+            return RTO_OK;
+        },
+        [&] { return check_range_order(c, name, v->range_lo, v->range_hi); },
+        [&] { return frame_tree_check(c, name, true, ": a field view needs a canonical octree (descriptor tree)"); });
 }
 
-// The work buffers of a field view, kept on the context under the lit render's rules: the summary block, the timing events and,
-// for a caller without d_values, a value buffer that grows with the frame.
-static int field_reserve(rto_context* c, const char* fn, size_t pixels, bool needValues, hipStream_t s) {
-    const bool grow = needValues && c->fvCap < pixels;
-    if (!grow && c->d_fvSum) return RTO_OK;
-    if (stream_is_capturing(s))
-        return fail(c, RTO_E_UNSUPPORTED, std::string(fn) + ": a larger frame allocates its work buffers; render one such frame "
-                                          "before hipStreamBeginCapture");
-    if (!c->d_fvSum) {
-        RTO_HIP(c, hipMalloc(&c->d_fvSum, kFieldSlots * sizeof(FieldSumRaw)));
-        for (hipEvent_t& e : c->fvEv) RTO_HIP(c, hipEventCreate(&e));
-    }
-    if (grow) {
-        (void)hipFree(c->d_fvValues); c->d_fvValues = nullptr;       // hipFree waits for the device: no frame still reads it
-        c->fvCap = 0;
-        RTO_HIP(c, hipMalloc(&c->d_fvValues, pixels * sizeof(int)));
-        c->fvCap = pixels;
-    }
+// ---- the work buffers a frame keeps on the context.  d must hold n elements: if it must grow and the stream is capturing, the call
+// is refused with fn + why; otherwise it is freed, allocated anew and its capacity recorded.
+template <class T>
+static int work_buffer(rto_context* c, T*& d, size_t& cap, size_t n, hipStream_t s, const char* fn, const char* why) {
+    if (cap >= n) return RTO_OK;
+    if (stream_is_capturing(s)) return fail(c, RTO_E_UNSUPPORTED, std::string(fn) + why);
+    (void)hipFree(d); d = nullptr;                       // hipFree waits for the device: no frame still reads it
+    cap = 0;
+    RTO_HIP(c, hipMalloc(&d, n * sizeof(T)));
+    cap = n;
     return RTO_OK;
 }
+
+// A family's stage timer, made on first use: creating events is refused under capture with the buffers.
+template <int N>
+static int stage_events(rto_context* c, StageEvents<N>& ev, hipStream_t s, const char* fn, const char* why) {
+    if (ev.ready()) return RTO_OK;
+    if (stream_is_capturing(s)) return fail(c, RTO_E_UNSUPPORTED, std::string(fn) + why);
+    RTO_HIP(c, ev.ensure());
+    return RTO_OK;
+}
+
+// The work buffers of a field view: the summary block, the timing events and, for a caller without d_values, a value buffer that
+// grows with the frame.
+static int field_reserve(rto_context* c, const char* fn, size_t pixels, bool needValues, hipStream_t s) {
+    const char* why = ": a larger frame allocates its work buffers; render one such frame before hipStreamBeginCapture";
+    size_t sumCap = c->d_fvSum ? sizeof(FieldSumRaw[kFieldSlots]) : 0;              // the summary block: of one size, made once
+    int rc = work_buffer(c, c->d_fvSum, sumCap, sizeof(FieldSumRaw[kFieldSlots]), s, fn, why);
+    if (rc == RTO_OK) rc = stage_events(c, c->fvEv, s, fn, why);
+    if (rc == RTO_OK && needValues) rc = work_buffer(c, c->d_fvValues, c->fvCap, pixels, s, fn, why);
+    return rc;
+}
+
+// ---- the _host forms' staging: the frame and the LUT on the device, the outputs the caller asked for, the caller's volume; what
+// was registered comes back in finish().  Device memory is the call's scratch.  The first HIP error sticks, with the call that
+// failed, and makes everything after it a no-op: status(), asked once before the frame runs, reports it.
+struct HostStage {
+    rto_context* c;
+    BuildScratch scratch;
+    size_t pixels;
+    hipError_t err = hipSuccess;
+    const char* failed = nullptr;                        // the call that gave err
+    struct Out { void* host; const void* dev; size_t bytes; };
+    std::vector<Out> outs;
+    float4* d_rgba;
+    unsigned* d_lut;
+
+    HostStage(rto_context* ctx, const rto_frame* f, const uint32_t* lut, float* host_rgba)
+        : c(ctx), scratch(ctx->stream), pixels((size_t)f->width * (size_t)f->height) {
+        d_rgba = optional(reinterpret_cast<float4*>(host_rgba), pixels);
+        d_lut = upload(reinterpret_cast<const unsigned*>(lut), 256);
+    }
+    template <class T> T* device(size_t count) {
+        T* d = nullptr;
+        if (err == hipSuccess && (err = scratch.alloc(&d, count)) != hipSuccess) failed = "hipMallocAsync of a staging buffer";
+        return d;
+    }
+    template <class T> void copy_in(T* d, const T* host, size_t count) {
+        if (err == hipSuccess && (err = hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+            failed = "hipMemcpyAsync of an input to its staging buffer";
+    }
+    template <class T> T* upload(const T* host, size_t count) {
+        T* d = device<T>(count);
+        copy_in(d, host, count);
+        return d;
+    }
+    // an output the caller may leave out: its device buffer, downloaded by finish(), or null
+    template <class T> T* optional(T* host, size_t count) {
+        if (!host) return nullptr;
+        T* d = device<T>(count);
+        outs.push_back({ host, d, count * sizeof(T) });
+        return d;
+    }
+    // the frame's volume: the caller's (RTO_FIELD_CALLER, the family's check), uploaded, or the resident one
+    const int* volume(const int32_t* host_volume, const int* resident) {
+        return host_volume ? upload(host_volume, (size_t)grid_voxels(c)) : resident;
+    }
+    int status() const { return err == hipSuccess ? RTO_OK : fail(c, RTO_E_HIP, std::string(failed) + ": " + hipGetErrorString(err)); }
+    int finish() {
+        for (const Out& o : outs) RTO_HIP(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c->stream));
+        RTO_HIP(c, hipStreamSynchronize(c->stream));
+        return RTO_OK;
+    }
+};
+
+// Is a pointer off the alignment its mask asks for?  (A null one is not.)
+static bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 static int render_field(rto_context* c, const char* fn, const rto_frame* f, const rto_field_view* v, const unsigned* d_lut, const int* volume,
                         float4* d_rgba, int32_t* d_values, rto_field_view_summary* d_summary, int64_t* d_bins, hipStream_t s) {
@@ -331,19 +440,18 @@ static int render_field(rto_context* c, const char* fn, const rto_frame* f, cons
     const bool timed = !(stream_is_capturing(s) || c->eventsOff);
     RTO_HIP(c, hipMemsetAsync(c->d_fvSum, 0, kFieldSlots * sizeof(FieldSumRaw), s));
     if (d_bins) RTO_HIP(c, hipMemsetAsync(d_bins, 0, 256 * sizeof(int64_t), s));
-    if (timed) RTO_HIP(c, hipEventRecord(c->fvEv[0], s));
+    RTO_HIP(c, c->fvEv.mark(0, s, timed));
     const size_t lds = desc_stack_bytes(P.depth);
     const int64_t tiles = (int64_t)P.tilesX * P.tilesY;
     const dim3 grid((unsigned)((tiles + kBlock / kWave - 1) / (kBlock / kWave)));
     if (v->mode == RTO_QUERY_FIRST) hipLaunchKernelGGL(k_field_sample<kQueryFirst>, grid, dim3(kBlock), lds, s, P, A, c->d_desc);
     else hipLaunchKernelGGL(k_field_sample<kQueryClosest>, grid, dim3(kBlock), lds, s, P, A, c->d_desc);
     RTO_HIP(c, hipGetLastError());
-    if (timed) RTO_HIP(c, hipEventRecord(c->fvEv[1], s));
+    RTO_HIP(c, c->fvEv.mark(1, s, timed));
     const int64_t blocks = std::min<int64_t>((int64_t)c->numCUs * 8, ((int64_t)pixels + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_field_shade, dim3((unsigned)blocks), dim3(kBlock), 0, s, S);
     RTO_HIP(c, hipGetLastError());
-    if (timed) RTO_HIP(c, hipEventRecord(c->fvEv[2], s));
-    c->fvTimed = timed;
+    RTO_HIP(c, c->fvEv.mark(2, s, timed));
     return RTO_OK;
 }
 
@@ -354,8 +462,8 @@ int rto_render_field_device(rto_context* c, const rto_frame* frame, const rto_fi
     if (!c) return RTO_E_INVALID;
     const char* fn = "rto_render_field_device";
     if (frame && view && d_lut && d_rgba &&
-        ((reinterpret_cast<uintptr_t>(d_rgba) & 15) || (reinterpret_cast<uintptr_t>(d_lut) & 3) || (reinterpret_cast<uintptr_t>(d_volume) & 3) ||
-         (reinterpret_cast<uintptr_t>(d_values) & 3) || (reinterpret_cast<uintptr_t>(d_summary) & 7) || (reinterpret_cast<uintptr_t>(d_bins) & 7)))
+        (misaligned(d_rgba, 15) || misaligned(d_lut, 3) || misaligned(d_volume, 3) || misaligned(d_values, 3) || misaligned(d_summary, 7) ||
+         misaligned(d_bins, 7)))
         return fail(c, RTO_E_INVALID, std::string(fn) + ": d_rgba must be 16-byte, d_summary and d_bins 8-byte, d_lut, d_volume and d_values 4-byte aligned");
     const int* volume = nullptr;
     const int rc = field_check(c, fn, frame, view, d_lut, d_volume, d_rgba, &volume);
@@ -372,44 +480,16 @@ int rto_render_field_host(rto_context* c, const rto_frame* frame, const rto_fiel
     int rc = field_check(c, fn, frame, view, lut, host_volume, host_rgba, &volume);
     if (rc != RTO_OK) return rc;
     RTO_HIP(c, hipSetDevice(c->device));
-    const size_t pixels = (size_t)frame->width * (size_t)frame->height;
-    BuildScratch scratch(c->stream);
-    float4* d_rgba = nullptr;
-    int32_t* d_values = nullptr;
-    unsigned* d_lut = nullptr;
-    rto_field_view_summary* d_summary = nullptr;
-    int64_t* d_bins = nullptr;
-    RTO_HIP(c, scratch.alloc(&d_rgba, pixels));
-    RTO_HIP(c, scratch.alloc(&d_lut, 256));
-    if (host_values) RTO_HIP(c, scratch.alloc(&d_values, pixels));
-    if (host_summary) RTO_HIP(c, scratch.alloc(&d_summary, 1));
-    if (host_bins) RTO_HIP(c, scratch.alloc(&d_bins, 256));
-    RTO_HIP(c, hipMemcpyAsync(d_lut, lut, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if (host_volume) {                                               // RTO_FIELD_CALLER (field_check)
-        int32_t* d_volume = nullptr;
-        RTO_HIP(c, scratch.alloc(&d_volume, (size_t)grid_voxels(c)));
-        RTO_HIP(c, hipMemcpyAsync(d_volume, host_volume, (size_t)grid_voxels(c) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        volume = d_volume;
-    }
-    if ((rc = render_field(c, fn, frame, view, d_lut, volume, d_rgba, d_values, d_summary, d_bins, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(host_rgba, d_rgba, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    if (host_values) RTO_HIP(c, hipMemcpyAsync(host_values, d_values, pixels * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (host_summary) RTO_HIP(c, hipMemcpyAsync(host_summary, d_summary, sizeof *host_summary, hipMemcpyDeviceToHost, c->stream));
-    if (host_bins) RTO_HIP(c, hipMemcpyAsync(host_bins, d_bins, 256 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    HostStage H(c, frame, lut, host_rgba);
+    int32_t* d_values = H.optional(host_values, H.pixels);
+    rto_field_view_summary* d_summary = H.optional(host_summary, 1);
+    int64_t* d_bins = H.optional(host_bins, 256);
+    volume = H.volume(host_volume, volume);
+    if ((rc = H.status()) != RTO_OK) return rc;
+    if ((rc = render_field(c, fn, frame, view, H.d_lut, volume, H.d_rgba, d_values, d_summary, d_bins, c->stream)) != RTO_OK) return rc;
+    return H.finish();
 }
 
-int rto_last_field_view_ms(const rto_context* c, float ms[2]) {
-    if (!c || !ms) return RTO_E_INVALID;
-    ms[0] = ms[1] = -1.0f;
-    if (!c->fvTimed) return RTO_OK;
-    if (hipEventSynchronize(c->fvEv[2]) != hipSuccess) return RTO_E_HIP;
-    if (hipEventElapsedTime(&ms[0], c->fvEv[0], c->fvEv[1]) != hipSuccess || hipEventElapsedTime(&ms[1], c->fvEv[1], c->fvEv[2]) != hipSuccess) {
-        ms[0] = ms[1] = -1.0f;
-        return RTO_E_HIP;
-    }
-    return RTO_OK;
-}
+int rto_last_field_view_ms(const rto_context* c, float ms[2]) { return c && ms ? c->fvEv.read(ms) : RTO_E_INVALID; }
 
 }  // extern "C"

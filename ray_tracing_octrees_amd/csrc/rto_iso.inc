@@ -345,20 +345,16 @@ static int iso_check(rto_context* c, const char* fn, const rto_iso_params* p, co
     if ((reinterpret_cast<uintptr_t>(given) & 3) != 0) return fail(c, RTO_E_INVALID, name + ": the volume must be 4-byte aligned");
     if (p->source < RTO_FIELD_DISTANCE || p->source > RTO_FIELD_CALLER) return fail(c, RTO_E_INVALID, name + ": unknown source " + std::to_string(p->source));
     for (int r : p->reserved) if (r != 0) return fail(c, RTO_E_INVALID, name + ": params.reserved must be 0");
-    if (p->valid_lo > p->valid_hi || p->valid_lo <= RTO_FIELD_PIXEL_NONE)
-        return fail(c, RTO_E_INVALID, name + ": valid_lo must be above INT32_MIN + 1 and at most valid_hi");
+    int rc = check_valid_window(c, name, p->valid_lo, p->valid_hi);
+    if (rc != RTO_OK) return rc;
     if (!std::isfinite(p->level) || !std::isfinite(p->outside)) return fail(c, RTO_E_INVALID, name + ": level and outside must be finite");
     if (p->pad != 0 && p->pad != 1) return fail(c, RTO_E_INVALID, name + ": pad must be 0 or 1");
-    if (p->source == RTO_FIELD_CALLER && !given) return fail(c, RTO_E_INVALID, name + ": RTO_FIELD_CALLER needs a volume");
-    if (p->source != RTO_FIELD_CALLER && given) return fail(c, RTO_E_INVALID, name + ": a volume goes with RTO_FIELD_CALLER only");
+    if ((rc = check_caller_volume(c, name, p->source, given)) != RTO_OK) return rc;
     if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, name + ": no octree uploaded");
     if (!c->d_vox) return fail(c, RTO_E_UNSUPPORTED, name + ": the octree came from rto_upload_octree: no voxel grid is resident");
     if (((int64_t)c->voxDim[0] + 1) * ((int64_t)c->voxDim[1] + 1) * ((int64_t)c->voxDim[2] + 1) >= 0x80000000ll)
         return fail(c, RTO_E_UNSUPPORTED, name + ": (dimX + 1)(dimY + 1)(dimZ + 1) is 2^31 or more: a cell's index does not fit tri_cell");
-    if (p->clip)
-        for (int a = 0; a < 3; a++)
-            if (p->clip_lo[a] < 0 || p->clip_hi[a] > c->voxDim[a] || p->clip_lo[a] >= p->clip_hi[a])
-                return fail(c, RTO_E_INVALID, name + ": the clip box needs 0 <= clip_lo < clip_hi <= dim on every axis");
+    if ((rc = check_clip_box(c, name, p->clip, p->clip_lo, p->clip_hi)) != RTO_OK) return rc;
     return field_view_volume(c, fn, p->source, given, volume);
 }
 

@@ -527,6 +527,150 @@ def test_gpu_the_device_form(ctx, orc):
 
 
 @gpu
+def test_gpu_untimed_and_captured_frames(orc):
+    """What the three field families share on the host and no other test runs: frames that record no events, and work buffers that
+    would have to grow inside a stream capture.  The "odd" grid's air field at 13 x 9 on a context of its own (its work buffers
+    must not exist yet), a MAX projection and an occluded composite against their statements bit for bit, a field view against
+    its own timed frame.  (1) A capture in which the brick table, then the solid table would have to be allocated: each call is
+    refused with RTO_E_UNSUPPORTED and its family's text, and the capture goes on.  (2) Frames captured in a HIP graph, tables on
+    and off: the replay is the statement, and rto_last_*_ms give -1.  (3) A camera with an infinite coordinate, the one miss rule
+    of the walk's entry that no frame meets otherwise: the statement's frame of misses.  (4) The host forms under
+    rto_timing_begin(ctx, -1): the statement, and -1 again.  (5) A second context whose first frames are a field view and a
+    composite: its first projection allocates nothing, so it may be captured, and replays to the statement."""
+    torch = pytest.importorskip("torch")
+    import ray_tracing_octrees_amd as rto
+    hip = _hip()
+    g = tp._odd()
+    W, H = 13, 9
+    n = W * H
+    c = rto.Context(0)
+    try:
+        _build(c, g)
+        vol = c.distance_field(hip.SET_SOLID)[0]
+        p = tp._proj(hip, hip.FIELD_DISTANCE, pr.MAX, valid=(1, 0x7ffffffe))
+        v = _comp(hip, hip.FIELD_DISTANCE, valid=(1, 0x7ffffffe), range=(1, 150), stop_q16=256, occlude=1)
+        fv = hip.make_field_view(hip.FIELD_DISTANCE, sample=hip.SAMPLE_FRONT)
+        view, pos, cells = tp._walks(orc, "odd", "outside", W, H, p)
+        f = tp._frame(view, pos, W, H)
+        want_p = pr.frame_of(cells, W, H, vol, p, tp._lut())
+        want_c = cr.frame_of(cells, W, H, vol, g, v, _lut("ramp"))
+        assert want_p[5]["valued"] >= 20 and want_c[5]["contributing"] >= 20 and want_c[5]["occluded"] >= 20
+        stream = torch.cuda.Stream()
+        sp = stream.cuda_stream
+        d_plut = torch.from_numpy(tp._lut().view(np.int32)).cuda()
+        d_clut = torch.from_numpy(_lut("ramp").view(np.int32)).cuda()
+        rgba_v, rgba_p, rgba_c = (torch.zeros(n * 4, dtype=torch.float32, device="cuda") for _ in range(3))
+        values, counts = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        torch.cuda.synchronize()
+
+        def field_view():
+            c.render_field_device(f, fv, d_plut.data_ptr(), rgba_v.data_ptr(), stream=sp)
+
+        def projection():
+            c.project_field_device(f, p, d_plut.data_ptr(), rgba_p.data_ptr(), d_values=values.data_ptr(), stream=sp)
+
+        def composite():
+            c.composite_field_device(f, v, d_clut.data_ptr(), rgba_c.data_ptr(), d_counts=counts.data_ptr(), stream=sp)
+
+        def replayed(graph, *checks):
+            for t in (rgba_v, rgba_p, rgba_c, values, counts):
+                t.fill_(7)
+            graph.replay()
+            torch.cuda.synchronize()
+            for check in checks:
+                check()
+
+        def is_view():
+            assert rgba_v.cpu().numpy().tobytes() == timed_view
+
+        def is_projection():
+            assert rgba_p.cpu().numpy().tobytes() == want_p[0].tobytes() and np.array_equal(values.cpu().numpy().reshape(H, W), want_p[1])
+
+        def is_composite():
+            assert rgba_c.cpu().numpy().tobytes() == want_c[0].tobytes() and np.array_equal(counts.cpu().numpy().reshape(H, W), want_c[4])
+
+        field_view()                                         # the ray tables and the views' buffers; no brick table yet
+        stream.synchronize()
+        timed_view = rgba_v.cpu().numpy().tobytes()
+        assert all(m > 0 for m in c.last_field_view_ms()) and timed_view != bytes(len(timed_view))
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(stream):
+            with torch.cuda.graph(graph, stream=stream):
+                with pytest.raises(rto.RtoError) as e:
+                    projection()
+                field_view()
+        assert e.value.code == hip.RTO_E_UNSUPPORTED and "rto_project_field_device: a larger grid allocates the brick table" in str(e.value)
+        assert c.last_field_view_ms() == (-1.0, -1.0)
+        replayed(graph, is_view)
+        projection()
+        stream.synchronize()
+        is_projection()
+        assert all(m > 0 for m in c.last_projection_ms())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(stream):
+            with torch.cuda.graph(graph, stream=stream):
+                with pytest.raises(rto.RtoError) as e:
+                    composite()
+                projection()
+        assert e.value.code == hip.RTO_E_UNSUPPORTED and "rto_composite_field_device: a larger grid allocates the solid table" in str(e.value)
+        assert c.last_projection_ms() == (-1.0, -1.0, -1.0)
+        replayed(graph, is_projection)
+        composite()
+        stream.synchronize()
+        is_composite()
+        assert all(m > 0 for m in c.last_composite_ms())
+        for table in (True, False):
+            c.debug_set_projection_table(table)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(stream):
+                with torch.cuda.graph(graph, stream=stream):
+                    field_view()
+                    projection()
+                    composite()
+            assert c.last_composite_ms() == c.last_projection_ms() == (-1.0, -1.0, -1.0) and c.last_field_view_ms() == (-1.0, -1.0)
+            replayed(graph, is_view, is_projection, is_composite)
+        del graph
+        far = np.array(pos, np.float32)
+        far[1] = np.inf                                      # a camera that is nowhere: every pixel misses by the walk's first rule
+        none = pr.walks(tp.GMIN, tp.VOX, tp._dims(g), far, tp._rays(orc, view, far, W, H), None)
+        assert len(none) == n and not any(none)
+        ff = tp._frame(view, far, W, H)
+        tp._same(c.project_field_host(ff, p, tp._lut()), pr.frame_of(none, W, H, vol, p, tp._lut()), "a camera at infinity")
+        _same(c.composite_field_host(ff, v, _lut("ramp")), cr.frame_of(none, W, H, vol, g, v, _lut("ramp")), "a camera at infinity")
+        c.timing_begin(-1)
+        for table in (True, False):
+            c.debug_set_projection_table(table)
+            tp._same(c.project_field_host(f, p, tp._lut()), want_p, f"no events, table {table}")
+            _same(c.composite_field_host(f, v, _lut("ramp")), want_c, f"no events, table {table}")
+            assert c.render_field_host(f, fv, tp._lut())[0].tobytes() == timed_view
+            assert c.last_composite_ms() == c.last_projection_ms() == (-1.0, -1.0, -1.0) and c.last_field_view_ms() == (-1.0, -1.0)
+    finally:
+        c.close()
+    # (5) on a second context: the composite makes the brick table, so the projections' events have to come with it
+    c = rto.Context(0)
+    try:
+        _build(c, g)
+        c.distance_field(hip.SET_SOLID)
+        field_view()
+        composite()
+        stream.synchronize()
+        is_composite()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(stream):
+            with torch.cuda.graph(graph, stream=stream):
+                projection()
+        assert c.last_projection_ms() == (-1.0, -1.0, -1.0)
+        replayed(graph, is_projection)
+        del graph
+        projection()
+        stream.synchronize()
+        is_projection()
+        assert all(m > 0 for m in c.last_projection_ms())
+    finally:
+        c.close()
+
+
+@gpu
 def test_gpu_an_edit_drops_the_named_sources_and_renews_the_tables(ctx, orc):
     """After an rto_edit_voxels with changed > 0 every named source is refused in its readers' words; a CALLER composite with
     occlusion is the statement on the edited grid (the solid table is the new grid's); after the field is made again the composite
