@@ -57,6 +57,55 @@ template <int N> struct StageEvents {
     void destroy() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// The kernel timer of the octree and triangle frames: an event pair around the traversal kernel(s) of every launch that records one,
+// taken from the ring of rto_timing_begin while that has a free slot (rto_timing_read), else ev0 / ev1.
+struct KernelTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<hipEvent_t> ring;                    // start, stop, start, stop ...: the first ringUsed pairs are recorded
+    size_t ringUsed = 0;
+    hipEvent_t openA = nullptr, openB = nullptr;     // the interval that is open (nullptr: none, or one that records nothing)
+    hipEvent_t lastA = nullptr, lastB = nullptr;     // the interval closed last: what rto_last_kernel_ms reads while `timed`
+    bool timed = false;
+
+    hipError_t create() { const hipError_t e = hipEventCreate(&ev0); return e != hipSuccess ? e : hipEventCreate(&ev1); }
+    void destroy() { (void)reset_ring(0); if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); }
+    // drops the ring and makes one of `capacity` pairs; the caller has waited for the device
+    hipError_t reset_ring(int capacity) {
+        for (hipEvent_t e : ring) (void)hipEventDestroy(e);
+        ring.clear(); ringUsed = 0; openA = openB = nullptr; lastA = ev0; lastB = ev1;
+        for (int i = 0; i < 2 * capacity; i++) {
+            hipEvent_t e = nullptr;
+            const hipError_t r = hipEventCreate(&e);
+            if (r != hipSuccess) return r;
+            ring.push_back(e);
+        }
+        return hipSuccess;
+    }
+    // Opens an interval on `s`, in front of the kernel(s) it is to bracket.  record == false (a stream being captured: events recorded
+    // inside a capture cannot be timed; rto_timing_begin(ctx, -1): each record costs ~2 us between launches): nothing is recorded and no
+    // ring slot is taken.  A slot is taken by the record itself: a launch that is refused before it leaves the ring alone.
+    hipError_t open(hipStream_t s, bool record) {
+        openA = openB = nullptr;
+        if (!record) return hipSuccess;
+        const bool slot = 2 * ringUsed + 1 < ring.size();
+        const hipEvent_t a = slot ? ring[2 * ringUsed] : ev0;
+        const hipError_t e = hipEventRecord(a, s);
+        if (e != hipSuccess) return e;
+        openA = a; openB = slot ? ring[2 * ringUsed + 1] : ev1;
+        ringUsed += slot ? 1 : 0;
+        return hipSuccess;
+    }
+    // Closes it behind the kernel(s): from here on rto_last_kernel_ms reads this interval, or refuses if it recorded nothing.
+    hipError_t close(hipStream_t s) {
+        if (openB) { const hipError_t e = hipEventRecord(openB, s); if (e != hipSuccess) return e; }
+        lastA = openA; lastB = openB; timed = openB != nullptr;
+        openA = openB = nullptr;
+        return hipSuccess;
+    }
+    // ev1 as an ordering point of the caller's own (rto_comm): the last launch's interval is no longer readable
+    hipEvent_t borrow_stop() { timed = false; return ev1; }
+};
+
 struct rto_context {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -176,13 +225,8 @@ struct rto_context {
     int* d_steps = nullptr;
     size_t stepsCap = 0;
     Counters* d_counters = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    KernelTimer timer;
     bool eventsOff = false;    // rto_timing_begin(ctx, -1): no hipEventRecord around the traversal kernels at all
-    // optional ring of event pairs, one per traversal-kernel launch (rto_timing_begin / rto_timing_read)
-    std::vector<hipEvent_t> ringStart, ringStop;
-    size_t ringUsed = 0;
-    hipEvent_t lastA = nullptr, lastB = nullptr;
     float buildMs = -1.f;      // device time of the last rto_build_octree (pyramid + emission kernels)
     bool descPooled = false;   // d_descFirstChild lives in d_desc's allocation (Morton-order build)
     bool asyncPooled = false;  // d_nodes / d_desc come from the stream-ordered memory pool (hipMallocAsync): a rebuild reuses them without hipMalloc
@@ -429,7 +473,7 @@ int rto_create(int device_ordinal, rto_context** out) {
         return fail(nullptr, RTO_E_NO_DEVICE, msg);
     }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess ||
+        (e = c->timer.create()) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->evCull, hipEventDisableTiming)) != hipSuccess ||
         (e = hipMalloc(&c->d_counters, sizeof(Counters))) != hipSuccess ||
         (e = hipMalloc(&c->d_visibleCount, 2 * sizeof(int64_t))) != hipSuccess ||     // [0] count of visible nodes, [1] the root's flag
@@ -475,10 +519,7 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_meshNode);
     (void)hipFree(c->d_iso);
     (void)hipFree(c->d_isoCell);
-    for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ringStop) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    c->timer.destroy();
     if (c->evCull) (void)hipEventDestroy(c->evCull);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2098,35 +2139,48 @@ static size_t lds_for_occupancy(size_t lds, int wavesDefault) {
     return std::max(lds, std::min<size_t>(perGroup, 64 * 1024));
 }
 
+// The stacks of a lean launch in LDS: one 8-byte entry per lane and level for each wave of the workgroup (+1: the dummy entry).
+static size_t lean_stack_bytes(int path, int depth) { return (size_t)lean_wpb(path) * (depth + 1) * kWave * sizeof(uint2); }
+
+// What a frame launcher does first on its stream `s`: a stream other than the context's is noted for the next update of the
+// visibility state (wait_for_other_streams), the launch is ordered behind the last one (order_after_cull), and -- where the
+// launcher asks -- the one capture test of the launch is made.
+static int launch_prologue(rto_context* c, hipStream_t s, bool* capturing = nullptr) {
+    if (s != c->stream) c->otherStreams = true;
+    const int rc = order_after_cull(c, s);
+    if (rc == RTO_OK && capturing) *capturing = stream_is_capturing(s);
+    return rc;
+}
+
+// Does rto_set_kernel's choice put an octree frame on the descriptors (any packed kernel) rather than on the 60-byte nodes?
+static bool packed_selected(const rto_context* c) {
+    return c->kernelMode >= RTO_KERNEL_PACKED || (c->kernelMode == RTO_KERNEL_AUTO && c->canonical);
+}
+
 template <int MODE>
 static int launch_trace(rto_context* c, const RenderParams& P, float4* d_out, hipStream_t s) {
-    if (s != c->stream) c->otherStreams = true;
-    { const int rcOrder = order_after_cull(c, s); if (rcOrder != RTO_OK) return rcOrder; }
+    bool capturing = false;
+    { const int rcOrder = launch_prologue(c, s, &capturing); if (rcOrder != RTO_OK) return rcOrder; }
     const int tiles = P.tilesX * P.tilesY;
     if (tiles <= 0) return RTO_OK;
     const int blocks = (tiles + (kBlock / kWave) - 1) / (kBlock / kWave);
-    const bool packed = c->kernelMode >= RTO_KERNEL_PACKED || (c->kernelMode == RTO_KERNEL_AUTO && c->canonical);
+    const bool packed = packed_selected(c);
     if (packed && !c->canonical) return fail(c, RTO_E_UNSUPPORTED, "render: packed kernel needs a canonical BFS octree");
-    const bool capturing = stream_is_capturing(s);
     if (capturing && s != c->stream) c->foreignCaptured = true;
-    const bool noEvents = capturing || c->eventsOff;     // events inside a capture cannot be timed; each record costs ~2 us between launches
-    bool stopRecorded = false;
-    hipEvent_t evA = c->ev0, evB = c->ev1;
-    // a timing-ring slot is only taken by a launch that records events (events inside a capture cannot be timed)
-    if (!noEvents && c->ringUsed < c->ringStart.size()) { evA = c->ringStart[c->ringUsed]; evB = c->ringStop[c->ringUsed]; c->ringUsed++; }
-    bool startRecorded = false;
+    const bool record = !(capturing || c->eventsOff);
     // The lean kernels take the result of a frustum update from the device (StartState: visible at all? start at the root
     // or -- root culled, descendants visible, S/RT:765-812 -- at the first visible node): nothing to know on the host.
     // Every other kernel needs the host's copy; for them the culled-root edge goes to the generic kernel over the compacted array.
-    const bool leanKernel = packed && c->canonical && (c->kernelMode == RTO_KERNEL_AUTO || c->kernelMode == RTO_KERNEL_PACKED || c->kernelMode == RTO_KERNEL_PACKED_PERSISTENT);
+    const bool v1 = c->kernelMode == RTO_KERNEL_PACKED_V1, v3 = c->kernelMode == RTO_KERNEL_PACKED_V3;
+    const bool persistentMode = c->kernelMode == RTO_KERNEL_PACKED_PERSISTENT;
+    const bool leanKernel = packed && !v1 && !v3;             // k_trace_lean and its persistent form (packed: the tree is canonical)
     const bool deviceStart = leanKernel && c->culling && c->cullAsync;
     if (c->culling && !deviceStart) { const int rcState = sync_cull_state(c); if (rcState != RTO_OK) return rcState; }
     const bool rootCulledEdge = !deviceStart && c->culling && !c->rootVisible && c->visibleNodes > 0;
     if (packed && !rootCulledEdge) {
         const size_t ldsStacks = (size_t)(kBlock / kWave) * (P.depth + 1) * kWave * sizeof(uint2);   // +1: the lean kernel's dummy entry
-        if (c->kernelMode == RTO_KERNEL_PACKED_V1) {
-            if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));
-            startRecorded = true;
+        if (v1) {
+            RTO_HIP(c, c->timer.open(s, record));
             RenderParams Q = P;
             Q.rootVisible = c->rootVisible;                 // as of sync_cull_state above
             hipLaunchKernelGGL(k_trace_packed<MODE>, dim3(blocks), dim3(kBlock), ldsStacks, s, Q, c->d_desc, d_out, c->d_steps, c->d_counters);
@@ -2137,23 +2191,21 @@ static int launch_trace(rto_context* c, const RenderParams& P, float4* d_out, hi
             const bool frameMode = MODE == kModeColor || MODE == kModeShade;
             rto_context::OrderState* st = nullptr;
             const int solidRect[4] = { P.solidX0, P.solidY0, P.solidX1, P.solidY1 };
+            const bool maskable = leanKernel && !persistentMode;      // k_trace_lean itself: the occupancy mask and the LDS padding are its own
             {
-                const bool maskable = leanKernel && c->kernelMode != RTO_KERNEL_PACKED_PERSISTENT;
                 const int rc = prepare_schedule(c, s, capturing, frameMode, MODE == kModeTimeline, 0, solidRect, Q, &st, maskable ? 0 : -1, true);
                 if (rc != RTO_OK) return rc;
             }
             const int lblocks = (Q.launchWaves + (kBlock / kWave) - 1) / (kBlock / kWave);
             const int lblocksLean = (Q.launchWaves + lean_wpb(0) - 1) / lean_wpb(0);
-            const size_t ldsLean = (size_t)lean_wpb(0) * (P.depth + 1) * kWave * sizeof(uint2);
+            const size_t ldsLean = lean_stack_bytes(0, P.depth);
             // 5 resident waves per SIMD when the frame's waves with work would all be resident at once at 6 (see lds_for_occupancy): about
             // 40 % of the box's tiles have work behind the mask, so up to 3 x the machine's slots at 6 per SIMD.
             const bool fewWaves = Q.traceWaves <= 3 * 6 * 4 * c->numCUs;
-            const size_t lds = Q.tileMask ? lds_for_occupancy(ldsLean, fewWaves ? 5 : 0) : (leanKernel && !(c->kernelMode == RTO_KERNEL_PACKED_PERSISTENT) ? lds_for_occupancy(ldsLean, 0) : ldsStacks);
+            const size_t lds = Q.tileMask ? lds_for_occupancy(ldsLean, fewWaves ? 5 : 0) : (maskable ? lds_for_occupancy(ldsLean, 0) : ldsStacks);
             Q.maskLdsBytes = (int)lds;
-            if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));        // after the order kernel: the pair brackets the traversal kernel alone
-            startRecorded = true;
-            const bool persistent = c->kernelMode == RTO_KERNEL_PACKED_PERSISTENT && st && frameMode;
-            if (persistent) {
+            RTO_HIP(c, c->timer.open(s, record));        // after the order kernel: the pair brackets the traversal kernel alone
+            if (persistentMode && st && frameMode) {
                 if (!st->d_queue) {
                     if (capturing)
                         return fail(c, RTO_E_UNSUPPORTED, "render: the first persistent-kernel frame on a stream allocates its slot counter; "
@@ -2167,7 +2219,7 @@ static int launch_trace(rto_context* c, const RenderParams& P, float4* d_out, hi
                 const int resident = c->numCUs * RTO_PERSIST_WAVES;
                 hipLaunchKernelGGL(k_trace_lean_persistent<MODE>, dim3(std::min(lblocks, resident)), dim3(kBlock), lds, s, Q, c->d_desc, d_out,
                                    c->d_steps, c->d_counters, st->d_queue);
-            } else if (c->kernelMode == RTO_KERNEL_PACKED_V3) {
+            } else if (v3) {
                 hipLaunchKernelGGL(k_trace_packed3<MODE>, dim3(lblocks), dim3(kBlock), lds, s, Q, c->d_desc, d_out, c->d_steps, c->d_counters);
             } else {
                 // maskMode 2 (tests): a launch of the mask workgroups alone first, so that every wave of the frame finds the mask complete
@@ -2186,15 +2238,11 @@ static int launch_trace(rto_context* c, const RenderParams& P, float4* d_out, hi
         RenderParams Q = P;
         if (c->culling && c->visibleNodes == 0) Q.rootVisible = 0;   // empty SSBO: nothing to traverse
         else if (c->culling) Q.rootVisible = 1;                      // compacted index 0 is whatever survived first (S/RT:765-772)
-        if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));
-        startRecorded = true;
+        RTO_HIP(c, c->timer.open(s, record));
         hipLaunchKernelGGL(k_trace_generic<MODE>, dim3(blocks), dim3(kBlock), 0, s, Q, nodes, d_out, c->d_steps, c->d_counters);
     }
     RTO_HIP(c, hipGetLastError());
-    (void)startRecorded;
-    if (!stopRecorded && !noEvents) RTO_HIP(c, hipEventRecord(evB, s));
-    if (evA != c->ev0) { c->lastA = evA; c->lastB = evB; } else { c->lastA = c->ev0; c->lastB = c->ev1; }
-    c->timed = !noEvents;
+    RTO_HIP(c, c->timer.close(s));
     return RTO_OK;
 }
 
@@ -2241,51 +2289,33 @@ static int build_triangle_records(rto_context* c, hipStream_t s) {
     return RTO_OK;
 }
 
-// The batch kernels put (mask workgroups per frame) x (frames) workgroups in front of the grid: every frame of a batch brings
-// its mask, or none does (a frame skipped by the loop above, a degenerate projection).
-static void batch_mask_all_or_none(RenderBatch& B) {
-    bool all = true;
-    for (int i = 0; i < B.n; i++) all = all && B.P[i].tileMask != nullptr && B.P[i].maskBlocks == B.P[0].maskBlocks;
-    if (all) return;
-    for (int i = 0; i < B.n; i++) { B.P[i].tileMask = nullptr; B.P[i].maskBlocks = 0; }
-}
-
-// n frames (n <= kMaxBatch) in one launch of k_trace_lean_batch; falls back to n launches when the lean kernel is not the
-// one in use (generic array, another kernel selected, the culled-root edge).  MODE: kModeColor or kModeShade.
-template <int MODE>
-static int launch_trace_batch(rto_context* c, const RenderParams* Ps, int n, float4* const* outs, hipStream_t s) {
-    if (s != c->stream) c->otherStreams = true;
-    const bool packed = c->kernelMode >= RTO_KERNEL_PACKED || (c->kernelMode == RTO_KERNEL_AUTO && c->canonical);
-    const bool lean = packed && c->canonical && (c->kernelMode == RTO_KERNEL_AUTO || c->kernelMode == RTO_KERNEL_PACKED) &&
-                      (!c->culling || c->cullAsync);
-    bool sameDepth = true;
-    for (int i = 1; i < n; i++) sameDepth = sameDepth && Ps[i].depth == Ps[0].depth;
-    if (!lean || n == 1 || !sameDepth) {
-        for (int i = 0; i < n; i++) {
-            const int rc = launch_trace<MODE>(c, Ps[i], outs[i], s);
-            if (rc != RTO_OK) return rc;
-        }
-        return RTO_OK;
-    }
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && s != c->stream) c->foreignCaptured = true;
-    { const int rcOrder = order_after_cull(c, s); if (rcOrder != RTO_OK) return rcOrder; }
-    const bool noEvents = capturing || c->eventsOff;
+// One launch of a lean batch kernel for n <= kMaxBatch frames on path 0 (octree) / 1 (triangles): what the two batch launchers share.
+// Theirs are `fill` (frame i's parameters: the octree form copies its caller's and patches them under culling, the triangle form
+// makes them), the LDS bytes for a tree depth and `launch` (their kernel on a grid of so many workgroups).
+template <class Fill, class Lds, class Launch>
+static int launch_batch(rto_context* c, hipStream_t s, int path, int n, float4* const* outs, const Fill& fill, const Lds& ldsFor, const Launch& launch) {
+    bool capturing = false;
+    { const int rcOrder = launch_prologue(c, s, &capturing); if (rcOrder != RTO_OK) return rcOrder; }
+    if (path == 0 && capturing && s != c->stream) c->foreignCaptured = true;       // the octree first-hit frames only: docs/LAB_NOTES.md
     RenderBatch B;
     B.n = n;
     int maxWaves = 0;
     rto_context::OrderState* st = nullptr;
     for (int i = 0; i < n; i++) {
-        B.P[i] = Ps[i];
-        if (c->culling) { B.P[i].start = c->d_start; B.P[i].rootVisible = 1; }     // the frustum update's result stays on the device (launch_trace)
-        B.out[i] = outs[i];
-        if (Ps[i].tilesX * Ps[i].tilesY <= 0) { B.P[i].launchWaves = 0; continue; }
-        const int solidRect[4] = { Ps[i].solidX0, Ps[i].solidY0, Ps[i].solidX1, Ps[i].solidY1 };
-        const int rc = prepare_schedule(c, s, capturing, true, false, 0, solidRect, B.P[i], &st, i);
+        int rc = fill(i, B.P[i]);
         if (rc != RTO_OK) return rc;
+        B.out[i] = outs[i];
+        if (B.P[i].tilesX * B.P[i].tilesY <= 0) { B.P[i].launchWaves = 0; continue; }
+        const int solidRect[4] = { B.P[i].solidX0, B.P[i].solidY0, B.P[i].solidX1, B.P[i].solidY1 };
+        if ((rc = prepare_schedule(c, s, capturing, true, false, path, solidRect, B.P[i], &st, i)) != RTO_OK) return rc;
         maxWaves = std::max(maxWaves, B.P[i].launchWaves);
     }
-    batch_mask_all_or_none(B);
+    // The batch kernels put (mask workgroups per frame) x (frames) workgroups in front of the grid: every frame of a batch brings
+    // its mask, or none does (a frame skipped by the loop above, a degenerate projection).
+    bool all = true;
+    for (int i = 0; i < n; i++) all = all && B.P[i].tileMask != nullptr && B.P[i].maskBlocks == B.P[0].maskBlocks;
+    if (!all)
+        for (int i = 0; i < n; i++) { B.P[i].tileMask = nullptr; B.P[i].maskBlocks = 0; }
     // the frames share this stream's launch-order table: its entries are relative to the box's corner, so it serves every
     // frame whose box has the size of the one it was last rebuilt for (a moving camera shifts the box far more often than
     // it resizes it); any other box falls back to the centre-out order (any permutation of a frame's own box renders it)
@@ -2296,22 +2326,79 @@ static int launch_trace_batch(rto_context* c, const RenderParams* Ps, int n, flo
         B.P[i].tileOrder = fits ? T.d : nullptr;
     }
     if (maxWaves <= 0) return RTO_OK;
-    hipEvent_t evA = c->ev0, evB = c->ev1;
-    if (!noEvents && c->ringUsed < c->ringStart.size()) { evA = c->ringStart[c->ringUsed]; evB = c->ringStop[c->ringUsed]; c->ringUsed++; }
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));
-    const size_t lds = lds_for_occupancy((size_t)lean_wpb(0) * (Ps[0].depth + 1) * kWave * sizeof(uint2), 0);
+    RTO_HIP(c, c->timer.open(s, !(capturing || c->eventsOff)));
+    const size_t lds = ldsFor(B.P[0].depth);
     for (int i = 0; i < n; i++) B.P[i].maskLdsBytes = (int)lds;
     const long long waves = (long long)maxWaves * n;
+    const unsigned maskGroups = (unsigned)(B.P[0].maskBlocks * n);
+    if (c->maskMode == 2 && maskGroups > 0) launch(maskGroups, lds, B, true);       // tests: the masks complete before any frame wave looks
+    launch((unsigned)((waves + lean_wpb(path) - 1) / lean_wpb(path)) + maskGroups, lds, B, false);
+    RTO_HIP(c, hipGetLastError());
+    RTO_HIP(c, c->timer.close(s));
+    return RTO_OK;
+}
+
+// n frames (n <= kMaxBatch) in one launch of k_trace_lean_batch; falls back to n launches when the lean kernel is not the
+// one in use (generic array, another kernel selected, the culled-root edge).  MODE: kModeColor or kModeShade.
+template <int MODE>
+static int launch_trace_batch(rto_context* c, const RenderParams* Ps, int n, float4* const* outs, hipStream_t s) {
+    const bool lean = packed_selected(c) && c->canonical && (c->kernelMode == RTO_KERNEL_AUTO || c->kernelMode == RTO_KERNEL_PACKED) &&
+                      (!c->culling || c->cullAsync);
+    bool sameDepth = true;
+    for (int i = 1; i < n; i++) sameDepth = sameDepth && Ps[i].depth == Ps[0].depth;
+    if (!lean || n == 1 || !sameDepth) {
+        for (int i = 0; i < n; i++) {
+            const int rc = launch_trace<MODE>(c, Ps[i], outs[i], s);
+            if (rc != RTO_OK) return rc;
+        }
+        return RTO_OK;
+    }
+    const auto fill = [&](int i, RenderParams& P) {
+        P = Ps[i];
+        if (c->culling) { P.start = c->d_start; P.rootVisible = 1; }     // the frustum update's result stays on the device (launch_trace)
+        return (int)RTO_OK;
+    };
     // the batch kernel keeps the run-time flag: with waves of several frames to fill every SIMD, its one build (all five child-test forms
     // in the loop) measured 1.5-3 % FASTER than the two builds that pay for single frames (4 frames per launch: 0.0259 against 0.0270 ms)
-    auto* kern = k_trace_lean_batch<MODE, -1>;
-    if (c->maskMode == 2 && B.P[0].maskBlocks > 0)
-        hipLaunchKernelGGL(kern, dim3((unsigned)(B.P[0].maskBlocks * n)), dim3(lean_block(0)), lds, s, B, c->d_desc);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((waves + lean_wpb(0) - 1) / lean_wpb(0)) + (unsigned)(B.P[0].maskBlocks * n)), dim3(lean_block(0)), lds, s, B, c->d_desc);
-    RTO_HIP(c, hipGetLastError());
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evB, s));
-    c->lastA = evA; c->lastB = evB;                       // what rto_last_kernel_ms reads
-    c->timed = !noEvents;
+    return launch_batch(c, s, 0, n, outs, fill, [](int depth) { return lds_for_occupancy(lean_stack_bytes(0, depth), 0); },
+                        [&](unsigned groups, size_t lds, const RenderBatch& B, bool) {
+                            hipLaunchKernelGGL((k_trace_lean_batch<MODE, -1>), dim3(groups), dim3(lean_block(0)), lds, s, B, c->d_desc);
+                        });
+}
+
+// The host form of a frame family: `launch` renders the frame of `f` into c->d_frame on the context's stream, with the counters
+// zeroed in front of it when `stats` are wanted; the frame (and the counters) come back, the stream is waited for.
+template <class Launch>
+static int render_to_host(rto_context* c, const rto_frame* f, float* host_rgba, rto_stats* stats, const Launch& launch) {
+    const size_t pixels = (size_t)f->width * f->height;
+    int rc = ensure_frame(c, pixels);
+    if (rc != RTO_OK) return rc;
+    if (stats) RTO_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
+    if ((rc = launch()) != RTO_OK) return rc;
+    Counters h{ 0, 0, 0 };
+    if (stats) RTO_HIP(c, hipMemcpyAsync(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipMemcpyAsync(host_rgba, c->d_frame, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RTO_HIP(c, hipStreamSynchronize(c->stream));
+    if (stats) { stats->rays = pixels; stats->pops = h.pops; stats->hits = h.hits; stats->capped = 0; }
+    return RTO_OK;
+}
+
+// The batch entry points: n frames of one size, frame i at d_out + i * frame_stride_bytes, kMaxBatch of them per `launch`.
+template <class Launch>
+static int render_batches(rto_context* c, const char* who, const rto_frame* frames, int n, void* d_out, size_t frame_stride_bytes, const Launch& launch) {
+    if (!c) return RTO_E_INVALID;
+    if (!frames || n < 1 || !d_out) return fail(c, RTO_E_INVALID, std::string(who) + ": NULL argument / empty batch");
+    RTO_HIP(c, hipSetDevice(c->device));
+    for (int i = 0; i < n; i++)
+        if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
+            return fail(c, RTO_E_INVALID, std::string(who) + ": the frames of a batch share width and height");
+    for (int i0 = 0; i0 < n; i0 += kMaxBatch) {
+        const int m = std::min(kMaxBatch, n - i0);
+        float4* outs[kMaxBatch];
+        for (int i = 0; i < m; i++) outs[i] = reinterpret_cast<float4*>(static_cast<char*>(d_out) + (size_t)(i0 + i) * frame_stride_bytes);
+        const int rc = launch(i0, m, outs);
+        if (rc != RTO_OK) return rc;
+    }
     return RTO_OK;
 }
 
@@ -2344,12 +2431,7 @@ int rto_render_host(rto_context* c, const rto_frame* f, float* host_rgba) {
     RenderParams P;
     int rc = fill_params(c, f, nullptr, P);
     if (rc != RTO_OK) return rc;
-    const size_t pixels = (size_t)f->width * f->height;
-    if ((rc = ensure_frame(c, pixels)) != RTO_OK) return rc;
-    if ((rc = launch_trace<kModeColor>(c, P, c->d_frame, c->stream)) != RTO_OK) return rc;
-    RTO_HIP(c, hipMemcpyAsync(host_rgba, c->d_frame, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    return RTO_OK;
+    return render_to_host(c, f, host_rgba, nullptr, [&] { return launch_trace<kModeColor>(c, P, c->d_frame, c->stream); });
 }
 
 static int assemble_common(rto_context* c, const rto_frame* f, const rto_partition* p, const void* d_gathered, int batch, int index,
@@ -2387,26 +2469,15 @@ int rto_assemble_batch_device(rto_context* c, const rto_frame* f, const rto_part
 
 int rto_render_batch_device(rto_context* c, const rto_frame* frames, int n, const rto_partition* p, int shade_payload, void* d_out,
                             size_t frame_stride_bytes, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    if (!frames || n < 1 || !d_out) return fail(c, RTO_E_INVALID, "rto_render_batch_device: NULL argument / empty batch");
-    RTO_HIP(c, hipSetDevice(c->device));
-    for (int i = 0; i < n; i++)
-        if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
-            return fail(c, RTO_E_INVALID, "rto_render_batch_device: the frames of a batch share width and height");
-    for (int i0 = 0; i0 < n; i0 += kMaxBatch) {
-        const int m = std::min(kMaxBatch, n - i0);
+    const hipStream_t s = (hipStream_t)hip_stream;
+    return render_batches(c, "rto_render_batch_device", frames, n, d_out, frame_stride_bytes, [&](int i0, int m, float4* const* outs) {
         RenderParams P[kMaxBatch];
-        float4* outs[kMaxBatch];
         for (int i = 0; i < m; i++) {
-            const int rc = fill_params(c, &frames[i0 + i], p, P[i], (hipStream_t)hip_stream);
+            const int rc = fill_params(c, &frames[i0 + i], p, P[i], s);
             if (rc != RTO_OK) return rc;
-            outs[i] = reinterpret_cast<float4*>(static_cast<char*>(d_out) + (size_t)(i0 + i) * frame_stride_bytes);
         }
-        const int rc = shade_payload ? launch_trace_batch<kModeShade>(c, P, m, outs, (hipStream_t)hip_stream)
-                                     : launch_trace_batch<kModeColor>(c, P, m, outs, (hipStream_t)hip_stream);
-        if (rc != RTO_OK) return rc;
-    }
-    return RTO_OK;
+        return shade_payload ? launch_trace_batch<kModeShade>(c, P, m, outs, s) : launch_trace_batch<kModeColor>(c, P, m, outs, s);
+    });
 }
 
 int rto_assemble_batch_all_device(rto_context* c, const rto_frame* frames, int batch, const rto_partition* p, const void* d_gathered,
@@ -2631,12 +2702,15 @@ int rto_download_leaf_triangles(rto_context* c, float* tris, int64_t tri_capacit
     return RTO_OK;
 }
 
+// LDS of the lean triangle kernels: the stacks + the keys of the triangle rounds (one 8-byte word per lane)
+static size_t lean_triangle_lds_bytes(int depth) { return lean_stack_bytes(1, depth) + (size_t)lean_wpb(1) * kWave * sizeof(unsigned long long); }
+
 static int launch_triangles(rto_context* c, const rto_frame* f, const rto_partition* p, int shadow, float4* d_out, hipStream_t s,
                             bool count, bool shadeOut = false) {
-    if (s != c->stream) c->otherStreams = true;
     if (!c->d_triOffset) return fail(c, RTO_E_NO_OCTREE, "render_triangles: no leaf triangles uploaded");
     if (c->culling) return fail(c, RTO_E_UNSUPPORTED, "render_triangles: not available while frustum culling is active");
-    { const int rcOrder = order_after_cull(c, s); if (rcOrder != RTO_OK) return rcOrder; }      // a culling switch-off rewrites the descriptors too
+    bool capturing = false;
+    { const int rcOrder = launch_prologue(c, s, &capturing); if (rcOrder != RTO_OK) return rcOrder; }      // a culling switch-off rewrites the descriptors too
     RenderParams P;
     int rc = fill_params(c, f, p, P, s);
     if (rc != RTO_OK) return rc;
@@ -2644,56 +2718,46 @@ static int launch_triangles(rto_context* c, const rto_frame* f, const rto_partit
     if (tiles <= 0) return RTO_OK;
     const int blocks = (tiles + (kBlock / kWave) - 1) / (kBlock / kWave);
     const bool packed = c->canonical && c->numInternal > 0 && c->kernelMode != RTO_KERNEL_GENERIC;
-    const bool capturing = stream_is_capturing(s);
+    const bool leanTri = c->d_triRec && c->kernelMode != RTO_KERNEL_PACKED_V3;
     if (packed) {
         // same launch geometry and launch order as the octree frames: waves for the geometry's rectangle only, wide stores
         // for the rest, costliest tiles of earlier frames first (the instrumented frame keeps one wave per tile)
         rto_context::OrderState* st = nullptr;
         const int solidRect[4] = { P.solidX0, P.solidY0, P.solidX1, P.solidY1 };
-        const bool leanTri = c->d_triRec && c->kernelMode != RTO_KERNEL_PACKED_V3;
         if ((rc = prepare_schedule(c, s, capturing, !count, false, 1, solidRect, P, &st, leanTri ? 0 : -1, true)) != RTO_OK) return rc;
     }
-    const bool noEvents = capturing || c->eventsOff;
-    hipEvent_t evA = c->ev0, evB = c->ev1;                 // a timing-ring slot per launch that records events (rto_timing_begin)
-    if (!noEvents && c->ringUsed < c->ringStart.size()) { evA = c->ringStart[c->ringUsed]; evB = c->ringStop[c->ringUsed]; c->ringUsed++; }
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));
-    if (packed) {
-        const int lblocks = (P.launchWaves + (kBlock / kWave) - 1) / (kBlock / kWave);
-        if (c->d_triRec && c->kernelMode != RTO_KERNEL_PACKED_V3) {
-            // default: the lean loop on the unified records (8-byte stack entries, shadow rays start inside the loop)
-            LeanTriScene S{ c->d_triRec, c->d_tris };
+    RTO_HIP(c, c->timer.open(s, !(capturing || c->eventsOff)));
+    // each family's three builds (shade payload / counting / plain) share a signature: one is chosen, one launch is written
+    if (packed && leanTri) {
+        // default: the lean loop on the unified records (8-byte stack entries, shadow rays start inside the loop)
+        LeanTriScene S{ c->d_triRec, c->d_tris };
 #if defined(RTO_TRI_TIMELINE)
-            S.timeline = (!count && !shadeOut && !capturing && ensure_steps(c, (size_t)tiles * 8) == RTO_OK) ? c->d_steps : nullptr;
+        S.timeline = (!count && !shadeOut && !capturing && ensure_steps(c, (size_t)tiles * 8) == RTO_OK) ? c->d_steps : nullptr;
 #endif
 #if defined(RTO_TRI_STAMP)
-            S.stamp = (!count && !shadeOut && !capturing && ensure_steps(c, (size_t)tiles * 24) == RTO_OK) ? reinterpret_cast<unsigned*>(c->d_steps) : nullptr;
+        S.stamp = (!count && !shadeOut && !capturing && ensure_steps(c, (size_t)tiles * 24) == RTO_OK) ? reinterpret_cast<unsigned*>(c->d_steps) : nullptr;
 #endif
-            const size_t lds = (size_t)lean_wpb(1) * ((P.depth + 1) * kWave * sizeof(uint2) + kWave * sizeof(unsigned long long));   // stacks + the keys of the triangle rounds
-            P.maskLdsBytes = (int)lds;
-            const dim3 lb(lean_block(1)), lgrid((P.launchWaves + lean_wpb(1) - 1) / lean_wpb(1) + P.maskBlocks);
-            if (c->maskMode == 2 && P.maskBlocks > 0 && !count)
-                hipLaunchKernelGGL((k_trace_lean_triangles<kModeColor, false>), dim3(P.maskBlocks), lb, lds, s, P, S, shadow, d_out, c->d_counters);
-            if (shadeOut) hipLaunchKernelGGL((k_trace_lean_triangles<kModeColor, true>), lgrid, lb, lds, s, P, S, shadow, d_out, c->d_counters);
-            else if (count) hipLaunchKernelGGL((k_trace_lean_triangles<kModeSteps, false>), lgrid, lb, lds, s, P, S, shadow, d_out, c->d_counters);
-            else hipLaunchKernelGGL((k_trace_lean_triangles<kModeColor, false>), lgrid, lb, lds, s, P, S, shadow, d_out, c->d_counters);
-        } else {
-            // RTO_KERNEL_PACKED_V3: round 1's form on the descriptors + triOffset (kept in the test matrix)
-            PackedTriScene S{ c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset };
-            const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * sizeof(uint4);
-            if (shadeOut) hipLaunchKernelGGL((k_trace_packed_triangles<kModeColor, true>), dim3(lblocks), dim3(kBlock), lds, s, P, S, shadow, d_out, c->d_counters);
-            else if (count) hipLaunchKernelGGL((k_trace_packed_triangles<kModeSteps, false>), dim3(lblocks), dim3(kBlock), lds, s, P, S, shadow, d_out, c->d_counters);
-            else hipLaunchKernelGGL((k_trace_packed_triangles<kModeColor, false>), dim3(lblocks), dim3(kBlock), lds, s, P, S, shadow, d_out, c->d_counters);
-        }
+        const size_t lds = lean_triangle_lds_bytes(P.depth);
+        P.maskLdsBytes = (int)lds;
+        const dim3 lb(lean_block(1)), lgrid((P.launchWaves + lean_wpb(1) - 1) / lean_wpb(1) + P.maskBlocks);
+        if (c->maskMode == 2 && P.maskBlocks > 0 && !count)
+            hipLaunchKernelGGL((k_trace_lean_triangles<kModeColor, false>), dim3(P.maskBlocks), lb, lds, s, P, S, shadow, d_out, c->d_counters);
+        auto* kern = shadeOut ? k_trace_lean_triangles<kModeColor, true> : count ? k_trace_lean_triangles<kModeSteps, false> : k_trace_lean_triangles<kModeColor, false>;
+        hipLaunchKernelGGL(kern, lgrid, lb, lds, s, P, S, shadow, d_out, c->d_counters);
+    } else if (packed) {
+        // RTO_KERNEL_PACKED_V3: round 1's form on the descriptors + triOffset (kept in the test matrix)
+        PackedTriScene S{ c->d_desc, c->d_descFirstChild, c->d_tris, c->d_triOffset };
+        const int lblocks = (P.launchWaves + (kBlock / kWave) - 1) / (kBlock / kWave);
+        const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * sizeof(uint4);
+        auto* kern = shadeOut ? k_trace_packed_triangles<kModeColor, true> : count ? k_trace_packed_triangles<kModeSteps, false> : k_trace_packed_triangles<kModeColor, false>;
+        hipLaunchKernelGGL(kern, dim3(lblocks), dim3(kBlock), lds, s, P, S, shadow, d_out, c->d_counters);
     } else {
         TriScene S{ c->d_nodes, c->d_tris, c->d_triOffset };
-        if (shadeOut) hipLaunchKernelGGL((k_trace_triangles<kModeColor, true>), dim3(blocks), dim3(kBlock), 0, s, P, S, shadow, d_out, c->d_counters);
-        else if (count) hipLaunchKernelGGL((k_trace_triangles<kModeSteps, false>), dim3(blocks), dim3(kBlock), 0, s, P, S, shadow, d_out, c->d_counters);
-        else hipLaunchKernelGGL((k_trace_triangles<kModeColor, false>), dim3(blocks), dim3(kBlock), 0, s, P, S, shadow, d_out, c->d_counters);
+        auto* kern = shadeOut ? k_trace_triangles<kModeColor, true> : count ? k_trace_triangles<kModeSteps, false> : k_trace_triangles<kModeColor, false>;
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, s, P, S, shadow, d_out, c->d_counters);
     }
     RTO_HIP(c, hipGetLastError());
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evB, s));
-    c->lastA = evA; c->lastB = evB;
-    c->timed = !noEvents;
+    RTO_HIP(c, c->timer.close(s));
     return RTO_OK;
 }
 
@@ -2701,7 +2765,6 @@ static int launch_triangles(rto_context* c, const rto_frame* f, const rto_partit
 // lean triangle kernel is not the one in use.
 static int launch_triangles_batch(rto_context* c, const rto_frame* frames, int n, const rto_partition* p, int shadow, float4* const* outs,
                                   hipStream_t s, bool shadeOut) {
-    if (s != c->stream) c->otherStreams = true;
     const bool lean = c->d_triRec && c->canonical && c->numInternal > 0 && !c->culling &&
                       (c->kernelMode == RTO_KERNEL_AUTO || c->kernelMode == RTO_KERNEL_PACKED);
     if (!lean || n == 1) {
@@ -2712,68 +2775,22 @@ static int launch_triangles_batch(rto_context* c, const rto_frame* frames, int n
         return RTO_OK;
     }
     if (!c->d_triOffset) return fail(c, RTO_E_NO_OCTREE, "render_triangles: no leaf triangles uploaded");
-    const bool capturing = stream_is_capturing(s);
-    { const int rcOrder = order_after_cull(c, s); if (rcOrder != RTO_OK) return rcOrder; }
-    const bool noEvents = capturing || c->eventsOff;
-    RenderBatch B;
-    B.n = n;
-    int maxWaves = 0;
-    rto_context::OrderState* st = nullptr;
-    for (int i = 0; i < n; i++) {
-        int rc = fill_params(c, &frames[i], p, B.P[i], s);
-        if (rc != RTO_OK) return rc;
-        B.out[i] = outs[i];
-        if (B.P[i].tilesX * B.P[i].tilesY <= 0) { B.P[i].launchWaves = 0; continue; }
-        const int solidRect[4] = { B.P[i].solidX0, B.P[i].solidY0, B.P[i].solidX1, B.P[i].solidY1 };
-        if ((rc = prepare_schedule(c, s, capturing, true, false, 1, solidRect, B.P[i], &st, i)) != RTO_OK) return rc;
-        maxWaves = std::max(maxWaves, B.P[i].launchWaves);
-    }
-    batch_mask_all_or_none(B);
-    for (int i = 0; i < n; i++) {                                   // one box-relative order table per stream: see launch_trace_batch
-        if (!st || B.P[i].launchWaves <= 0 || !B.P[i].tileCost) continue;
-        const rto_context::OrderState::Table& T = st->tab[st->active];
-        const bool fits = T.valid && B.P[i].boxW == T.box[2] && B.P[i].boxH == T.box[3] && B.P[i].traceWaves > 0;
-        B.P[i].tileOrder = fits ? T.d : nullptr;
-    }
-    if (maxWaves <= 0) return RTO_OK;
-    hipEvent_t evA = c->ev0, evB = c->ev1;
-    if (!noEvents && c->ringUsed < c->ringStart.size()) { evA = c->ringStart[c->ringUsed]; evB = c->ringStop[c->ringUsed]; c->ringUsed++; }
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evA, s));
     LeanTriScene S{ c->d_triRec, c->d_tris };
 #if defined(RTO_TRI_TIMELINE)
     S.timeline = nullptr;
 #endif
-    const size_t lds = (size_t)lean_wpb(1) * ((B.P[0].depth + 1) * kWave * sizeof(uint2) + kWave * sizeof(unsigned long long));
-    for (int i = 0; i < n; i++) B.P[i].maskLdsBytes = (int)lds;
-    const long long waves = (long long)maxWaves * n;
-    const dim3 grid((unsigned)((waves + lean_wpb(1) - 1) / lean_wpb(1)) + (unsigned)(B.P[0].maskBlocks * n));
-    if (c->maskMode == 2 && B.P[0].maskBlocks > 0)
-        hipLaunchKernelGGL(k_trace_lean_triangles_batch<false>, dim3((unsigned)(B.P[0].maskBlocks * n)), dim3(lean_block(1)), lds, s, B, S, shadow);
-    if (shadeOut) hipLaunchKernelGGL(k_trace_lean_triangles_batch<true>, grid, dim3(lean_block(1)), lds, s, B, S, shadow);
-    else hipLaunchKernelGGL(k_trace_lean_triangles_batch<false>, grid, dim3(lean_block(1)), lds, s, B, S, shadow);
-    RTO_HIP(c, hipGetLastError());
-    if (!noEvents) RTO_HIP(c, hipEventRecord(evB, s));
-    c->lastA = evA; c->lastB = evB;
-    c->timed = !noEvents;
-    return RTO_OK;
+    return launch_batch(c, s, 1, n, outs, [&](int i, RenderParams& P) { return fill_params(c, &frames[i], p, P, s); }, lean_triangle_lds_bytes,
+                        [&](unsigned groups, size_t lds, const RenderBatch& B, bool maskOnly) {
+                            auto* kern = shadeOut && !maskOnly ? k_trace_lean_triangles_batch<true> : k_trace_lean_triangles_batch<false>;
+                            hipLaunchKernelGGL(kern, dim3(groups), dim3(lean_block(1)), lds, s, B, S, shadow);
+                        });
 }
 
 int rto_render_triangles_batch_device(rto_context* c, const rto_frame* frames, int n, const rto_partition* p, int shadow, int shade_payload,
                                       void* d_out, size_t frame_stride_bytes, void* hip_stream) {
-    if (!c) return RTO_E_INVALID;
-    if (!frames || n < 1 || !d_out) return fail(c, RTO_E_INVALID, "rto_render_triangles_batch_device: NULL argument / empty batch");
-    RTO_HIP(c, hipSetDevice(c->device));
-    for (int i = 0; i < n; i++)
-        if (frames[i].width != frames[0].width || frames[i].height != frames[0].height)
-            return fail(c, RTO_E_INVALID, "rto_render_triangles_batch_device: the frames of a batch share width and height");
-    for (int i0 = 0; i0 < n; i0 += kMaxBatch) {
-        const int m = std::min(kMaxBatch, n - i0);
-        float4* outs[kMaxBatch];
-        for (int i = 0; i < m; i++) outs[i] = reinterpret_cast<float4*>(static_cast<char*>(d_out) + (size_t)(i0 + i) * frame_stride_bytes);
-        const int rc = launch_triangles_batch(c, &frames[i0], m, p, shadow, outs, (hipStream_t)hip_stream, shade_payload != 0);
-        if (rc != RTO_OK) return rc;
-    }
-    return RTO_OK;
+    return render_batches(c, "rto_render_triangles_batch_device", frames, n, d_out, frame_stride_bytes, [&](int i0, int m, float4* const* outs) {
+        return launch_triangles_batch(c, &frames[i0], m, p, shadow, outs, (hipStream_t)hip_stream, shade_payload != 0);
+    });
 }
 
 int rto_render_triangles_device(rto_context* c, const rto_frame* f, const rto_partition* p, int shadow, void* d_out, void* hip_stream) {
@@ -2834,17 +2851,7 @@ int rto_render_triangles_host(rto_context* c, const rto_frame* f, int shadow, fl
     if (!c) return RTO_E_INVALID;
     if (!host_rgba || !f) return fail(c, RTO_E_INVALID, "rto_render_triangles_host: NULL argument");
     RTO_HIP(c, hipSetDevice(c->device));
-    const size_t pixels = (size_t)f->width * f->height;
-    int rc = ensure_frame(c, pixels);
-    if (rc != RTO_OK) return rc;
-    if (stats) RTO_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
-    if ((rc = launch_triangles(c, f, nullptr, shadow, c->d_frame, c->stream, stats != nullptr)) != RTO_OK) return rc;
-    Counters h{ 0, 0, 0 };
-    if (stats) RTO_HIP(c, hipMemcpyAsync(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipMemcpyAsync(host_rgba, c->d_frame, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    if (stats) { stats->rays = pixels; stats->pops = h.pops; stats->hits = h.hits; stats->capped = 0; }
-    return RTO_OK;
+    return render_to_host(c, f, host_rgba, stats, [&] { return launch_triangles(c, f, nullptr, shadow, c->d_frame, c->stream, stats != nullptr); });
 }
 
 int rto_octree_ray_skip(rto_context* c, const float ro[3], const float* rd, int64_t n, float t_min, float t_max,
@@ -2879,11 +2886,11 @@ int rto_octree_ray_skip(rto_context* c, const float ro[3], const float* rd, int6
 
 // ---- the reference's closest-hit traversal (its earlier, block-commented shader: S/RT:46-166) --------------------------------
 static int launch_closest(rto_context* c, const rto_frame* f, const rto_partition* p, float4* d_out, hipStream_t s, bool count) {
-    if (s != c->stream) c->otherStreams = true;
     RenderParams P;
     int rc = fill_params(c, f, p, P, s);
     if (rc != RTO_OK) return rc;
-    if ((rc = order_after_cull(c, s)) != RTO_OK) return rc;
+    bool capturing = false;
+    if ((rc = launch_prologue(c, s, &capturing)) != RTO_OK) return rc;
     const int tiles = P.tilesX * P.tilesY;
     if (tiles <= 0) return RTO_OK;
     // canonical trees without a frustum update in force: the descriptor form (k_closest_lean); RTO_KERNEL_GENERIC keeps the node-by-node form
@@ -2896,7 +2903,7 @@ static int launch_closest(rto_context* c, const rto_frame* f, const rto_partitio
             // launch geometry, launch order and occupancy mask of the first-hit frames (path 3: tables of its own kind on the stream)
             rto_context::OrderState* st = nullptr;
             const int solidRect[4] = { P.solidX0, P.solidY0, P.solidX1, P.solidY1 };
-            if ((rc = prepare_schedule(c, s, stream_is_capturing(s), true, false, 3, solidRect, P, &st, 0, true)) != RTO_OK) return rc;
+            if ((rc = prepare_schedule(c, s, capturing, true, false, 3, solidRect, P, &st, 0, true)) != RTO_OK) return rc;
             P.maskLdsBytes = (int)lds;
             const int blocksN = (P.launchWaves + (kBlock / kWave) - 1) / (kBlock / kWave) + P.maskBlocks;
             if (c->maskMode == 2 && P.maskBlocks > 0) hipLaunchKernelGGL(k_closest_near_first, dim3(P.maskBlocks), dim3(kBlock), lds, s, P, c->d_desc, d_out);
@@ -2928,17 +2935,7 @@ int rto_render_closest_host(rto_context* c, const rto_frame* f, float* host_rgba
     if (!f || !host_rgba) return fail(c, RTO_E_INVALID, "rto_render_closest_host: NULL argument");
     RTO_HIP(c, hipSetDevice(c->device));
     if (f->width <= 0 || f->height <= 0) return fail(c, RTO_E_INVALID, "render: width/height must be positive");
-    const size_t pixels = (size_t)f->width * f->height;
-    int rc = ensure_frame(c, pixels);
-    if (rc != RTO_OK) return rc;
-    if (stats) RTO_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
-    if ((rc = launch_closest(c, f, nullptr, c->d_frame, c->stream, stats != nullptr)) != RTO_OK) return rc;
-    Counters h{ 0, 0, 0 };
-    if (stats) RTO_HIP(c, hipMemcpyAsync(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipMemcpyAsync(host_rgba, c->d_frame, pixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RTO_HIP(c, hipStreamSynchronize(c->stream));
-    if (stats) { stats->rays = pixels; stats->pops = h.pops; stats->hits = h.hits; stats->capped = 0; }
-    return RTO_OK;
+    return render_to_host(c, f, host_rgba, stats, [&] { return launch_closest(c, f, nullptr, c->d_frame, c->stream, stats != nullptr); });
 }
 
 // ---- N1 as a render mode + N1's consumer ------------------------------------------------------------------------------
@@ -2946,11 +2943,11 @@ static int launch_skip_render(rto_context* c, const rto_frame* f, const rto_part
     if (!d_rgba && !d_dist) return fail(c, RTO_E_INVALID, "rto_render_skip: neither output given");
     if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_render_skip: no octree uploaded");
     if (!(c->canonical && c->numInternal > 0)) return fail(c, RTO_E_UNSUPPORTED, "rto_render_skip: needs a canonical BFS octree (what setOctree / rto_build_octree produce)");
-    if (s != c->stream) c->otherStreams = true;
     RenderParams P;
     int rc = fill_params(c, f, p, P, s);
     if (rc != RTO_OK) return rc;
-    if ((rc = order_after_cull(c, s)) != RTO_OK) return rc;
+    bool capturing = false;
+    if ((rc = launch_prologue(c, s, &capturing)) != RTO_OK) return rc;
     const int tiles = P.tilesX * P.tilesY;
     if (tiles <= 0) return RTO_OK;
     const size_t lds = (size_t)(kBlock / kWave) * P.depth * kWave * sizeof(uint4);
@@ -2959,7 +2956,7 @@ static int launch_skip_render(rto_context* c, const rto_frame* f, const rto_part
     // launch geometry, launch order and occupancy mask of the first-hit frames (path 2: tables of its own kind on the stream)
     rto_context::OrderState* st = nullptr;
     const int solidRect[4] = { P.solidX0, P.solidY0, P.solidX1, P.solidY1 };
-    if ((rc = prepare_schedule(c, s, stream_is_capturing(s), true, false, 2, solidRect, P, &st, 0, true)) != RTO_OK) return rc;
+    if ((rc = prepare_schedule(c, s, capturing, true, false, 2, solidRect, P, &st, 0, true)) != RTO_OK) return rc;
     P.maskLdsBytes = (int)lds;
     const int blocks = (P.launchWaves + (kBlock / kWave) - 1) / (kBlock / kWave) + P.maskBlocks;
     if (c->maskMode == 2 && P.maskBlocks > 0)
@@ -2995,8 +2992,7 @@ static int launch_probe_skip(rto_context* c, const float view[16], const float c
     if (!view || !cam_pos || !d_skip) return fail(c, RTO_E_INVALID, "rto_probe_skip: NULL argument");
     if (c->numNodes <= 0) return fail(c, RTO_E_NO_OCTREE, "rto_probe_skip: no octree uploaded");
     if (!(c->canonical && c->numInternal > 0)) return fail(c, RTO_E_UNSUPPORTED, "rto_probe_skip: needs a canonical BFS octree");
-    if (s != c->stream) c->otherStreams = true;
-    { const int rcOrder = order_after_cull(c, s); if (rcOrder != RTO_OK) return rcOrder; }
+    { const int rcOrder = launch_prologue(c, s); if (rcOrder != RTO_OK) return rcOrder; }      // no capture test: nothing here depends on it
     ProbeParams Q;
     // S/VR:1608-1612: P = perspective(radians(45), aspect, 0.1, 5000); invV = inverse(V); invP = inverse(P) -- pixel independent, on the host
     const rtmath::mat4 P = rtmath::perspective(rtmath::radians(45.0f), aspect, 0.1f, 5000.0f);
@@ -3038,9 +3034,9 @@ int rto_probe_skip_host(rto_context* c, const float view[16], const float cam_po
 
 int rto_last_kernel_ms(rto_context* c, float* ms) {
     if (!c || !ms) return RTO_E_INVALID;
-    if (!c->timed) return fail(c, RTO_E_INVALID, "rto_last_kernel_ms: no kernel launched yet");
+    if (!c->timer.timed) return fail(c, RTO_E_INVALID, "rto_last_kernel_ms: no kernel launched yet");
     RTO_HIP(c, hipSetDevice(c->device));
-    hipEvent_t a = c->lastA ? c->lastA : c->ev0, b = c->lastB ? c->lastB : c->ev1;
+    const hipEvent_t a = c->timer.lastA, b = c->timer.lastB;
     RTO_HIP(c, hipEventSynchronize(b));
     RTO_HIP(c, hipEventElapsedTime(ms, a, b));
     return RTO_OK;
@@ -3052,14 +3048,7 @@ int rto_timing_begin(rto_context* c, int capacity) {
     if (capacity < 0) capacity = 0;
     RTO_HIP(c, hipSetDevice(c->device));
     RTO_HIP(c, hipDeviceSynchronize());
-    for (hipEvent_t e : c->ringStart) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ringStop) (void)hipEventDestroy(e);
-    c->ringStart.clear(); c->ringStop.clear(); c->ringUsed = 0; c->lastA = c->lastB = nullptr;
-    for (int i = 0; i < capacity; i++) {
-        hipEvent_t a, b;
-        RTO_HIP(c, hipEventCreate(&a)); c->ringStart.push_back(a);
-        RTO_HIP(c, hipEventCreate(&b)); c->ringStop.push_back(b);
-    }
+    RTO_HIP(c, c->timer.reset_ring(capacity));
     return RTO_OK;
 }
 
@@ -3067,10 +3056,11 @@ int rto_timing_read(rto_context* c, float* ms, int capacity, int* count) {
     if (!c || !count) return RTO_E_INVALID;
     RTO_HIP(c, hipSetDevice(c->device));
     RTO_HIP(c, hipDeviceSynchronize());
-    *count = (int)c->ringUsed;
+    const KernelTimer& t = c->timer;
+    *count = (int)t.ringUsed;
     if (!ms) return RTO_OK;
-    if (capacity < (int)c->ringUsed) return fail(c, RTO_E_INVALID, "rto_timing_read: capacity too small");
-    for (size_t i = 0; i < c->ringUsed; i++) RTO_HIP(c, hipEventElapsedTime(&ms[i], c->ringStart[i], c->ringStop[i]));
+    if (capacity < (int)t.ringUsed) return fail(c, RTO_E_INVALID, "rto_timing_read: capacity too small");
+    for (size_t i = 0; i < t.ringUsed; i++) RTO_HIP(c, hipEventElapsedTime(&ms[i], t.ring[2 * i], t.ring[2 * i + 1]));
     return RTO_OK;
 }
 

@@ -460,9 +460,9 @@ int rto_comm_render_resident_all(rto_comm* const* comms, int n_comms, const rto_
     if ((rc = rto_comm_submit_all(comms, n_comms, frame, 1, mode, c0->d_frame, pixels * sizeof(float4))) != RTO_OK) return rc;
     // order the context's own stream (what rto_download_resident waits on) behind the assembly
     RTO_CHIP(comms[0], hipSetDevice(c0->device));
-    RTO_CHIP(comms[0], hipEventRecord(c0->ev1, comms[0]->commStream));
-    RTO_CHIP(comms[0], hipStreamWaitEvent(c0->stream, c0->ev1, 0));
-    c0->timed = false;
+    const hipEvent_t ev1 = c0->timer.borrow_stop();
+    RTO_CHIP(comms[0], hipEventRecord(ev1, comms[0]->commStream));
+    RTO_CHIP(comms[0], hipStreamWaitEvent(c0->stream, ev1, 0));
     c0->residentW = frame->width; c0->residentH = frame->height;
     return RTO_OK;
 }
