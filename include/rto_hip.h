@@ -1678,6 +1678,81 @@ int  rto_download_isosurface(rto_context* ctx, float* tris, int64_t capacity, in
  * kernel ran).  The read-back of the count and the growth of the output buffer lie between the last two and are in none of them. */
 int  rto_last_isosurface_ms(const rto_context* ctx, float ms[3]);
 
+/* ---- dose fields: point sources seen through the grid, per voxel ----------------
+ * Which air voxels see these lamps, cameras, antennas or radiation points, how much of each reaches a voxel through how many walls,
+ * how much of the street space does the set cover: for every evaluated EMPTY voxel the sum over the sources of the source's weight,
+ * attenuated by the number of SOLID voxels the straight segment to the source crosses and, if asked for, by the squared distance.
+ * The purpose of the reference's radiation splat, which DESIGN.md section 9 leaves out because the splat ignores the buildings.
+ * Exact in integers; every result is an integer that a plain loop over rto_download_voxels reproduces bit for bit.
+ *
+ * Rule.  Index, layout, SOLID and EMPTY are rto_exposure_field's; the crossing rule is its rule cut to a
+ * segment.
+ *   source    s = (i, j, k, w), four int32: a voxel of the resident grid and a weight w >= 0.  n sources, 1 <= n <=
+ *             RTO_DOSE_MAX_SOURCES; the sum W of the weights must be <= 2^31 - 1.  A source may sit in a SOLID voxel (a lamp on a
+ *             wall); a source given twice counts twice.  Both ends of every segment lie in the grid, which is convex: nothing
+ *             outside the grid is ever visited.
+ *   segment   for an evaluated voxel p and a source s, d = s - p: centre(p) + t d, 0 < t < 1.  A voxel q outside {p, s} is crossed
+ *             when some t in (0, 1) puts the point strictly inside q's open cube; on an axis where d is zero q has p's coordinate.
+ *             A segment through an edge or a corner crosses neither cube it only touches.  Equivalently: q is crossed by
+ *             rto_exposure_field's ray (p, d) and by the ray (s, -d); or: q is an entry of periods 0 .. g - 1 of the template of
+ *             d / g, g the gcd of d's components, without the last entry, which is s.
+ *   reach     1 <= r <= RTO_DOSE_MAX_REACH, in voxels; RTO_DOSE_NO_LIMIT, and every value above RTO_DOSE_MAX_REACH, means
+ *             RTO_DOSE_MAX_REACH; below 1 is RTO_E_INVALID.  A pair whose max-norm |d| exceeds r is out of reach: it contributes
+ *             nothing and is not seen.  (1,023 keeps the crossing times on one common denominator in 32 bits; grids with a longer
+ *             side are accepted, their far pairs are out of reach.)
+ *   walls     k(p, s): the number of crossed voxels that are SOLID.
+ *   transmit  a table T[0 .. m - 1] of uint32 in Q16 (65,536 is 1.0), every entry <= 65,536, 1 <= m <= RTO_DOSE_MAX_TABLE; a
+ *             pair with k >= m transmits 0.  NULL stands for {65536}: plain line of sight.  T need not be monotone.
+ *   falloff   RTO_DOSE_FALLOFF_NONE: D = 1.  RTO_DOSE_FALLOFF_INVERSE_SQUARE: D = max(1, |d|^2), the squared Euclidean length in
+ *             voxels.
+ *   c(p, s)   floor(((uint64) w T[k] >> 16) / D) for a pair in reach, else 0.  Every c is at most w: no sum leaves int32.
+ *   evaluated RTO_DOSE_ALL: every EMPTY voxel.  RTO_DOSE_SKIN: the EMPTY voxels with a SOLID face neighbour (rto_exposure_field's
+ *             two sets, with the same values).
+ *   field     e[v] as int32: for an evaluated voxel the sum of c(p, s) over the sources; -1 for every other voxel.
+ *   coverage  covered[s], one int64 per source: the evaluated voxels in reach of s with k = 0 (p = s counts when p is evaluated).
+ *   summary   evaluated; total, the sum of e; dark, the voxels with e == 0; seen, the evaluated voxels with at least one source in
+ *             reach and k = 0; peak, the maximum of e; peak_voxel, the smallest linear index that attains it.  With nothing
+ *             evaluated: 0, 0, 0, 0, -1, -1.
+ * rto_dose_field keeps the volume (int32 per voxel) and the coverage table resident beside the other fields, with its n, W, m,
+ * falloff, mode and reach; every call that changes or replaces the grid frees both, and the readers then return RTO_E_INVALID.
+ * Synchronous on the context's stream.
+ * There is NO RTO_FIELD_* source code for the dose field: the views, projections, composites and isosurfaces show it as
+ * rto_dose_device's pointer with RTO_FIELD_CALLER, like any int32 device volume of the caller's.
+ * Errors, in this order, each leaving the context and every resident product untouched: RTO_E_INVALID (NULL sources; n below 1 or
+ * above RTO_DOSE_MAX_SOURCES; a negative weight or W above 2^31 - 1; m below 1 or above RTO_DOSE_MAX_TABLE; a table entry above
+ * 65,536; unknown falloff or mode; reach below 1); RTO_E_NO_OCTREE (no octree built); RTO_E_UNSUPPORTED (the octree came from
+ * rto_upload_octree: no resident grid; more than 2^31 - 2 voxels); RTO_E_INVALID (a source outside the grid: the message names the
+ * first such source's index).  The readers: RTO_E_INVALID without a resident dose field or with too small a capacity. */
+#define RTO_DOSE_ALL                    0
+#define RTO_DOSE_SKIN                   1
+#define RTO_DOSE_FALLOFF_NONE           0
+#define RTO_DOSE_FALLOFF_INVERSE_SQUARE 1
+#define RTO_DOSE_MAX_SOURCES            1024
+#define RTO_DOSE_MAX_REACH              1023
+#define RTO_DOSE_MAX_TABLE              64
+#define RTO_DOSE_NO_LIMIT               0x7fffffff
+typedef struct rto_dose_summary {   /* 48 bytes */
+    int64_t evaluated;              /* voxels with e >= 0 */
+    int64_t total;                  /* the sum of e over them */
+    int64_t dark;                   /* evaluated voxels with e == 0 */
+    int64_t seen;                   /* evaluated voxels with a source in reach and no SOLID voxel crossed on the way */
+    int64_t peak;                   /* the maximum of e; -1: nothing evaluated */
+    int64_t peak_voxel;             /* the smallest linear index with e == peak; -1: nothing evaluated */
+} rto_dose_summary;
+
+int  rto_dose_field(rto_context* ctx, const int32_t* sources /* n x 4: i, j, k, w */, int n,
+                    const uint32_t* transmit /* m, NULL: {65536} */, int m,
+                    int falloff, int mode, int reach, rto_dose_summary* summary /* may be NULL */);
+/* dimZ x dimY x dimX int32, x fastest. */
+int  rto_download_dose(rto_context* ctx, int32_t* out, int64_t capacity);
+/* The resident field (a device pointer the context owns, valid until the field is freed): the volume to hand to
+ * rto_render_field_* / rto_project_field_* / rto_composite_field_* / rto_extract_isosurface_* with RTO_FIELD_CALLER. */
+int  rto_dose_device(rto_context* ctx, int32_t** d_e);
+/* covered[0 .. n - 1] of the resident field's n sources (capacity: int64 entries, at least n). */
+int  rto_download_dose_coverage(rto_context* ctx, int64_t* out /* n */, int64_t capacity);
+/* Device time in ms of the last rto_dose_field: prepare (bit rows, selection, uploads), march, summary (-1: not run). */
+int  rto_last_dose_ms(const rto_context* ctx, float ms[3]);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

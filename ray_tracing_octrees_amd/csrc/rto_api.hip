@@ -22,8 +22,8 @@ using namespace rto;
 namespace rto { struct CcComp; }   // rto_components.inc
 
 // The resident voxel fields of a context (rto_context::d_field) and the noun each goes by in error texts.
-enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldParts, kFieldCount };
-static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure", "part label" };
+enum FieldSlot { kFieldDistance, kFieldGeodesic, kFieldThickness, kFieldSkeleton, kFieldExposure, kFieldParts, kFieldDose, kFieldCount };
+static const char* const kFieldNoun[kFieldCount] = { "distance", "geodesic", "thickness", "skeleton", "exposure", "part label", "dose" };
 
 // The stage timer of a frame family: the events around the N stages of its last frame, and whether that frame recorded them (not
 // under stream capture, not after rto_timing_begin(ctx, -1)).
@@ -288,9 +288,9 @@ struct rto_context {
     rto_measure* d_ccMeasures = nullptr;      // nullptr: no measures resident; count records, then the total
     float measureMs[2] = { -1.f, -1.f };      // the last rto_measure_components: the measuring kernels, the total
 
-    // resident voxel fields: the last distance, geodesic, thickness, skeleton and exposure field and the last part labels of the
-    // resident grid, one int32 per voxel each (nullptr: none resident).  A maker owns its new field as a FieldDraft until the call
-    // has succeeded; all six are dropped whenever the grid changes (free_fields).  What a field was made for, and the times of its
+    // resident voxel fields: the last distance, geodesic, thickness, skeleton, exposure and dose field and the last part labels of
+    // the resident grid, one int32 per voxel each (nullptr: none resident).  A maker owns its new field as a FieldDraft until the call
+    // has succeeded; all seven are dropped whenever the grid changes (free_fields).  What a field was made for, and the times of its
     // maker, are kept per family below.
     int* d_field[kFieldCount] = {};
 
@@ -327,6 +327,13 @@ struct rto_context {
     int expoN = 0, expoMode = 0, expoReach = 0;
     int64_t expoW = 0;
     float expoMs[3] = { -1.f, -1.f, -1.f };   // the last rto_exposure_field: prepare, march, summary
+
+    // dose fields (rto_dose.inc): the coverage table of the resident field (one int64 per source; freed with the field) and the
+    // sources, weight sum, table length, falloff, mode and reach the field was made for
+    long long* d_doseCov = nullptr;
+    int doseN = 0, doseM = 0, doseFalloff = 0, doseMode = 0, doseReach = 0;
+    int64_t doseW = 0;
+    float doseMs[3] = { -1.f, -1.f, -1.f };   // the last rto_dose_field: prepare, march, summary
 
     // part segmentation (rto_parts.inc): the label volume is d_field[kFieldParts]; the part and neck tables of that volume, its
     // summary and what the last rto_segment_parts did (basin edges downloaded, edge-table slots, flatten rounds)
@@ -397,6 +404,8 @@ static void free_components(rto_context* c) {
 // The resident voxel fields: each describes one state of the grid.
 static void free_fields(rto_context* c) {
     for (int*& d : c->d_field) { (void)hipFree(d); d = nullptr; }
+    (void)hipFree(c->d_doseCov); c->d_doseCov = nullptr;       // the dose field's coverage table goes with its field
+    c->doseN = 0;
 }
 
 // The part and neck tables of the resident part labels (rto_parts.inc); the label volume itself is a field (free_fields).
@@ -1094,7 +1103,7 @@ static int download_resident(rto_context* c, const char* who, void* out, int64_t
     return RTO_OK;
 }
 
-// ---------------------------------------------------------------- resident voxel fields: what their six families share
+// ---------------------------------------------------------------- resident voxel fields: what their seven families share
 // A field that is the call's own until the call has succeeded.  begin(): the device is set, the context's stream drained and one
 // int32 per voxel of the resident grid allocated, in that order.  publish(): the slot's old field is freed and the new one takes its
 // place.  A call that returns before publish() leaves the slot as it was and the draft goes with the scope.
@@ -1226,8 +1235,8 @@ struct VoxelList {
 // voxelSize) leaves, followed by rto_build_leaf_triangles(NULL) when `triangles` -- the callers pass "were triangles resident?",
 // sampled before the call, or what their parameters ask for.  Every grid edit and the voxelizer's commit end here.
 //   dropped:  the octree's arrays and all that describes the grid or the tree as it was (free_octree_arrays): component labels,
-//             table and measures, the six resident voxel fields (distance, geodesic, thickness, skeleton, exposure, part
-//             labels) with the part and neck tables, leaf triangles and their records, cull buffers and the culling switch,
+//             table and measures, the seven resident voxel fields (distance, geodesic, thickness, skeleton, exposure, part
+//             labels, dose) with the part and neck tables and the dose coverage table, leaf triangles and their records, cull buffers and the culling switch,
 //             occupancy cells, mesh levels; every stream's tile orders and cost history are invalidated.
 //   survives: d_vox, voxDim, gridMin, voxelSize, buildPath (and everything that is not per octree: kernel mode, frame buffers,
 //             the last extracted mesh, the thickness gather's offset table).
@@ -3098,4 +3107,5 @@ int rto_synchronize(rto_context* c) {
 #include "rto_measure.inc"
 #include "rto_skeleton.inc"
 #include "rto_exposure.inc"
+#include "rto_dose.inc"
 #include "rto_parts.inc"

@@ -55,6 +55,7 @@ SYMBOLS = (
     "rto_skeleton_field", "rto_download_skeleton", "rto_skeleton_device", "rto_edit_skeleton", "rto_last_skeleton_ms",
     "rto_last_skeleton_edit_ms", "rto_debug_skeleton_passes", "rto_debug_set_skeleton_look",
     "rto_exposure_field", "rto_download_exposure", "rto_exposure_device", "rto_last_exposure_ms",
+    "rto_dose_field", "rto_download_dose", "rto_dose_device", "rto_download_dose_coverage", "rto_last_dose_ms",
     "rto_thickness_field", "rto_download_thickness", "rto_thickness_device", "rto_thickness_histogram", "rto_last_thickness_ms",
     "rto_debug_thickness_table",
     "rto_measure_components", "rto_download_measures", "rto_measures_device", "rto_last_measure_ms",
@@ -116,6 +117,14 @@ EXPO_ALL, EXPO_SKIN = 0, 1
 EXPO_MAX_COMP = 255      # RTO_EXPO_MAX_COMP: the largest |component| of a direction
 EXPO_MAX_DIRS = 1024     # RTO_EXPO_MAX_DIRS
 EXPO_NO_LIMIT = 0x7fffffff
+# struct rto_dose_summary, 48 bytes: dose fields (rto_dose_field)
+DOSE_SUMMARY_DTYPE = np.dtype([("evaluated", "<i8"), ("total", "<i8"), ("dark", "<i8"), ("seen", "<i8"), ("peak", "<i8"), ("peak_voxel", "<i8")])
+DOSE_ALL, DOSE_SKIN = 0, 1
+DOSE_FALLOFF_NONE, DOSE_FALLOFF_INVERSE_SQUARE = 0, 1
+DOSE_MAX_SOURCES = 1024  # RTO_DOSE_MAX_SOURCES
+DOSE_MAX_REACH = 1023    # RTO_DOSE_MAX_REACH: what DOSE_NO_LIMIT, and every reach above it, stands for
+DOSE_MAX_TABLE = 64      # RTO_DOSE_MAX_TABLE: the longest transmission table
+DOSE_NO_LIMIT = 0x7fffffff
 # struct rto_thick_summary, 32 bytes: local thickness fields (rto_thickness_field)
 THICK_SUMMARY_DTYPE = np.dtype([("min_t2", "<i8"), ("argmin", "<i8"), ("thin", "<i8"), ("medium", "<i8")])
 THICK_MAX_C = 64         # RTO_THICK_MAX_C: balls of up to 8 voxels
@@ -670,6 +679,11 @@ def load():
     L.rto_download_exposure.argtypes = [vp, vp, C.c_int64]
     L.rto_exposure_device.argtypes = [vp, C.POINTER(vp)]
     L.rto_last_exposure_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_dose_field.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.rto_download_dose.argtypes = [vp, vp, C.c_int64]
+    L.rto_dose_device.argtypes = [vp, C.POINTER(vp)]
+    L.rto_download_dose_coverage.argtypes = [vp, vp, C.c_int64]
+    L.rto_last_dose_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.rto_thickness_field.argtypes = [vp, C.c_int, C.c_float, vp]
     L.rto_download_thickness.argtypes = [vp, vp, C.c_int64]
     L.rto_thickness_device.argtypes = [vp, C.POINTER(vp)]
@@ -1692,6 +1706,49 @@ class Context:
     def last_exposure_ms(self):
         """Device ms of the last exposure_field: (prepare, march, summary); -1: not run."""
         return self._last_ms("rto_last_exposure_ms", 3)
+
+    # -- dose fields: point sources seen through the grid ---------------------------------
+    def dose_field(self, sources, transmit=None, falloff: int = DOSE_FALLOFF_NONE, mode: int = DOSE_ALL, reach=None):
+        """rto_dose_field: (the int32 (dimZ, dimY, dimX) volume e: for every evaluated EMPTY voxel (DOSE_ALL: all of them; DOSE_SKIN:
+        those with a SOLID face neighbour) the sum over the sources within `reach` voxels of floor((w T[k] >> 16) / D), k the SOLID
+        voxels the segment to the source crosses and D the squared distance under DOSE_FALLOFF_INVERSE_SQUARE, -1 for every other
+        voxel; the summary as a DOSE_SUMMARY_DTYPE scalar).  `sources` is (n, 4) integers: the voxel i, j, k of the grid and the
+        weight; `transmit` the Q16 table T (65536 is 1.0) or None for plain line of sight; reach None: DOSE_MAX_REACH.  The field
+        and its coverage table (dose_coverage) stay resident until the grid changes.  There is no FIELD_* code for it: the views,
+        projections, composites and isosurfaces take dose_device() with FIELD_CALLER."""
+        s = np.ascontiguousarray(np.asarray(sources, np.int64).reshape(-1, 4))
+        if s.size and (np.abs(s) > 0x7fffffff).any():
+            raise ValueError("a source's coordinate or weight does not fit int32")
+        s = np.ascontiguousarray(s, np.int32)
+        t = None
+        if transmit is not None:
+            t = np.asarray(transmit, np.int64).reshape(-1)
+            if t.size and ((t < 0) | (t > 0xffffffff)).any():
+                raise ValueError("a table entry does not fit uint32")
+            t = np.ascontiguousarray(t, np.uint32)
+        summary = np.zeros((), DOSE_SUMMARY_DTYPE)
+        self._check(self._L.rto_dose_field(self._h, s.ctypes.data if s.size else None, len(s), None if t is None else t.ctypes.data,
+                                           0 if t is None else t.size, int(falloff), int(mode), DOSE_NO_LIMIT if reach is None else int(reach),
+                                           summary.ctypes.data))
+        return self.dose(), summary
+
+    def dose(self) -> np.ndarray:
+        """The resident dose field (rto_download_dose)."""
+        return self._resident_field("rto_dose_device", "rto_download_dose")
+
+    def dose_device(self) -> int:
+        """The device pointer of the resident int32 dose field: the volume for FIELD_CALLER."""
+        return self._device_pointer("rto_dose_device")
+
+    def dose_coverage(self) -> np.ndarray:
+        """covered[s] of the resident dose field's sources (rto_download_dose_coverage): int64, one per source."""
+        out = np.full(DOSE_MAX_SOURCES, -1, np.int64)                   # a count is never negative: the entries written are the table
+        self._check(self._L.rto_download_dose_coverage(self._h, out.ctypes.data, out.size))
+        return out[:int((out >= 0).sum())].copy()
+
+    def last_dose_ms(self):
+        """Device ms of the last dose_field: (prepare, march, summary); -1: not run."""
+        return self._last_ms("rto_last_dose_ms", 3)
 
     # -- local thickness fields ----------------------------------------------------------
     def thickness_field(self, medium: int = SET_SOLID, max_radius: float | None = None):

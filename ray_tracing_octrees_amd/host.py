@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _build
-from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, FIELD_VIEW_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
+from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, DOSE_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, FIELD_VIEW_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
                   THICK_MAX_C, THICK_SUMMARY_DTYPE, IsoParams, IsoSummary, RtoError, _f)
 
 _lib = None
@@ -214,6 +214,16 @@ def load():
     L.rtoh_rt_exposure_field.restype = C.c_int
     L.rtoh_rt_exposure.argtypes = [_vp, _vp, C.c_int64]
     L.rtoh_rt_exposure.restype = C.c_int
+    L.rtoh_dose_cpu.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.rtoh_dose_cpu.restype = C.c_int
+    L.rtoh_rt_dose_field.argtypes = [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]
+    L.rtoh_rt_dose_field.restype = C.c_int
+    L.rtoh_rt_dose.argtypes = [_vp, _vp, C.c_int64]
+    L.rtoh_rt_dose.restype = C.c_int
+    L.rtoh_rt_dose_coverage.argtypes = [_vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rtoh_rt_dose_coverage.restype = C.c_int
+    L.rtoh_rt_hottest_voxel.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.rtoh_rt_hottest_voxel.restype = C.c_int
     L.rtoh_rt_geodesic_field.argtypes = [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp]
     L.rtoh_rt_geodesic_field.restype = C.c_int
     L.rtoh_parts_cpu.argtypes = [_vp, C.c_int, C.c_int, C.c_int]
@@ -487,6 +497,32 @@ class VoxelGrid:
                                           0 if d is None else len(d), int(mode), int(reach), e.ctypes.data, summary.ctypes.data, C.byref(steps)))
         out = (rc, (e if rc == 0 else None), summary)
         return out + (steps.value,) if withSteps else out
+
+    def doseField(self, sources, transmit=None, falloff: int = 0, mode: int = 0, reach: int = 0x7fffffff, withSteps: bool = False):
+        """Addition: doseFieldCPU (host/Dose.h) -- the rule of rto_dose_field on the CPU: (code, e int32 (dimZ, dimY, dimX) or None when
+        refused, covered int64 (n) or None, summary as a hip.DOSE_SUMMARY_DTYPE scalar), and with withSteps the crossed voxels tested
+        as a fifth value.  `sources` is (n, 4) integers i, j, k, w (None stands for the NULL pointer), `transmit` the Q16 table or
+        None for plain line of sight.  After a refusal for a source outside the grid, badSource is its index (else -1)."""
+        dx, dy, dz = self.dims
+        s, t = _dose_args(sources, transmit)
+        e = np.empty((dz, dy, dx), np.int32)
+        covered = np.zeros(0 if s is None else len(s), np.int64)
+        summary = np.zeros((), DOSE_SUMMARY_DTYPE)
+        steps, bad = C.c_int64(), C.c_int(-1)
+        rc = int(load().rtoh_dose_cpu(self._h, None if s is None else s.ctypes.data, 0 if s is None else len(s), None if t is None else t.ctypes.data,
+                                      0 if t is None else len(t), int(falloff), int(mode), int(reach), e.ctypes.data,
+                                      covered.ctypes.data if covered.size else None, summary.ctypes.data, C.byref(steps), C.byref(bad)))
+        self.badSource = bad.value
+        out = (rc, (e if rc == 0 else None), (covered if rc == 0 else None), summary)
+        return out + (steps.value,) if withSteps else out
+
+
+def _dose_args(sources, transmit):
+    """(sources as contiguous (n, 4) int32 or None, the table as contiguous uint32 or None) for the dose entry points.  An (n, 4)
+    array of n = 0 sources stays an array: the entry point refuses it, not the wrapper."""
+    s = None if sources is None else np.ascontiguousarray(np.asarray(sources, np.int32).reshape(-1, 4))
+    t = None if transmit is None else np.ascontiguousarray(np.asarray(transmit, np.uint32).reshape(-1))
+    return s, t
 
 
 def _expo_args(dirs, weights):
@@ -1180,6 +1216,37 @@ class RayTracerBVH:
         e = np.empty((dims[2], dims[1], dims[0]), np.int32)
         rc = int(load().rtoh_rt_exposure(self._h, e.ctypes.data, e.size))
         return rc, (e if rc == 0 else None)
+
+    def doseField(self, sources, transmit=None, falloff: int = 0, mode: int = 0, reach: int = 0x7fffffff):
+        """Addition: RayTracerBVH::doseField -- (code, summary as a hip.DOSE_SUMMARY_DTYPE scalar); code is RTO_OK or the refusal's
+        (lastError).  The field stays resident: dose() downloads it, doseCoverage() its per-source counts."""
+        s, t = _dose_args(sources, transmit)
+        summary = np.zeros((), DOSE_SUMMARY_DTYPE)
+        rc = int(load().rtoh_rt_dose_field(self._h, None if s is None else s.ctypes.data, 0 if s is None else len(s), None if t is None else t.ctypes.data,
+                                           0 if t is None else len(t), int(falloff), int(mode), int(reach), summary.ctypes.data))
+        return rc, summary
+
+    def dose(self):
+        """Addition: RayTracerBVH::dose -- (code, e int32 (dimZ, dimY, dimX) or None when there is no resident field)."""
+        dims = (C.c_int * 3)()
+        load().rtoh_rt_grid(self._h, dims, None)
+        e = np.empty((dims[2], dims[1], dims[0]), np.int32)
+        rc = int(load().rtoh_rt_dose(self._h, e.ctypes.data, e.size))
+        return rc, (e if rc == 0 else None)
+
+    def doseCoverage(self):
+        """Addition: RayTracerBVH::doseCoverage -- (code, covered int64 (n) or None when there is no resident field)."""
+        out = np.zeros(1024, np.int64)
+        count = C.c_int64()
+        rc = int(load().rtoh_rt_dose_coverage(self._h, out.ctypes.data, out.size, C.byref(count)))
+        return rc, (out[:count.value].copy() if rc == 0 else None)
+
+    def hottestVoxel(self):
+        """Addition: RayTracerBVH::hottestVoxel -- (code, (i, j, k) of the resident dose field's peak, the smallest index among
+        equals, and its value; None, None when refused)."""
+        ijk, value = (C.c_int32 * 3)(), C.c_int32()
+        rc = int(load().rtoh_rt_hottest_voxel(self._h, ijk, C.byref(value)))
+        return (rc, tuple(ijk), value.value) if rc == 0 else (rc, None, None)
 
     def thin(self, mode: int = 1, maxPasses: int = 0x7fffffff) -> int:
         """Addition: RayTracerBVH::thin -- replaces the solid by its skeleton; voxels removed, or the refusal's code (negative)."""

@@ -5,6 +5,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +74,9 @@ struct HipApi {
     decltype(&rto_edit_skeleton) edit_skeleton = nullptr;
     decltype(&rto_exposure_field) exposure_field = nullptr;
     decltype(&rto_download_exposure) download_exposure = nullptr;
+    decltype(&rto_dose_field) dose_field = nullptr;
+    decltype(&rto_download_dose) download_dose = nullptr;
+    decltype(&rto_download_dose_coverage) download_dose_coverage = nullptr;
     decltype(&rto_thickness_field) thickness_field = nullptr;
     decltype(&rto_download_thickness) download_thickness = nullptr;
     decltype(&rto_thickness_histogram) thickness_histogram = nullptr;
@@ -169,6 +173,9 @@ struct HipApi {
         edit_skeleton = reinterpret_cast<decltype(edit_skeleton)>(sym("rto_edit_skeleton"));
         exposure_field = reinterpret_cast<decltype(exposure_field)>(sym("rto_exposure_field"));
         download_exposure = reinterpret_cast<decltype(download_exposure)>(sym("rto_download_exposure"));
+        dose_field = reinterpret_cast<decltype(dose_field)>(sym("rto_dose_field"));
+        download_dose = reinterpret_cast<decltype(download_dose)>(sym("rto_download_dose"));
+        download_dose_coverage = reinterpret_cast<decltype(download_dose_coverage)>(sym("rto_download_dose_coverage"));
         thickness_field = reinterpret_cast<decltype(thickness_field)>(sym("rto_thickness_field"));
         download_thickness = reinterpret_cast<decltype(download_thickness)>(sym("rto_download_thickness"));
         thickness_histogram = reinterpret_cast<decltype(thickness_histogram)>(sym("rto_thickness_histogram"));
@@ -1226,6 +1233,59 @@ int RayTracerBVH::exposure(std::vector<int32_t>& e) {
     e.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
     const int rc = api().download_exposure(m_ctx, e.data(), (int64_t)e.size());
     if (rc != RTO_OK) { e.clear(); return regionFailed(rc, "exposure"); }
+    return RTO_OK;
+}
+
+// The dose field of the first GPU's resident grid (rto_dose_field); the code is RTO_OK or the refusal's.
+int RayTracerBVH::doseField(const std::vector<int32_t>& sources, const std::vector<uint32_t>& transmit, int falloff, int mode, int reach,
+                            rto_dose_summary* summary) {
+    if (!computeUsable("doseField")) return RTO_E_INVALID;
+    if (sources.size() % 4 != 0) {
+        m_lastError = "doseField: four int32 a source: i, j, k and the weight";
+        return RTO_E_INVALID;
+    }
+    if (m_numNodes > 0 && !makeGridResident("dose field")) return RTO_E_HIP;
+    const int rc = api().dose_field(m_ctx, sources.empty() ? nullptr : sources.data(), (int)(sources.size() / 4), transmit.empty() ? nullptr : transmit.data(),
+                                    (int)transmit.size(), falloff, mode, reach, summary);
+    if (rc != RTO_OK) return regionFailed(rc, "doseField");
+    m_doseSources = (int)(sources.size() / 4);
+    return RTO_OK;
+}
+
+// The resident dose field, downloaded.
+int RayTracerBVH::dose(std::vector<int32_t>& e) {
+    e.clear();
+    if (!computeUsable("dose")) return RTO_E_INVALID;
+    e.resize((size_t)m_grid.dimX * m_grid.dimY * m_grid.dimZ);
+    const int rc = api().download_dose(m_ctx, e.data(), (int64_t)e.size());
+    if (rc != RTO_OK) { e.clear(); return regionFailed(rc, "dose"); }
+    return RTO_OK;
+}
+
+// The resident dose field's coverage table, downloaded: one count per source of the last doseField.
+int RayTracerBVH::doseCoverage(std::vector<int64_t>& covered) {
+    covered.clear();
+    if (!computeUsable("doseCoverage")) return RTO_E_INVALID;
+    covered.resize((size_t)RTO_DOSE_MAX_SOURCES);
+    const int rc = api().download_dose_coverage(m_ctx, covered.data(), (int64_t)covered.size());
+    if (rc != RTO_OK) { covered.clear(); return regionFailed(rc, "doseCoverage"); }
+    covered.resize((size_t)m_doseSources);
+    return RTO_OK;
+}
+
+// The voxel of the resident dose field with the largest value, the smallest linear index among equals.
+int RayTracerBVH::hottestVoxel(int32_t ijk[3], int32_t* value) {
+    std::vector<int32_t> e;
+    const int rc = dose(e);
+    if (rc != RTO_OK) return rc;
+    const auto top = std::max_element(e.begin(), e.end());              // the first of equals
+    if (top == e.end() || *top < 0) {
+        m_lastError = "hottestVoxel: the dose field evaluates no voxel";
+        return RTO_E_INVALID;
+    }
+    const int64_t v = top - e.begin();
+    ijk[0] = (int32_t)(v % m_grid.dimX); ijk[1] = (int32_t)(v / m_grid.dimX % m_grid.dimY); ijk[2] = (int32_t)(v / m_grid.dimX / m_grid.dimY);
+    if (value) *value = *top;
     return RTO_OK;
 }
 

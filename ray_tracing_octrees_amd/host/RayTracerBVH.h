@@ -308,6 +308,20 @@ public:
     int exposureField(const std::vector<int32_t>& dirs, const std::vector<int32_t>& weights, int mode = RTO_EXPO_SKIN, int reach = RTO_EXPO_NO_LIMIT,
                       rto_expo_summary* summary = nullptr);
     int exposure(std::vector<int32_t>& e);
+    // Dose fields of the resident grid (rto_dose_field).  doseField makes, on the first GPU, for every
+    // evaluated EMPTY voxel (RTO_DOSE_ALL / RTO_DOSE_SKIN) the sum over the point sources -- four int32 each: the voxel i, j, k
+    // of the grid and the weight -- of the weight times transmit[k] in Q16, k the SOLID voxels the segment to the source crosses
+    // (`transmit` empty: plain line of sight), divided by the squared distance under RTO_DOSE_FALLOFF_INVERSE_SQUARE, for the
+    // sources within `reach` voxels; the summary (may be null) gives the evaluated voxels, the sum, the dark and the seen ones and
+    // the peak without a download.  dose downloads the resident field (one int32 per voxel, x fastest, -1 for a voxel that is not
+    // evaluated), doseCoverage the voxels with a clear view of each source of the last doseField, and hottestVoxel gives the
+    // peak's voxel (the smallest index among equals) and value.  Each returns RTO_OK or the refusal's code, which is negative
+    // (lastError).  They need the compute pipeline; the CPU form of the same rule for a VoxelGrid is host/Dose.h.
+    int doseField(const std::vector<int32_t>& sources, const std::vector<uint32_t>& transmit = {}, int falloff = RTO_DOSE_FALLOFF_NONE,
+                  int mode = RTO_DOSE_ALL, int reach = RTO_DOSE_NO_LIMIT, rto_dose_summary* summary = nullptr);
+    int dose(std::vector<int32_t>& e);
+    int doseCoverage(std::vector<int64_t>& covered);
+    int hottestVoxel(int32_t ijk[3], int32_t* value = nullptr);
     // Part segmentation of the resident grid (rto_segment_parts / rto_edit_parts).  segmentParts runs the
     // watershed of the squared distance field of `set` on the first GPU under `connectivity` and merges basins with `ratio` in
     // [0, RTO_PARTS_RATIO_MAX] (0: the components, 1001: the basins): one int32 per voxel, x fastest, the part's number, -1 outside
@@ -428,6 +442,7 @@ private:
     ProjectionValues m_projection;                     // the last projectField's outputs per pixel
     CompositeValues m_composite;                       // the last compositeField's outputs per pixel
     rto_composite_summary m_compositeSummary{ 0, 0, 0, 0 };
+    int m_doseSources = 0;                             // the last doseField's sources: the length of its coverage table
 
     mutable std::vector<float> m_frame;
     mutable bool m_frameStale = false;   // the GPU holds a newer frame than m_frame

@@ -14,6 +14,7 @@
 #include "Distance.h"
 #include "Geodesic.h"
 #include "Skeleton.h"
+#include "Dose.h"
 #include "Exposure.h"
 #include "Thickness.h"
 #include "Parts.h"
@@ -641,6 +642,42 @@ int rtoh_rt_exposure(RayTracerBVH* rt, int32_t* e, int64_t capacity) {
     if (e) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), e);
     return RTO_OK;
 }
+// Dose fields.  rtoh_dose_cpu: the CPU form of the rule (Dose.h) on a grid: e (dims product int32), covered (n int64), summary, steps
+// and bad_source may be NULL; the code of rto_dose_field.  rtoh_rt_dose_field / rtoh_rt_dose / rtoh_rt_dose_coverage:
+// RayTracerBVH::doseField / dose / doseCoverage, the class's codes; e and covered are filled up to capacity, *count = the sources.
+int rtoh_dose_cpu(const VoxelGrid* g, const int32_t* sources, int n, const uint32_t* transmit, int m, int falloff, int mode, int reach, int32_t* out,
+                  int64_t* covered, rto_dose_summary* summary, int64_t* steps, int* bad_source) {
+    std::vector<int32_t> e;
+    std::vector<int64_t> cover;
+    const int rc = doseFieldCPU(*g, sources, n, transmit, m, falloff, mode, reach, e, &cover, summary, steps, bad_source);
+    if (rc != RTO_OK) return rc;
+    if (out) std::copy(e.begin(), e.end(), out);
+    if (covered) std::copy(cover.begin(), cover.end(), covered);
+    return RTO_OK;
+}
+int rtoh_rt_dose_field(RayTracerBVH* rt, const int32_t* sources, int n, const uint32_t* transmit, int m, int falloff, int mode, int reach,
+                       rto_dose_summary* summary) {
+    const size_t count = sources && n > 0 ? (size_t)n : 0;
+    if (transmit && m < 1) return RTO_E_INVALID;                        // an empty vector would stand for NULL: line of sight
+    return rt->doseField(std::vector<int32_t>(sources, sources + 4 * count),
+                         transmit && m > 0 ? std::vector<uint32_t>(transmit, transmit + m) : std::vector<uint32_t>(), falloff, mode, reach, summary);
+}
+int rtoh_rt_dose(RayTracerBVH* rt, int32_t* e, int64_t capacity) {
+    std::vector<int32_t> f;
+    const int rc = rt->dose(f);
+    if (rc != RTO_OK) return rc;
+    if (e) std::copy(f.begin(), f.begin() + (size_t)std::min<int64_t>((int64_t)f.size(), capacity), e);
+    return RTO_OK;
+}
+int rtoh_rt_dose_coverage(RayTracerBVH* rt, int64_t* covered, int64_t capacity, int64_t* count) {
+    std::vector<int64_t> t;
+    const int rc = rt->doseCoverage(t);
+    if (rc != RTO_OK) return rc;
+    if (covered) std::copy(t.begin(), t.begin() + (size_t)std::min<int64_t>((int64_t)t.size(), capacity), covered);
+    if (count) *count = (int64_t)t.size();
+    return RTO_OK;
+}
+int rtoh_rt_hottest_voxel(RayTracerBVH* rt, int32_t ijk[3], int32_t* value) { return rt->hottestVoxel(ijk, value); }
 // Geodesic fields.  rtoh_geodesic_cpu: the CPU form of the rule (Geodesic.h) on a grid: g (dims product int32) and summary may be
 // NULL; the code of rto_geodesic_field.  rtoh_geodesic_paths_cpu walks a field of that grid; rtoh_geodesic_flood_cpu edits the grid
 // in place (the number flipped, or the refusal's code).

@@ -6,6 +6,7 @@ and the legend (range, the 256 bins, the LUT) as JSON beside it.  numpy only.
     python3 tools/field_view.py --scene sphere128 --field thickness --clip 0.5 --out cut.ppm
     python3 tools/field_view.py --scene sphere128 --field distance --project max --out xray.ppm
     python3 tools/field_view.py --scene calgary --field air --composite --over-lit --out fog.ppm
+    python3 tools/field_view.py --scene calgary --field dose --sources 200,120,3,1000000 60,40,5,500000 --composite --out dose.ppm
 
 Scenes: sphereN (the test sphere of edge N, Camera(0.5, 0.7, 1.8)) and calgary (the shipped city grid, Camera(0.6, 0.5, 3500)).
 Fields: distance (to EMPTY, SQRT scale: how deep inside), thickness (SQRT), skeleton, labels and parts (CATEGORY), geodesic
@@ -19,7 +20,10 @@ projection instead (rto_project_field_host): the reduction of the field along ev
 stop at the first one); --stop Q ends a ray once its transmittance (of 65536) is at most Q; --range LO HI is the range of the
 colours (by default the smallest and largest value a 160 x 90 projection from the same camera finds).  --over-lit renders the lit
 frame on the device and composites over it in place (needs torch for the device buffers); without it the background is the sky
-colour.  Field `air` is the distance to SOLID, which lives in the empty space."""
+colour.  Field `air` is the distance to SOLID, which lives in the empty space.  Field `dose` (rto_dose_field) takes its point sources
+from --sources, one `i,j,k,w` each (a voxel of the grid and a weight), with --transmit (Q16 table entries; none: line of sight),
+--reach and the inverse-square falloff unless --no-falloff; it has no FIELD_* code, so its plain view, --project and --composite go
+through Context.dose_device() and FIELD_CALLER on the device entry points (needs torch for the device buffers)."""
 import argparse
 import json
 import os
@@ -90,6 +94,50 @@ def make_field(ctx, field, up, voxel):
     raise SystemExit(f"unknown field {field}")
 
 
+def dose_frame(ctx, f, a, lut, kw):
+    """The frame of --field dose and its legend: the resident dose field as FIELD_CALLER's device volume, whichever the mode."""
+    import torch
+    src = np.asarray([[int(c) for c in s.split(",")] for s in a.sources], np.int64).reshape(-1, 4)
+    e, s = ctx.dose_field(src, a.transmit, hip.DOSE_FALLOFF_NONE if a.no_falloff else hip.DOSE_FALLOFF_INVERSE_SQUARE,
+                          hip.DOSE_ALL if (a.composite or a.project) else hip.DOSE_SKIN, a.reach)
+    del e
+    volume = ctx.dose_device()
+    kw = dict(kw, source=hip.FIELD_CALLER, scale=hip.SCALE_SQRT, range=tuple(a.range) if a.range else (0, max(1, int(s["peak"]))))
+    if a.window:
+        kw["valid"] = tuple(a.window)
+    n = f.width * f.height
+    sky = (0.55, 0.7, 0.9, 1.0)
+    d_rgba = torch.empty(n * 4, dtype=torch.float32, device="cuda")
+    d_summary = torch.zeros(4, dtype=torch.int64, device="cuda")
+    legend = {name: int(s[name]) for name in hip.DOSE_SUMMARY_DTYPE.names}
+    legend.update(covered=ctx.dose_coverage().tolist(), dose_ms=list(ctx.last_dose_ms()))
+    if a.composite:
+        alpha = np.clip(a.opacity // 4 + (np.arange(256) * (a.opacity - a.opacity // 4)) // 255, 0, 255).astype(np.uint32)
+        lut = (lut & np.uint32(0x00ffffff)) | (alpha << np.uint32(24))
+        kw["valid"] = kw.get("valid", (1, 0x7ffffffe))                  # dark air adds nothing
+        comp = hip.make_field_composite(stop_q16=a.stop, occlude=not a.see_through, background_rgba=sky, miss_rgba=sky, **kw)
+        d_lut = torch.from_numpy(lut.view(np.int32)).cuda()
+        ctx.composite_field_device(f, comp, d_lut.data_ptr(), d_rgba.data_ptr(), volume, d_summary=d_summary.data_ptr())
+        names, ms = hip.COMPOSITE_SUMMARY_DTYPE, ctx.last_composite_ms
+    elif a.project:
+        op = {"max": hip.PROJECT_MAX, "min": hip.PROJECT_MIN, "mean": hip.PROJECT_MEAN, "count": hip.PROJECT_COUNT, "first": hip.PROJECT_FIRST}[a.project]
+        view = hip.make_field_projection(op=op, miss_rgba=sky, none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
+        d_lut = torch.from_numpy(lut.view(np.int32)).cuda()
+        ctx.project_field_device(f, view, d_lut.data_ptr(), d_rgba.data_ptr(), volume, d_summary=d_summary.data_ptr())
+        names, ms = hip.FIELD_VIEW_SUMMARY_DTYPE, ctx.last_projection_ms
+    else:
+        view = hip.make_field_view(sample=hip.SAMPLE_FRONT, mode=hip.QUERY_FIRST if a.mode == "first" else hip.QUERY_CLOSEST, shade=not a.flat,
+                                   miss_rgba=sky, none_rgba=(0.3, 0.3, 0.3, 1.0), **kw)
+        d_lut = torch.from_numpy(lut.view(np.int32)).cuda()
+        ctx.render_field_device(f, view, d_lut.data_ptr(), d_rgba.data_ptr(), volume, d_summary=d_summary.data_ptr())
+        names, ms = hip.FIELD_VIEW_SUMMARY_DTYPE, ctx.last_field_view_ms
+    ctx.synchronize()
+    frame = d_summary.cpu().numpy().view(names)[0]
+    legend.update({name: int(frame[name]) for name in names.names})
+    legend.update(range=list(kw["range"]), scale=int(kw["scale"]), lut_rgba=lut.view(np.uint8).reshape(256, 4).tolist(), ms=list(ms()))
+    return d_rgba.cpu().numpy().reshape(f.height, f.width, 4), legend
+
+
 def write_ppm(path, rgba):
     """Binary PPM of the frame's r, g, b (clamped to [0, 1], 8 bits)."""
     rgb = np.clip(np.rint(rgba[..., :3] * 255.0), 0, 255).astype(np.uint8)
@@ -152,18 +200,33 @@ def main():
     ap.add_argument("--opacity", type=int, default=24, help="with --composite: the largest alpha byte of the LUT")
     ap.add_argument("--stop", type=int, default=256, help="with --composite: stop_q16")
     ap.add_argument("--range", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="with --composite: the colours' range")
+    ap.add_argument("--sources", nargs="+", default=None, metavar="I,J,K,W", help="with --field dose: the point sources")
+    ap.add_argument("--transmit", type=int, nargs="+", default=None, help="with --field dose: the Q16 transmission table")
+    ap.add_argument("--reach", type=int, default=None, help="with --field dose: the reach in voxels")
+    ap.add_argument("--no-falloff", action="store_true", help="with --field dose: no inverse-square falloff")
     ap.add_argument("--out", default="field_view.ppm")
     a = ap.parse_args()
     grid, cam, up = scene(a.scene)
     ctx = rto.Context(0)
     ctx.build_octree(grid.data, grid.min, grid.voxelSize)
-    kw = make_field(ctx, a.field, up, grid.voxelSize)
+    if a.field == "dose" and not a.sources:
+        raise SystemExit("--field dose needs --sources I,J,K,W ...")
+    kw = {} if a.field == "dose" else make_field(ctx, a.field, up, grid.voxelSize)
     dx, dy, dz = grid.dims
     if a.clip is not None:
         kw["clip"] = ((0, 0, 0), (max(1, min(dx, int(round(a.clip * dx)))), dy, dz))
     lut = hip.ramp_lut(HEAT)
     W, H = a.width, a.height
     f = rto.make_frame(cam.getView(), cam.getPos(), W / H, 45.0, W, H)
+    if a.field == "dose":
+        rgba, legend = dose_frame(ctx, f, a, lut, kw)
+        write_ppm(a.out, rgba)
+        legend.update(scene=a.scene, field=a.field, frame=[W, H], project=a.project, composite=bool(a.composite))
+        with open(os.path.splitext(a.out)[0] + ".legend.json", "w") as fh:
+            json.dump(legend, fh)
+        print(f"{a.out}: {W}x{H}, dose of {len(a.sources)} sources: {legend['seen']} of {legend['evaluated']} voxels see one, peak {legend['peak']}")
+        ctx.close()
+        return
     if a.composite:
         rgba, legend = composite(ctx, f, kw, lut, a)
         write_ppm(a.out, rgba)
