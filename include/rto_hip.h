@@ -1753,6 +1753,86 @@ int  rto_download_dose_coverage(rto_context* ctx, int64_t* out /* n */, int64_t 
 /* Device time in ms of the last rto_dose_field: prepare (bit rows, selection, uploads), march, summary (-1: not run). */
 int  rto_last_dose_ms(const rto_context* ctx, float ms[3]);
 
+/* ---- dual contouring -----------------------------------------------------------
+ * The reference's second surface extractor over the resident grid, made on the GPU: one vertex per voxel,
+ * placed by the Hermite data of the sign changes around it, and a quad of two triangles wherever a cell and its +X, +Y or +Z
+ * neighbour differ -- the same 12-float records rto_extract_mesh and rto_extract_isosurface_* give.  This is the reference's
+ * deterministic pair: the per-voxel vertex rule gatherHermiteData(grid, x, y, z, 1) -> calculateIntersection -> generateDualVertex
+ * with QEFSolver (S/AdaptiveDualContouringRenderer.cpp:49-161, 1090-1357) and its triangulation buildTrianglesCPU (:377-486), word
+ * for word, oddities included.  The adaptive createTriangles path and the shipped GLSL are not.  All floats are float32, one IEEE
+ * operation per operator, in the order written, with no contraction; comparisons the reference makes against a double literal
+ * (1e-6, 1e-10) are made in double.  rto_update_frustum is ignored.  A voxel is solid when it is FILLED.  Rule:
+ *   vertex    of voxel (x, y, z): centre[a] = (gridMin[a] + (float)c[a] * voxelSize) + 0.5f * voxelSize.  Hermite points: for the
+ *             voxels x .. min(x + 1, dimX - 1) (likewise y, z; z slowest), for each its +X, +Y, +Z neighbour in that order (skipped
+ *             outside the grid), one point per sign change: position p1 + 0.5f * (p2 - p1) with p = gridMin + (float)c * voxelSize;
+ *             normal: the central differences of the +-1 scalar (solid: -1; out of grid: +1) on the two axes perpendicular to the
+ *             edge, taken at the first voxel, normalised (v * (1.0f / sqrt(dot(v, v)))), or the edge direction when their squared
+ *             length is below 1e-10; negated when (dot(normal, edge) > 0) == (the neighbour is solid).  No point: the vertex is the
+ *             centre.  Otherwise generateDualVertex(points, centre, voxelSize) in full: bounds centre -+ 0.5f * voxelSize inset by
+ *             0.001f * voxelSize; the mass point; the summed normal, when longer than 0.0001f normalised and, with a component
+ *             above 0.85f, snapped to that axis: the points whose normalised normal has dot > 0.7f with it give a plane point, the
+ *             centre is projected onto that plane and clamped; otherwise QEFSolver: AtA and Atb of the renormalised normals, the
+ *             mass point for at most 2 points, else (AtA + 0.3 I)^-1 Atb by glm 0.9.9.7's determinant and inverse, relaxed by 0.7
+ *             towards it from the mass point, accepted when its squared distance to the mass point is below the inset cell size
+ *             squared and then mixed 0.2 with the mass point (mix(x, y, a) = x * (1 - a) + y * a), else the mass point; clamped;
+ *             mixed 0.1 with the mass point.
+ *   cells     (x, y, z) with 0 <= c[a] < dim[a] - 1, or, with a clip box, clip_lo[a] <= c[a] < min(clip_hi[a], dim[a] - 1); z slowest.
+ *             Vertices are always those of the whole grid: boxes that partition the cells partition the list.  A grid with a
+ *             dimension of 1 has no cell: an empty list, not an error.  There is no pad ring: like the reference's loop, the call
+ *             does not close the surface at the grid's faces.
+ *   faces     each cell tests +X, +Y, +Z in that order; a face exists when solid(c) != solid(c + e_a).  Its four voxels V00, V01,
+ *             V11, V10 are c + (0, +y, +x+y, +x) for X, (0, +x, +x+y, +y) for Y, (0, +y, +y+z, +z) for Z; its triangles are
+ *             (V00, V01, V11) then (V00, V11, V10) of their vertices.
+ *   normal    n = cross(v1 - v0, v2 - v0), l2 = dot(n, n); l2 > 0 and finite: n * (1.0f / sqrt(l2)), negated when the cell's own
+ *             voxel is solid; otherwise (+0, +0, +0) and the triangle counts as degenerate.
+ *   area rule RTO_DC_AREA_REFERENCE keeps a triangle when 0.5f * sqrt(l2) > 1e-6 (the reference's absolute test: at voxel sizes
+ *             near 1 / 512 it drops real triangles); RTO_DC_AREA_NONE keeps every triangle.
+ *   record    12 floats per triangle: v0, v1, v2, normal.  tri_cell[j] = (z * dimY + y) * dimX + x of the owning cell.
+ *   summary   faces found; triangles kept; triangles dropped by the area rule (kept + dropped = 2 * faces); degenerate triangles
+ *             among the kept; vertex_voxels: the voxels that are one of the four of at least one face found and have at least one
+ *             Hermite point.
+ * rto_extract_dual_contour is synchronous on the context's stream (one count is read back).  The result is a snapshot in a buffer of
+ * its own, beside rto_extract_mesh's and the isosurface's, valid until the next dual-contour extraction or rto_destroy, untouched by
+ * later edits or builds.  An empty result is RTO_OK with 0 triangles; a box without a cell runs no kernel.  Errors, each leaving the
+ * previous list and the context untouched, checked in this order: RTO_E_INVALID: NULL params, an unknown area_rule, reserved != 0.
+ * RTO_E_NO_OCTREE: nothing uploaded.  RTO_E_UNSUPPORTED: no resident grid (rto_upload_octree), then more than 2^31 - 1 voxels.
+ * RTO_E_INVALID: a clip box with clip_lo[a] < 0, clip_hi[a] > dim[a] or clip_lo[a] >= clip_hi[a].  RTO_E_UNSUPPORTED: more than
+ * 2^31 - 1 triangles (the count saturates).  A device failure (RTO_E_HIP) after the output buffer has been replaced by a larger one
+ * leaves no list. */
+#define RTO_DC_AREA_REFERENCE 0
+#define RTO_DC_AREA_NONE      1
+typedef struct rto_dc_params {      /* 48 bytes */
+    int32_t  area_rule;             /* RTO_DC_AREA_* */
+    int32_t  clip;                  /* != 0: the box of cells below applies */
+    int32_t  clip_lo[3], clip_hi[3];   /* cell indices, x y z: 0 <= clip_lo < clip_hi <= dim */
+    int32_t  reserved[4];           /* 0 */
+} rto_dc_params;
+typedef struct rto_dc_summary {     /* 48 bytes */
+    int64_t  faces;
+    int64_t  triangles;             /* kept: the length of the list */
+    int64_t  dropped;               /* by the area rule */
+    int64_t  degenerate;            /* kept triangles whose normal is (0, 0, 0) */
+    int64_t  vertex_voxels;         /* voxels read by a face that have at least one Hermite point */
+    int64_t  reserved;
+} rto_dc_summary;
+typedef struct rto_dual_vertex {    /* 16 bytes */
+    float    p[3];
+    int32_t  points;                /* Hermite points gathered; -1: the index lies outside the grid (p is 0) */
+} rto_dual_vertex;
+
+int  rto_extract_dual_contour(rto_context* ctx, const rto_dc_params* params, rto_dc_summary* summary /* host; may be NULL */);
+/* The last list where it lies: num_tris records of 48 bytes and as many int32 (both may be NULL for the count alone). */
+int  rto_dual_contour_device(rto_context* ctx, void** d_tris, int32_t** d_tri_cell, int64_t* num_tris);
+/* Copies it out; tris == NULL and tri_cell == NULL: the count alone.  RTO_E_INVALID: none extracted yet, capacity too small. */
+int  rto_download_dual_contour(rto_context* ctx, float* tris, int64_t capacity, int32_t* tri_cell /* may be NULL */, int64_t* num_tris);
+/* Device time in ms of the last extraction: count, rank, emit (-1: not run, or the box had no cell and no kernel ran). */
+int  rto_last_dual_contour_ms(const rto_context* ctx, float ms[3]);
+/* The vertex of any voxel of the resident grid, one thread per voxel: voxels[i] = (z * dimY + y) * dimX + x; an index outside
+ * [0, dimX dimY dimZ) gives points = -1 and zeros.  Synchronous on the context's stream.  Errors, in order: RTO_E_INVALID (n < 0, or
+ * n > 0 with a NULL pointer; 8- and 4-byte alignment), RTO_E_NO_OCTREE, RTO_E_UNSUPPORTED (no resident grid).  n == 0 is RTO_OK. */
+int  rto_query_dual_vertices_device(rto_context* ctx, const int64_t* d_voxels, int64_t n, rto_dual_vertex* d_out);
+int  rto_query_dual_vertices_host(rto_context* ctx, const int64_t* voxels, int64_t n, rto_dual_vertex* out);
+
 /* ---- instrumentation ------------------------------------------------------*/
 /* Renders the frame once with counting enabled (synchronous). */
 int  rto_frame_stats(rto_context* ctx, const rto_frame* frame, rto_stats* out);

@@ -275,6 +275,11 @@ struct rto_context {
     int* d_isoCell = nullptr;
     int64_t isoTris = -1, isoCap = 0;         // -1: no isosurface extracted yet
     float isoMs[3] = { -1.f, -1.f, -1.f };
+    // dual contouring (rto_dc.inc): the last list, a snapshot the context owns, apart from the two above
+    float4* d_dc = nullptr;
+    int* d_dcCell = nullptr;
+    int64_t dcTris = -1, dcCap = 0;           // -1: no list extracted yet
+    float dcMs[3] = { -1.f, -1.f, -1.f };
 
     // connected components (rto_components.inc): the last labelling of the resident grid; dropped whenever the grid changes
     int* d_ccLabels = nullptr;                // nullptr: no labels resident
@@ -528,6 +533,8 @@ void rto_destroy(rto_context* c) {
     (void)hipFree(c->d_meshNode);
     (void)hipFree(c->d_iso);
     (void)hipFree(c->d_isoCell);
+    (void)hipFree(c->d_dc);
+    (void)hipFree(c->d_dcCell);
     c->timer.destroy();
     if (c->evCull) (void)hipEventDestroy(c->evCull);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -3099,6 +3106,7 @@ int rto_synchronize(rto_context* c) {
 #include "rto_tri_lit.inc"
 #include "rto_mesh.inc"
 #include "rto_iso.inc"
+#include "rto_dc.inc"
 #include "rto_region.inc"
 #include "rto_components.inc"
 #include "rto_distance.inc"

@@ -66,6 +66,8 @@ SYMBOLS = (
     "rto_composite_field_device", "rto_composite_field_host", "rto_last_composite_ms",
     "rto_extract_isosurface_device", "rto_extract_isosurface_host", "rto_isosurface_device", "rto_download_isosurface",
     "rto_last_isosurface_ms",
+    "rto_extract_dual_contour", "rto_dual_contour_device", "rto_download_dual_contour", "rto_last_dual_contour_ms",
+    "rto_query_dual_vertices_device", "rto_query_dual_vertices_host",
 )
 MESH_MC, MESH_CUBES = 0, 1
 SPLIT_MAX_FRAMES = 32
@@ -367,6 +369,35 @@ def make_iso_params(source, level, outside=0.0, valid=(0, 0x7ffffffe), pad=True,
     v.valid_lo, v.valid_hi = int(valid[0]), int(valid[1])
     v.level, v.outside = _f(level), _f(outside)
     v.pad = int(pad)
+    v.clip = 0 if clip is None else 1
+    for a in (0, 1, 2):
+        v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
+        v.clip_hi[a] = 0 if clip is None else int(clip[1][a])
+    return v
+
+
+# struct rto_dc_params (48 bytes) / rto_dc_summary (48 bytes) / rto_dual_vertex (16 bytes): dual contouring (rto_extract_dual_contour)
+DC_AREA_REFERENCE, DC_AREA_NONE = 0, 1
+
+
+class DcParams(C.Structure):
+    _fields_ = [("area_rule", C.c_int32), ("clip", C.c_int32), ("clip_lo", C.c_int32 * 3), ("clip_hi", C.c_int32 * 3),
+                ("reserved", C.c_int32 * 4)]
+
+
+class DcSummary(C.Structure):
+    _fields_ = [("faces", C.c_int64), ("triangles", C.c_int64), ("dropped", C.c_int64), ("degenerate", C.c_int64),
+                ("vertex_voxels", C.c_int64), ("reserved", C.c_int64)]
+
+
+DUAL_VERTEX_DTYPE = np.dtype([("p", np.float32, 3), ("points", np.int32)])
+
+
+def make_dc_params(area_rule=DC_AREA_REFERENCE, clip=None) -> DcParams:
+    """An rto_dc_params.  area_rule: DC_AREA_REFERENCE drops triangles of area <= 1e-6 as the reference does (at voxel sizes near
+    1 / 512 that drops real ones), DC_AREA_NONE keeps all.  clip: None or ((x0, y0, z0), (x1, y1, z1)) in cell indices."""
+    v = DcParams()
+    v.area_rule = int(area_rule)
     v.clip = 0 if clip is None else 1
     for a in (0, 1, 2):
         v.clip_lo[a] = 0 if clip is None else int(clip[0][a])
@@ -718,6 +749,12 @@ def load():
     L.rto_isosurface_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.rto_download_isosurface.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
     L.rto_last_isosurface_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_extract_dual_contour.argtypes = [vp, C.POINTER(DcParams), C.POINTER(DcSummary)]
+    L.rto_dual_contour_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.rto_download_dual_contour.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.rto_last_dual_contour_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rto_query_dual_vertices_device.argtypes = [vp, vp, C.c_int64, vp]
+    L.rto_query_dual_vertices_host.argtypes = [vp, vp, C.c_int64, vp]
     _lib = L
     return L
 
@@ -1953,6 +1990,53 @@ class Context:
     def last_isosurface_ms(self):
         """Device ms of the last isosurface: (count, rank, emit); -1: not run."""
         return self._last_ms("rto_last_isosurface_ms", 3)
+
+    # -- dual contouring ----------------------------------------------------
+    def extract_dual_contour_count(self, params: DcParams) -> DcSummary:
+        """rto_extract_dual_contour: the list stays on the device (dual_contour_device / download_dual_contour)."""
+        summary = DcSummary()
+        self._check(self._L.rto_extract_dual_contour(self._h, C.byref(params) if params is not None else None, C.byref(summary)))
+        return summary
+
+    def download_dual_contour(self):
+        """The last dual-contour list: (tris float32 (n, 12): v0, v1, v2, normal; tri_cell int32 (n,): the owning cell)."""
+        n = C.c_int64()
+        self._check(self._L.rto_download_dual_contour(self._h, None, 0, None, C.byref(n)))
+        tris = np.zeros((n.value, 12), np.float32)
+        cell = np.zeros(n.value, np.int32)
+        if n.value:
+            self._check(self._L.rto_download_dual_contour(self._h, tris.ctypes.data, n.value, cell.ctypes.data, C.byref(n)))
+        return tris, cell
+
+    def extract_dual_contour(self, params: DcParams):
+        """Dual contouring of the resident grid, in the reference's buildTrianglesCPU order.  Returns
+        (tris (n, 12), tri_cell (n,), summary)."""
+        summary = self.extract_dual_contour_count(params)
+        tris, cell = self.download_dual_contour()
+        return tris, cell, summary
+
+    def dual_contour_device(self):
+        """(device pointer of the 48-byte records, device pointer of tri_cell, count) of the last dual-contour list."""
+        t, cl, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._L.rto_dual_contour_device(self._h, C.byref(t), C.byref(cl), C.byref(n)))
+        return t.value or 0, cl.value or 0, n.value
+
+    def last_dual_contour_ms(self):
+        """Device ms of the last dual-contour extraction: (count, rank, emit); -1: not run."""
+        return self._last_ms("rto_last_dual_contour_ms", 3)
+
+    def query_dual_vertices(self, voxels, out=None):
+        """rto_query_dual_vertices_*: the dual-contouring vertex of each voxel (linear indices, x fastest).  voxels: a host array
+        of int64 -> a DUAL_VERTEX_DTYPE array (p, points; points = -1 outside the grid); or a device int64 tensor with `out` a
+        device tensor of 16 bytes per voxel, which is filled and returned."""
+        if hasattr(voxels, "data_ptr") and getattr(voxels, "is_cuda", False):
+            n = int(voxels.numel())
+            self._check(self._L.rto_query_dual_vertices_device(self._h, voxels.data_ptr(), n, out.data_ptr() if out is not None else None))
+            return out
+        v = np.ascontiguousarray(np.asarray(voxels, dtype=np.int64).reshape(-1))
+        res = np.zeros(len(v), DUAL_VERTEX_DTYPE)
+        self._check(self._L.rto_query_dual_vertices_host(self._h, v.ctypes.data, len(v), res.ctypes.data))
+        return res
 
     def scene_bounds(self) -> SceneBounds:
         b = SceneBounds()

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _build
 from .hip import (BRUSH_DTYPE, COMPONENT_DTYPE, DIST_SUMMARY_DTYPE, DOSE_SUMMARY_DTYPE, EXPO_SUMMARY_DTYPE, FIELD_VIEW_SUMMARY_DTYPE, GEO_SUMMARY_DTYPE, HIT_DTYPE, MEASURE_DTYPE, NEAREST_DTYPE, NECK_DTYPE, NODE_DTYPE, PART_DTYPE, PARTS_SUMMARY_DTYPE, POINT_HIT_DTYPE, REGION_DTYPE, SKEL_SUMMARY_DTYPE, SPAN_DTYPE, TRI_HIT_DTYPE,
-                  THICK_MAX_C, THICK_SUMMARY_DTYPE, IsoParams, IsoSummary, RtoError, _f)
+                  THICK_MAX_C, THICK_SUMMARY_DTYPE, IsoParams, IsoSummary, DcParams, DcSummary, DUAL_VERTEX_DTYPE, RtoError, _f)
 
 _lib = None
 _vp = C.c_void_p
@@ -299,6 +299,19 @@ def load():
     L.rtoh_iso_surface_volume_ms.restype = C.c_double
     L.rtoh_rt_iso_surface.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_int, _vp, C.POINTER(C.c_int64)]
     L.rtoh_rt_iso_surface.restype = _vp
+    L.rtoh_dual_contour_volume.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.POINTER(DcParams), C.POINTER(DcSummary),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.rtoh_dual_contour_volume.restype = _vp
+    L.rtoh_dual_contour_volume_ms.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.POINTER(DcParams), C.POINTER(C.c_int64)]
+    L.rtoh_dual_contour_volume_ms.restype = C.c_double
+    L.rtoh_dual_vertex_volume.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, _vp]
+    L.rtoh_dual_vertex_volume.restype = None
+    L.rtoh_adc_render.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, C.c_int, _vp, C.POINTER(C.c_int64)]
+    L.rtoh_adc_render.restype = _vp
+    L.rtoh_rt_dual_contour.argtypes = [_vp, C.POINTER(DcParams), C.POINTER(DcSummary), C.POINTER(C.c_int64)]
+    L.rtoh_rt_dual_contour.restype = _vp
+    L.rtoh_rt_dual_vertices.argtypes = [_vp, _vp, C.c_int64, _vp]
+    L.rtoh_rt_dual_vertices.restype = C.c_int
     _lib = L
     return L
 
@@ -688,6 +701,63 @@ def isoSurfaceVolumeMs(volume, gridMin, voxelSize: float, params: IsoParams):
     n = C.c_int64(0)
     ms = load().rtoh_iso_surface_volume_ms(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), C.byref(params), C.byref(n))
     return float(ms), int(n.value)
+
+
+def _dc_grid(voxels, gridMin):
+    v = np.ascontiguousarray(np.asarray(voxels, np.uint8))
+    dz, dy, dx = v.shape
+    return v, dx, dy, dz, np.ascontiguousarray(np.asarray(gridMin, np.float32).reshape(3))
+
+
+def dualContourVolume(voxels, gridMin, voxelSize: float, params: DcParams):
+    """Addition: the dual-contouring rule on the CPU, a plain triple loop over the cells of a uint8 grid
+    (dimZ, dimY, dimX; 1 is FILLED).  Returns (tris (n, 18) float32, tri_cell (n,) int32, DcSummary); RtoError where the C ABI refuses."""
+    v, dx, dy, dz, g = _dc_grid(voxels, gridMin)
+    n, rc, summary = C.c_int64(0), C.c_int(0), DcSummary()
+    lst = load().rtoh_dual_contour_volume(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), C.byref(params), C.byref(summary),
+                                          C.byref(rc), C.byref(n))
+    out = np.zeros((n.value, 18), np.float32)
+    cell = np.zeros(n.value, np.int32)
+    load().rtoh_iso_take(lst, out.ctypes.data, cell.ctypes.data)                # one extraction: copied out and freed
+    if rc.value != 0:
+        raise RtoError(rc.value, "dualContourVolume: invalid parameters")
+    return out, cell, summary
+
+
+def dualContourVolumeMs(voxels, gridMin, voxelSize: float, params: DcParams):
+    """Addition: (milliseconds of one dualContourVolume on one core, timed inside the library; triangles)."""
+    v, dx, dy, dz, g = _dc_grid(voxels, gridMin)
+    n = C.c_int64(0)
+    ms = load().rtoh_dual_contour_volume_ms(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), C.byref(params), C.byref(n))
+    return float(ms), int(n.value)
+
+
+def dualVertexVolume(voxels, gridMin, voxelSize: float) -> np.ndarray:
+    """Addition: the dual-contouring vertex of every voxel on the CPU, by the arithmetic the kernels run: a DUAL_VERTEX_DTYPE
+    array (dimZ, dimY, dimX)."""
+    v, dx, dy, dz, g = _dc_grid(voxels, gridMin)
+    out = np.zeros((dz, dy, dx), DUAL_VERTEX_DTYPE)
+    load().rtoh_dual_vertex_volume(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), out.ctypes.data)
+    return out
+
+
+def adaptiveDualContouringVertices(voxels, gridMin, voxelSize: float) -> np.ndarray:
+    """AdaptiveDualContouringRenderer's per-voxel vertex rule in the reference's own shape (gatherHermiteData(size 1),
+    generateDualVertex, QEFSolver): (dimZ, dimY, dimX, 4) float32, w the number of Hermite points."""
+    v, dx, dy, dz, g = _dc_grid(voxels, gridMin)
+    out = np.zeros((dz, dy, dx, 4), np.float32)
+    load().rtoh_adc_render(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), 0, out.ctypes.data, None)
+    return out
+
+
+def adaptiveDualContouringRender(voxels, gridMin, voxelSize: float) -> np.ndarray:
+    """AdaptiveDualContouringRenderer::render's top-level call on the CPU: (n, 18) float32."""
+    v, dx, dy, dz, g = _dc_grid(voxels, gridMin)
+    n = C.c_int64(0)
+    lst = load().rtoh_adc_render(v.ctypes.data, dx, dy, dz, g.ctypes.data, _f(voxelSize), 1, None, C.byref(n))
+    out = np.zeros((n.value, 18), np.float32)
+    load().rtoh_tris_take(lst, out.ctypes.data)
+    return out
 
 
 def freeOctree(root: OctreeNode | None):
@@ -1344,6 +1414,24 @@ class RayTracerBVH:
         out = np.zeros((n.value, 18), np.float32)
         load().rtoh_tris_take(lst, out.ctypes.data)
         return out
+
+    def dualContour(self, params: DcParams):
+        """Addition: RayTracerBVH::dualContour -- dual contouring of the resident grid, made on the GPU (DESIGN.md section 32).
+        ((n, 18) float32, tri_cell (n,) int32, DcSummary); empty with lastError set on an error."""
+        n, summary = C.c_int64(0), DcSummary()
+        lst = load().rtoh_rt_dual_contour(self._h, C.byref(params), C.byref(summary), C.byref(n))
+        out = np.zeros((n.value, 18), np.float32)
+        cell = np.zeros(n.value, np.int32)
+        load().rtoh_iso_take(lst, out.ctypes.data, cell.ctypes.data)
+        return out, cell, summary
+
+    def dualVertices(self, voxels) -> np.ndarray:
+        """Addition: RayTracerBVH::dualVertices -- the vertex of each voxel (linear indices): a DUAL_VERTEX_DTYPE array, or None
+        with lastError set on an error."""
+        v = np.ascontiguousarray(np.asarray(voxels, np.int64).reshape(-1))
+        out = np.zeros(len(v), DUAL_VERTEX_DTYPE)
+        ok = load().rtoh_rt_dual_vertices(self._h, v.ctypes.data, len(v), out.ctypes.data)
+        return out if ok else None
 
     def offsetSurface(self, distanceInVoxels: float) -> np.ndarray:
         """Addition: RayTracerBVH::offsetSurface -- the surface at that distance from the solids (the distance field to the

@@ -54,6 +54,9 @@ struct HipApi {
     decltype(&rto_download_mesh) download_mesh = nullptr;
     decltype(&rto_extract_isosurface_host) extract_isosurface_host = nullptr;
     decltype(&rto_download_isosurface) download_isosurface = nullptr;
+    decltype(&rto_extract_dual_contour) extract_dual_contour = nullptr;
+    decltype(&rto_download_dual_contour) download_dual_contour = nullptr;
+    decltype(&rto_query_dual_vertices_host) query_dual_vertices_host = nullptr;
     decltype(&rto_query_points_host) query_points_host = nullptr;
     decltype(&rto_query_regions_host) query_regions_host = nullptr;
     decltype(&rto_query_nearest_host) query_nearest_host = nullptr;
@@ -153,6 +156,9 @@ struct HipApi {
         download_mesh = reinterpret_cast<decltype(download_mesh)>(sym("rto_download_mesh"));
         extract_isosurface_host = reinterpret_cast<decltype(extract_isosurface_host)>(sym("rto_extract_isosurface_host"));
         download_isosurface = reinterpret_cast<decltype(download_isosurface)>(sym("rto_download_isosurface"));
+        extract_dual_contour = reinterpret_cast<decltype(extract_dual_contour)>(sym("rto_extract_dual_contour"));
+        download_dual_contour = reinterpret_cast<decltype(download_dual_contour)>(sym("rto_download_dual_contour"));
+        query_dual_vertices_host = reinterpret_cast<decltype(query_dual_vertices_host)>(sym("rto_query_dual_vertices_host"));
         query_points_host = reinterpret_cast<decltype(query_points_host)>(sym("rto_query_points_host"));
         query_regions_host = reinterpret_cast<decltype(query_regions_host)>(sym("rto_query_regions_host"));
         query_nearest_host = reinterpret_cast<decltype(query_nearest_host)>(sym("rto_query_nearest_host"));
@@ -702,6 +708,56 @@ std::vector<MCTriangle> RayTracerBVH::isoSurface(int source, float level, float 
         const float* r = rec.data() + 12 * i;
         for (int v = 0; v < 3; v++) out[i].v[v] = rto_host::vec3(r[3 * v], r[3 * v + 1], r[3 * v + 2]);
         out[i].normal[0] = out[i].normal[1] = out[i].normal[2] = rto_host::vec3(r[9], r[10], r[11]);
+    }
+    return out;
+}
+
+std::vector<MCTriangle> RayTracerBVH::dualContour(const rto_dc_params& params, std::vector<int32_t>* triCell, rto_dc_summary* summary) {
+    std::vector<MCTriangle> out;
+    if (triCell) triCell->clear();
+    m_lastError.clear();                       // an empty list with lastError() empty is an empty surface, not a failure
+    if (!computeUsable("dualContour")) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return out;
+    }
+    if (m_numNodes > 0 && !makeGridResident("dual contouring")) return out;
+    std::vector<float> rec;
+    int64_t n = 0;
+    if (api().extract_dual_contour(m_ctx, &params, summary) != RTO_OK || api().download_dual_contour(m_ctx, nullptr, 0, nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] dualContour failed: " << m_lastError << std::endl;
+        return out;
+    }
+    rec.resize((size_t)n * 12);
+    if (triCell) triCell->resize((size_t)n);
+    if (n > 0 && api().download_dual_contour(m_ctx, rec.data(), n, triCell ? triCell->data() : nullptr, &n) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] dualContour failed: " << m_lastError << std::endl;
+        if (triCell) triCell->clear();
+        return out;
+    }
+    out.resize((size_t)n);
+    for (size_t i = 0; i < out.size(); i++) {
+        const float* r = rec.data() + 12 * i;
+        for (int v = 0; v < 3; v++) out[i].v[v] = rto_host::vec3(r[3 * v], r[3 * v + 1], r[3 * v + 2]);
+        out[i].normal[0] = out[i].normal[1] = out[i].normal[2] = rto_host::vec3(r[9], r[10], r[11]);
+    }
+    return out;
+}
+
+std::vector<rto_dual_vertex> RayTracerBVH::dualVertices(const int64_t* voxels, int64_t n) {
+    std::vector<rto_dual_vertex> out;
+    m_lastError.clear();
+    if (!computeUsable("dualVertices")) {
+        std::cerr << "[RayTracerBVH] Compute pipeline not initialized or failed.\n";
+        return out;
+    }
+    if (m_numNodes > 0 && !makeGridResident("dual contouring")) return out;
+    out.resize(n > 0 ? (size_t)n : 0);
+    if (api().query_dual_vertices_host(m_ctx, voxels, n, out.data()) != RTO_OK) {
+        m_lastError = api().last_error(m_ctx);
+        std::cerr << "[RayTracerBVH] dualVertices failed: " << m_lastError << std::endl;
+        out.clear();
     }
     return out;
 }

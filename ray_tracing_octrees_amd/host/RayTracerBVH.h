@@ -385,6 +385,13 @@ public:
     std::vector<MCTriangle> isoSurface(int source, float level, float outside = 0.0f, bool pad = true, const int32_t* volume = nullptr,
                                        std::vector<int32_t>* triCell = nullptr, rto_iso_summary* summary = nullptr);
     std::vector<MCTriangle> offsetSurface(float distanceInVoxels);
+    // Dual contouring of the resident grid, made on the GPU (rto_extract_dual_contour): the list the
+    // reference's AdaptiveDualContouringRenderer gives by its per-voxel vertex rule and buildTrianglesCPU, in its order, with the
+    // area rule and the clip box of cells in `params`.  Empty, with lastError set, on an error.  dualVertices: the vertex of each
+    // of n voxels (linear indices, x fastest; outside the grid: points = -1); n entries, or none, with lastError set, on an error.
+    // The CPU form of the same rule is host/DualContouring.h.
+    std::vector<MCTriangle> dualContour(const rto_dc_params& params, std::vector<int32_t>* triCell = nullptr, rto_dc_summary* summary = nullptr);
+    std::vector<rto_dual_vertex> dualVertices(const int64_t* voxels, int64_t n);
     // BFS numbering of setOctree (RayTracerBVH.cpp:443-490) without touching the GPU.
     static std::vector<GPUNodes> flatten(const OctreeNode* root);
     const std::vector<GPUNodes>& flatNodes() const { return m_flatNodes; }   // empty after setOctreeFromGrid

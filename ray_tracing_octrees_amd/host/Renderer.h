@@ -1,7 +1,8 @@
 // Renderer.h -- the reference's mesh-extractor interface (453-skeleton/Renderer.h:10-55) and the walk that drives it
 // (renderOctree, 453-skeleton/main.cpp:95-208): kept so that code written against them compiles.  MarchingCubesRenderer's
 // triangles also feed the leaf-triangle ray path.  These are the CPU forms; RayTracerBVH::extractMesh makes the same lists on the
-// GPU (rto_extract_mesh).  Dual contouring is outside this repo's scope.
+// GPU (rto_extract_mesh).  The reference's third renderer, AdaptiveDualContouringRenderer, is in
+// DualContouring.h (RayTracerBVH::dualContour on the GPU).
 #pragma once
 
 #include <vector>

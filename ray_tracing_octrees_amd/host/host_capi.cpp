@@ -12,6 +12,7 @@
 #include "CacheUtils.h"
 #include "Components.h"
 #include "Distance.h"
+#include "DualContouring.h"
 #include "Geodesic.h"
 #include "Skeleton.h"
 #include "Dose.h"
@@ -828,6 +829,62 @@ void* rtoh_rt_iso_surface(RayTracerBVH* rt, int source, float level, float outsi
     auto* list = new std::vector<MCTriangle>(source < 0 ? rt->offsetSurface(level) : rt->isoSurface(source, level, outside, pad != 0, volume));
     *numTris = (int64_t)list->size();
     return list;
+}
+// dualContourVolume (host/DualContouring.h), once, as rtoh_iso_surface_volume: rtoh_iso_take copies the list out and frees the handle
+void* rtoh_dual_contour_volume(const uint8_t* voxels, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize,
+                               const rto_dc_params* params, rto_dc_summary* summary, int* rc, int64_t* numTris) {
+    auto* list = new IsoList();
+    list->tris = dualContourVolume(voxels, dimX, dimY, dimZ, rto_host::vec3(gridMin[0], gridMin[1], gridMin[2]), voxelSize, *params, &list->cells,
+                                   summary, rc);
+    *numTris = (int64_t)list->tris.size();
+    return list;
+}
+// the same, timed where it runs: the milliseconds of one extraction on one core; nothing is copied
+double rtoh_dual_contour_volume_ms(const uint8_t* voxels, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize,
+                                   const rto_dc_params* params, int64_t* numTris) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<MCTriangle> tris = dualContourVolume(voxels, dimX, dimY, dimZ, rto_host::vec3(gridMin[0], gridMin[1], gridMin[2]), voxelSize, *params);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (numTris) *numTris = (int64_t)tris.size();
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
+// dualVertexVolume: out holds dimX dimY dimZ rto_dual_vertex
+void rtoh_dual_vertex_volume(const uint8_t* voxels, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize, rto_dual_vertex* out) {
+    const std::vector<rto_dual_vertex> v = dualVertexVolume(voxels, dimX, dimY, dimZ, rto_host::vec3(gridMin[0], gridMin[1], gridMin[2]), voxelSize);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(rto_dual_vertex));
+}
+// AdaptiveDualContouringRenderer on a grid of bytes: which == 0: dualVertices (out: 4 floats per voxel; *numTris untouched, NULL
+// returned); which == 1: render's top-level call, a list for rtoh_tris_take
+void* rtoh_adc_render(const uint8_t* voxels, int dimX, int dimY, int dimZ, const float gridMin[3], float voxelSize, int which, float* out,
+                      int64_t* numTris) {
+    VoxelGrid grid;
+    grid.dimX = dimX; grid.dimY = dimY; grid.dimZ = dimZ;
+    grid.minX = gridMin[0]; grid.minY = gridMin[1]; grid.minZ = gridMin[2];
+    grid.voxelSize = voxelSize;
+    grid.data.resize((size_t)dimX * dimY * dimZ);
+    for (size_t i = 0; i < grid.data.size(); i++) grid.data[i] = voxels[i] == 1 ? VoxelState::FILLED : VoxelState::EMPTY;
+    AdaptiveDualContouringRenderer r;
+    if (which == 0) {
+        const std::vector<rtmath::vec4> v = r.dualVertices(grid);
+        if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(rtmath::vec4));
+        return nullptr;
+    }
+    auto* list = new std::vector<MCTriangle>(r.render(nullptr, grid, 0, 0, 0, grid.dimX));
+    *numTris = (int64_t)list->size();
+    return list;
+}
+// RayTracerBVH::dualContour / dualVertices
+void* rtoh_rt_dual_contour(RayTracerBVH* rt, const rto_dc_params* params, rto_dc_summary* summary, int64_t* numTris) {
+    auto* list = new IsoList();
+    list->tris = rt->dualContour(*params, &list->cells, summary);
+    *numTris = (int64_t)list->tris.size();
+    return list;
+}
+int rtoh_rt_dual_vertices(RayTracerBVH* rt, const int64_t* voxels, int64_t n, rto_dual_vertex* out) {
+    const std::vector<rto_dual_vertex> v = rt->dualVertices(voxels, n);
+    if ((int64_t)v.size() != n) return 0;
+    if (n > 0) std::memcpy(out, v.data(), (size_t)n * sizeof(rto_dual_vertex));
+    return 1;
 }
 void rtoh_rt_finish(const RayTracerBVH* rt) { rt->finish(); }
 void* rtoh_rt_context(const RayTracerBVH* rt) { return rt->context(); }
